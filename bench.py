@@ -6,8 +6,10 @@
 
 One "step" = one full ALI iteration (E+G update, two D updates, diagnostics: everything in the reference's
 image_scms/mnist.py:204-248) on one synthetic MorphoMNIST-shaped batch of 512 images per GPU, inputs already
-resident in HBM.  Prints ONE JSON line on rank 0 with `roofline` (dominant kernel, timed live with HIP events on
-the launch stream in an extra instrumented iteration) and `cpu_baseline` (the CPU oracle on the host cores).
+resident in HBM.  Prints ONE JSON line on rank 0.  A plain run only sets up, warms up and times the steps; `--full`
+adds `roofline` (dominant kernel, timed live with HIP events on the launch stream in an extra instrumented iteration)
+and `cpu_baseline` (the CPU oracle on the host cores), which are null otherwise.  `--dump-outputs DIR` writes what
+the last timed step computed (dump_outputs) so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -28,6 +30,9 @@ PEAK_F16_MFMA_TFLOPS = 2500.0      # MI355X_MICROARCH.md: dense fp16 / bf16 MFMA
 PEAK_HBM_GBS = 8000.0
 # committed rocprofv3 FETCH_SIZE / WRITE_SIZE passes of `python bench.py --workload W --precision P` (scratch/collect_profiles.sh)
 TRAFFIC_CSV = "profiles/r03_pmc_hbm_traffic_{workload}_{precision}.csv"
+# --dump-outputs: at most this many bytes of array data (MorphoMNIST's whole E / G / D state, 48.2 MiB, fits; the
+# spectrogram models are sampled), which keeps the directory under 64 MB with the .npy headers
+DUMP_BYTES = 56 << 20
 
 
 def synth_batch(bs, device, seed):
@@ -99,6 +104,29 @@ def cpu_baseline(bs, budget_s=25.0):
             "sample": f"{n} ALI iterations at bs={bs} after 1 warm-up, torch {torch.__version__} CPU fp32"}
 
 
+def dump_outputs(path, losses, modules):
+    """What a caller of the timed path holds after its last step: the step's returned losses and the E / G / D state
+    (parameters, BatchNorm buffers) it updated in place, as ``path/<name>.npy`` -- float32, integer buffers float64.
+    If the whole state exceeds DUMP_BYTES, every tensor is replaced by a seeded sample of its flattened elements:
+    the sorted indices depend only on the tensor's name and size, so two runs or two builds sample the same ones."""
+    import zlib
+    import numpy as np
+    import torch
+    arrays = {k: torch.as_tensor(v).detach() for k, v in losses.items()}
+    for n, m in modules:
+        arrays.update((f"{n}.{k}", v.detach()) for k, v in m.state_dict().items())
+    total = sum(v.numel() * (4 if v.is_floating_point() else 8) for v in arrays.values())
+    os.makedirs(path, exist_ok=True)
+    for name, v in arrays.items():
+        if total > DUMP_BYTES:
+            k = max(1, v.numel() * DUMP_BYTES // total)
+            idx = np.unique(np.random.default_rng(zlib.crc32(name.encode())).integers(0, v.numel(), k))
+            v = v.reshape(-1)[torch.from_numpy(idx).to(v.device)]
+        v = v.cpu()
+        np.save(os.path.join(path, name + ".npy"),
+                v.float().numpy() if v.is_floating_point() else v.double().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -114,8 +142,15 @@ def main():
     ap.add_argument("--pipeline-reduce", action="store_true",
                     help="N > 1: overlap the last all-reduce of an iteration with the next iteration's E(x) / G(z) forward "
                          "(AliStepper(pipeline_reduce=True); same arithmetic, tests/test_gpu_dp.py)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the live roofline (extra instrumented iterations) and, for "
+                         "MorphoMNIST on one GPU, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's losses and the E / G / D state it left as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -196,52 +231,56 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
     losses = {k: float(v) for k, v in r.items()}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, r, (("E", E), ("G", G), ("D", D)))
 
-    # ---- roofline leg: ONE instrumented eager iteration on every rank (collectives stay matched); on rank 0 every GEMM
-    # launch is timed once, in sequence, with HIP events on the launch stream (ops.KernelProfile).  The stream is kept
-    # busy with replays of the timed region's own iteration while the host enqueues the instrumented one, so its kernels
-    # run back to back and at steady-state clocks; the event / dispatch overhead of an interval is calibrated on spin
-    # kernels of known length, behind the same kind of busy stream, and subtracted.
-    prof = ops.KernelProfile()
-    step_ms = dt_local / args.steps * 1e3
-    graph_mode = args.mode == "stepper" and not args.no_graph
+    prof = None
+    if args.full:
+        # ---- roofline leg: ONE instrumented eager iteration on every rank (collectives stay matched); on rank 0 every
+        # GEMM launch is timed once, in sequence, with HIP events on the launch stream (ops.KernelProfile).  The stream is
+        # kept busy with replays of the timed region's own iteration while the host enqueues the instrumented one, so its
+        # kernels run back to back and at steady-state clocks; the event / dispatch overhead of an interval is calibrated
+        # on spin kernels of known length, behind the same kind of busy stream, and subtracted.
+        prof = ops.KernelProfile()
+        step_ms = dt_local / args.steps * 1e3
+        graph_mode = args.mode == "stepper" and not args.no_graph
 
-    def eager(i):
-        if args.mode == "stepper":
-            keep, stepper.capture = stepper.capture, False
-        try:
-            return one(i)
-        finally:
+        def eager(i):
             if args.mode == "stepper":
-                stepper.capture = keep
+                keep, stepper.capture = stepper.capture, False
+            try:
+                return one(i)
+            finally:
+                if args.mode == "stepper":
+                    stepper.capture = keep
 
-    def busy(ms):
-        """enqueue about ``ms`` milliseconds of the timed region's own work (same on every rank)"""
-        if graph_mode:
-            for i in range(int(ms / step_ms) + 1):
-                one(i)
-        elif rank == 0:
-            prof.hold(ms)
+        def busy(ms):
+            """enqueue about ``ms`` milliseconds of the timed region's own work (same on every rank)"""
+            if graph_mode:
+                for i in range(int(ms / step_ms) + 1):
+                    one(i)
+            elif rank == 0:
+                prof.hold(ms)
 
-    eager(0)                    # un-instrumented eager pass first (code objects / allocator warm for this mode) ...
-    fence()
-    th = time.perf_counter()
-    eager(1)                    # ... and one to learn how long the host needs to enqueue an iteration
-    host_ms = (time.perf_counter() - th) * 1e3
-    fence()
-    cover = min(2.5 * host_ms + 20.0, 1500.0)
-    if rank == 0:
-        prof.spin_rate()
-    if rank == 0 or graph_mode:
-        busy(30.0)
-    if rank == 0:
-        prof.calibrate(busy=lambda: None)          # (the stream is busy already)
-    busy(cover)
-    if rank == 0:
-        ops.set_profile(prof)
-    eager(2)
-    ops.set_profile(None)
-    fence()
+        eager(0)                    # un-instrumented eager pass first (code objects / allocator warm for this mode) ...
+        fence()
+        th = time.perf_counter()
+        eager(1)                    # ... and one to learn how long the host needs to enqueue an iteration
+        host_ms = (time.perf_counter() - th) * 1e3
+        fence()
+        cover = min(2.5 * host_ms + 20.0, 1500.0)
+        if rank == 0:
+            prof.spin_rate()
+        if rank == 0 or graph_mode:
+            busy(30.0)
+        if rank == 0:
+            prof.calibrate(busy=lambda: None)          # (the stream is busy already)
+        busy(cover)
+        if rank == 0:
+            ops.set_profile(prof)
+        eager(2)
+        ops.set_profile(None)
+        fence()
     rank_ms = [dt_local / args.steps * 1e3]
     if world > 1:
         t = torch.tensor(rank_ms, device=dev, dtype=torch.float64)
@@ -254,7 +293,7 @@ def main():
         ms = dt / args.steps * 1e3
         value = bs * world * args.steps / dt
         per_gpu = value / world
-        fam = prof.summary() if prof.records else {}
+        fam = prof.summary() if prof is not None and prof.records else {}
         for src, dst in (("gconv_t", "gconv"), ("wgrad_multi", "wgrad")):
             # conv-forward and transposed / data-gradient launches are one kernel; so are the weight-gradient GEMMs
             # launched alone and the jobs of a combined launch (wgrad_fast_kernel / wgrad_fast_multi_kernel)
@@ -342,7 +381,7 @@ def main():
             "ms_per_step_ranks": {"min": round(min(rank_ms), 3), "max": round(max(rank_ms), 3)},
             "losses_last_step": losses,
         }
-        if world == 1 and not args.no_cpu_baseline and args.workload == "mnist":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.workload == "mnist":
             out["cpu_baseline"] = cpu_baseline(bs)
             if bs != 64:      # BASELINE.json configs[0]: the reference's own CPU-runnable case
                 out["cpu_baseline"]["config0_bs64"] = cpu_baseline(64, budget_s=8.0)

@@ -23,7 +23,7 @@ open(f"profiles/{rnd}_bench_{tag}_kernel_stats.csv", "w").write(open(stats).read
 fa, fc = per_kernel(fetch)
 wa, wc = per_kernel(write)
 with open(f"profiles/{rnd}_pmc_hbm_traffic_{tag}.csv", "w") as f:
-    f.write("# rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python3 bench.py --steps 4 "
+    f.write("# rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python3 bench.py --full --steps 4 "
             "--warmup 2 --no-cpu-baseline\n# raw counter values in KB per launch; on gfx950 FETCH_SIZE reads 1/2 of wide "
             "coalesced streams (MI355X_MICROARCH.md HBM): hbm_read ~= 2*FETCH_SIZE\n")
     f.write("kernel,launches,FETCH_SIZE_KB_per_launch,WRITE_SIZE_KB_per_launch\n")
@@ -38,7 +38,7 @@ sa, sc = per_kernel(sq)
 names = ["SQ_WAVE_CYCLES", "SQ_WAIT_ANY", "SQ_WAIT_INST_ANY", "SQ_ACTIVE_INST_ANY", "SQ_ACTIVE_INST_VALU",
          "SQ_VALU_MFMA_BUSY_CYCLES", "SQ_BUSY_CYCLES", "SQ_INSTS_VALU_MFMA_MOPS_F32"]
 with open(f"profiles/{rnd}_pmc_sq_{tag}.csv", "w") as f:
-    f.write("# rocprofv3 --kernel-trace --pmc " + " ".join(names) + " -- python3 bench.py --steps 4 --warmup 2 --no-cpu-baseline\n"
+    f.write("# rocprofv3 --kernel-trace --pmc " + " ".join(names) + " -- python3 bench.py --full --steps 4 --warmup 2 --no-cpu-baseline\n"
             "# per-launch means.  SQ_WAVE_CYCLES = WAIT_ANY (parked at s_waitcnt / barrier) + WAIT_INST_ANY (issue stall: MFMA "
             "pipe busy, dependencies) + ACTIVE_INST_ANY (issuing); these count quad-cycles, SQ_VALU_MFMA_BUSY_CYCLES counts "
             "cycles summed over SIMDs (MI355X_MICROARCH.md).  mfma_busy = MFMA_BUSY_CYCLES / (duration * clock * 1024 SIMDs) "

@@ -7,7 +7,7 @@ W=${1:-mnist}; P=${2:-f32}; STEPS=${3:-20}; PASSES=${4:-ks,fetch,write,tcc,sq}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/r03prof_${W}_${P}
 rm -rf $OUT && mkdir -p $OUT
-ARGS="--workload $W --precision $P --no-cpu-baseline"
+ARGS="--full --workload $W --precision $P --no-cpu-baseline"
 if [[ $PASSES == *ks* ]]; then
   timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ks -o ks -- python3 bench.py $ARGS --steps $STEPS --warmup 3 > $OUT/bench_under_rocprof.log 2>&1
   grep '"metric"' $OUT/bench_under_rocprof.log | tail -1 > $OUT/bench_under_rocprof.json

@@ -8,7 +8,7 @@ import csv, os, shutil, sys
 w, p = sys.argv[1], sys.argv[2]
 src = f"gpurun_out/r03prof_{w}_{p}"
 tag = f"{w}_{p}"
-cmd = f"python3 bench.py --workload {w} --precision {p} --no-cpu-baseline"
+cmd = f"python3 bench.py --full --workload {w} --precision {p} --no-cpu-baseline"
 if os.path.exists(f"{src}/kernel_stats.csv"):
     shutil.copy(f"{src}/kernel_stats.csv", f"profiles/r03_bench_{tag}_kernel_stats.csv")
     shutil.copy(f"{src}/bench_under_rocprof.json", f"profiles/r03_bench_{tag}_under_rocprof.json")

@@ -4,9 +4,9 @@ set -e -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/r03roof
 rm -rf $OUT && mkdir -p $OUT
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_plain.log 2>&1
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_plain.log 2>&1
 grep '"metric"' $OUT/bench_plain.log | tail -1 > $OUT/bench_plain.json
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ks -o ks -- python3 bench.py --steps 40 --warmup 5 --no-cpu-baseline > $OUT/bench_under_rocprof.log 2>&1
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ks -o ks -- python3 bench.py --full --steps 40 --warmup 5 --no-cpu-baseline > $OUT/bench_under_rocprof.log 2>&1
 grep '"metric"' $OUT/bench_under_rocprof.log | tail -1 > $OUT/bench_under_rocprof.json
 find $OUT/ks -name "*kernel_stats.csv" -exec cp {} $OUT/kernel_stats.csv \;
 python scratch/kstats.py $OUT/kernel_stats.csv 48 40 > $OUT/kstats.txt
