@@ -195,6 +195,45 @@ def family_of(E, G, D):
     return SpectFamily(E, G, D) if hasattr(E, "cat_keys") else MnistFamily(E, G, D)
 
 
+class _Graphed:
+    """HIP graphs of one input signature: static copies of the inputs (tensors, dicts of tensors); ``warm`` run on them
+    once on a side stream outside capture (packs, workspace, plans), then ``restore`` (a warm-up is no training step);
+    one graph per ``capture``, on the current stream, all in one pool.  A call copies inputs in and replays in order."""
+
+    def __init__(self, inputs, warm, restore=None):
+        self.inputs = [{k: x.clone() for k, x in v.items()} if isinstance(v, dict) else v.clone() for v in inputs]
+        self.graphs, self.out, self._pool = [], None, torch.cuda.graph_pool_handle()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            warm(*self.inputs)
+        torch.cuda.current_stream().wait_stream(side)
+        if restore is not None:
+            restore()
+
+    def capture(self, fn, *args):
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, pool=self._pool, capture_error_mode="thread_local"):
+            out = fn(*args)
+        self.graphs.append(g)
+        return out
+
+    def load(self, inputs):
+        ops.copy_multi([p for st, v in zip(self.inputs, inputs)
+                        for p in ([(st[k], x) for k, x in v.items()] if isinstance(v, dict) else [(st, v)])])
+
+    def __call__(self, *inputs):
+        self.load(inputs)
+        for g in self.graphs:
+            g.replay()
+        return self.out
+
+
+def _allreduce_now(flat, pg):
+    """the collective of the capture pass: synchronous (the ranks' sequences stay aligned), nothing left to wait for"""
+    dp.allreduce_sum_(flat, pg)
+
+
 class AliStepper:
     def __init__(self, E, G, D, lr=1e-4, betas=(0.5, 0.999), eps=1e-8, family=None, process_group=None,
                  capture=False, precision="f32", loss_scale=None, pipeline_reduce=False):
@@ -232,7 +271,7 @@ class AliStepper:
         self.capture = capture
         self.segmented = False     # tests: force the data-parallel (segmented) replay on a single rank
         self._capture_snapshot = None
-        self._graph = {}           # captured graphs by (input shapes, do_eg): a ragged last batch keeps its own
+        self._graph = {}           # (_Graphed, replay steps) by input shape, do_eg, ...: a ragged last batch has its own
 
         self.bn_buffers = [b for n_, b in D.named_buffers() if "running" in n_]
         self.iter_t = torch.zeros(1, dtype=torch.int64, device=self.opt_d.flat.device)
@@ -458,7 +497,7 @@ class AliStepper:
         return ((g if self._join else g.contiguous()).unflatten(1, (1, 1, cols)),)
 
     # ------------------------------------------------------------------ the iteration, phase by phase
-    def _begin(self, images, c, z, do_eg=True):
+    def _begin(self, images, c, z, do_eg=True, ahead=None):
         B = images.shape[0]
         # (iter_t = iterations completed so far: it keys this iteration's Dropout2d masks and advances at the end of the
         # iteration, in the launch that also applies the BatchNorm batch counts)
@@ -467,8 +506,11 @@ class AliStepper:
         _dropout.begin_iteration(self.iter_t, owner=self, tag=(B, bool(do_eg)))
         _chain.defer_batch_counts()
         idx, cont, onehots = self.family.conditioning(c)
-        return {"images": images, "B": B, "idx": idx, "cont": cont, "onehots": onehots,
-                "zin": z.reshape(B, -1).float().contiguous(), "out": {}}
+        cx = {"images": images, "B": B, "idx": idx, "cont": cont, "onehots": onehots,
+              "zin": z.reshape(B, -1).float().contiguous(), "out": {}}
+        if self._pipelined(do_eg):     # the E(x) / G(z) forward computed ahead (_ensure_ahead), the next batch
+            cx["eg_fwd"], cx["ahead"], self._ahead = self._ahead["fwd"], ahead, None
+        return cx
 
     def _eg_grads(self, cx):
         """E+G gradients (reference mnist.py:224-229)."""
@@ -648,31 +690,32 @@ class AliStepper:
         segs.append((lambda cx: (self._apply_d(), self._phase_scores(cx, average_bn=False)), None, True))
         return segs
 
-    def _take_ahead(self, cx, images, c, z):
-        """pipeline_reduce: the E+G phase consumes the forward passes computed ahead (by the previous ``step``'s tail,
-        or right here when this batch was not announced)"""
-        if self._ahead is None or self._ahead["fwd"] is None or self._ahead["key"] != self._batch_key(images, z):
+    def _ensure_ahead(self, images, c, z, graphed=False):
+        """pipeline_reduce: compute this batch's E(x) / G(z) forward now unless the previous ``step``'s tail computed it
+        ahead -- eagerly (its tensors at hand) or, ``graphed``, by a replayed segment into the buffers the graphs name"""
+        a = self._ahead
+        if a is None or a["key"] != self._batch_key(images, z) or (a["fwd"] is None and not graphed):
             self._prefetch(images, c, z)
-        cx["eg_fwd"], self._ahead = self._ahead["fwd"], None
 
-    def _iteration(self, images, c, z, do_eg=True, ahead=None):
-        pipe = self._pipelined(do_eg)
-        if pipe and (self._ahead is None or self._ahead["fwd"] is None or self._ahead["key"] != self._batch_key(images, z)):
-            self._prefetch(images, c, z)       # (in front of _begin: it runs its own attribute plumbing)
-        cx = self._begin(images, c, z, do_eg)
-        if pipe:
-            self._take_ahead(cx, images, c, z)
-            cx["ahead"] = ahead
+    def _run_segments(self, cx, steps, reduce):
+        """Walk a (step, group, wait) list like ``_segments``'s: a step with ``wait`` first waits for the all-reduce in
+        flight, and data parallel, ``reduce(flat, pg)`` is issued on the group's flat gradient right after its step."""
         pending = None
-        for work, group, wait in self._segments(do_eg, ahead is not None):
+        for step, group, wait in steps:
             if wait and pending is not None:
-                pending.wait()
+                pending.wait()                  # stream-level: the next step waits for the all-reduce in flight
                 pending = None
-            work(cx)
+            step(cx)
             if group is not None and self.dist:
-                pending = dp.allreduce_sum_async_(group.grad, self.pg)
+                pending = reduce(group.grad, self.pg)
         if self.dist:
             dp.average_buffers_(self.bn_buffers, self.pg)
+
+    def _iteration(self, images, c, z, do_eg=True, ahead=None):
+        if self._pipelined(do_eg):
+            self._ensure_ahead(images, c, z)    # (in front of _begin: it runs its own attribute plumbing)
+        cx = self._begin(images, c, z, do_eg, ahead)
+        self._run_segments(cx, self._segments(do_eg, ahead is not None), dp.allreduce_sum_async_)
         return cx["out"]
 
     def _state_tensors(self):
@@ -795,9 +838,7 @@ class AliStepper:
         if not self.capture:
             return self._iteration(images, c, z, do_eg, ahead)
         try:
-            if self.dist or self.segmented:
-                return self._replay_segments(images, c, z, do_eg, ahead)
-            return self._replay(images, c, z, do_eg)
+            return self._replay(images, c, z, do_eg, ahead)
         except RuntimeError as e:  # graph capture refused (driver / RCCL combination): keep training, eagerly
             if self._graph or not any(w in str(e).lower() for w in ("captur", "graph")):
                 raise              # a failure of a graph that already ran, or an error that is not about capture
@@ -808,84 +849,44 @@ class AliStepper:
                 self._restore(self._capture_snapshot)
             return self._iteration(images, c, z, do_eg)
 
-    def _replay_segments(self, images, c, z, do_eg, ahead=None):
-        """Data-parallel replay: one HIP graph per segment, the gradient all-reduces in between launched eagerly."""
-        pipe = self._pipelined(do_eg)
-        key = ("seg", tuple(images.shape), do_eg, pipe, ahead is not None)
+    def _replay(self, images, c, z, do_eg, ahead=None):
+        """The iteration from HIP graphs.  One GPU: one graph over _begin and every segment (the launch sequence of
+        _iteration).  Data parallel (or ``segmented``): one graph per segment, the gradient all-reduces in between
+        launched eagerly."""
+        split, pipe = self.dist or self.segmented, self._pipelined(do_eg)
+        key = ("seg" if split else "one", tuple(images.shape), do_eg, pipe, ahead is not None)
         if key not in self._graph:
-            st = {"images": images.clone(), "z": z.clone(), "c": {k: v.clone() for k, v in c.items()}}
-            nxt = None
-            if ahead is not None:
-                nxt = (ahead[0].clone(), {k: v.clone() for k, v in ahead[1].items()}, ahead[2].clone())
-            snap = self._snapshot()
-            self._capture_snapshot = snap
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):          # warm-up outside capture (collectives included: all ranks do this)
-                self._iteration(st["images"], st["c"], st["z"], do_eg, nxt)
+            snap = self._capture_snapshot = self._snapshot()
+
+            def warm(im, cc, zz, *nxt):         # (collectives included: all ranks do this)
+                self._iteration(im, cc, zz, do_eg, nxt or None)
                 if pipe and self._ahead is None:
-                    self._prefetch(st["images"], st["c"], st["z"])     # the persistent buffers the capture will name
-            torch.cuda.current_stream().wait_stream(s)
-            self._restore(snap)
-            pool = torch.cuda.graph_pool_handle()
-            graphs, cx = [], None
-            for i, (fn, group, wait) in enumerate(self._segments(do_eg, ahead is not None)):
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, pool=pool, capture_error_mode="thread_local"):
-                    if i == 0:
-                        cx = self._begin(st["images"], st["c"], st["z"], do_eg)
-                        if pipe:
-                            cx["eg_fwd"], cx["ahead"] = self._ahead["fwd"], nxt      # (the persistent buffers)
-                    fn(cx)
-                graphs.append((g, group, wait))
-                if group is not None and self.dist:   # keep the ranks' collective sequences aligned while capturing
-                    dp.allreduce_sum_(group.grad, self.pg)
-            if self.dist:
-                dp.average_buffers_(self.bn_buffers, self.pg)
-            self._restore(snap)                 # capture executes nothing, but the eager collectives above ran
+                    self._prefetch(im, cc, zz)  # the persistent buffers the capture will name
+            ent = _Graphed((images, c, z, *(ahead or ())), warm, lambda: self._restore(snap))
+            im, cc, zz, *nxt = ent.inputs
+            segs = self._segments(do_eg, bool(nxt))
+            if not split:                       # one graph: the launch sequence of _iteration
+                segs = [(lambda cx, ws=[w for w, _, _ in segs]: [w(cx) for w in ws], None, False)]
+
+            def first(cx, w0=segs[0][0]):       # the first graph also starts the iteration
+                cx.update(self._begin(im, cc, zz, do_eg, tuple(nxt) or None))
+                w0(cx)
+            segs[0], cx = (first,) + segs[0][1:], {}
+            self._run_segments(cx, [(lambda cx, w=w: ent.capture(w, cx), g, wt) for w, g, wt in segs], _allreduce_now)
+            if split:
+                self._restore(snap)             # capture executes nothing, but the eager collectives above ran
             self._ahead = None                  # (what the buffers hold was computed with the warm-up's weights)
-            self._graph[key] = (graphs, st, cx["out"], nxt)
-        graphs, st, res, nxt = self._graph[key]
-        ops.copy_multi([(st["images"], images), (st["z"], z)] + [(st["c"][k], v) for k, v in c.items()])
-        if nxt is not None:
-            ops.copy_multi([(nxt[0], ahead[0]), (nxt[2], ahead[2])] + [(nxt[1][k], v) for k, v in ahead[1].items()])
-        if pipe and (self._ahead is None or self._ahead["key"] != self._batch_key(images, z)):
-            self._prefetch(st["images"], st["c"], st["z"])      # this batch was not announced: compute its forward now
+            ent.out = cx["out"]
+            self._graph[key] = ent, [(lambda cx, g=g: g.replay(), gr, wt) for g, (_, gr, wt) in zip(ent.graphs, segs)]
+        ent, steps = self._graph[key]
+        ent.load((images, c, z, *(ahead or ())))
+        if pipe:
+            self._ensure_ahead(images, c, z, graphed=True)
         self._ahead = None
-        pending = None
-        for g, group, wait in graphs:
-            if wait and pending is not None:
-                pending.wait()                  # stream-level: the next graph waits for the all-reduce in flight
-                pending = None
-            g.replay()
-            if group is not None and self.dist:
-                pending = dp.allreduce_sum_async_(group.grad, self.pg)
-        if self.dist:
-            dp.average_buffers_(self.bn_buffers, self.pg)
+        self._run_segments(None, steps, dp.allreduce_sum_async_)
         if pipe and ahead is not None:          # the replayed prefetch segment left the next batch's forward in the buffers
             self._ahead = {"key": self._batch_key(ahead[0], ahead[2]), "fwd": None}
-        return res
-
-    def _replay(self, images, c, z, do_eg):
-        key = (tuple(images.shape), do_eg)
-        if key not in self._graph:
-            st = {"images": images.clone(), "z": z.clone(), "c": {k: v.clone() for k, v in c.items()}}
-            snap = self._snapshot()
-            self._capture_snapshot = snap
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):          # warm-up outside capture: packs, workspace, plans
-                self._iteration(st["images"], st["c"], st["z"], do_eg)
-            torch.cuda.current_stream().wait_stream(s)
-            self._restore(snap)                 # the warm-up must not count as a training iteration
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                res = self._iteration(st["images"], st["c"], st["z"], do_eg)
-            self._graph[key] = (graph, st, res)
-        graph, st, res = self._graph[key]
-        ops.copy_multi([(st["images"], images), (st["z"], z)] + [(st["c"][k], v) for k, v in c.items()])
-        graph.replay()
-        return res
+        return ent.out
 
 
 class FinetuneStepper:
@@ -919,29 +920,24 @@ class FinetuneStepper:
             return self._step(x, a)
         key = (tuple(x.shape), tuple((k, tuple(v.shape), v.dtype) for k, v in sorted(a.items())), self.E.training,
                self.G.training)
-        ent = self._graphs.get(key)
-        if ent is None:
-            st_x, st_a = x.clone(), {k: v.clone() for k, v in a.items()}
-            snap = [t.clone() for t in (self.opt_e.flat, self.opt_e.m, self.opt_e.v, self.opt_e.step_t)]
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                self._step(st_x, st_a)                     # warm-up outside capture: packs, workspace, plans
-            torch.cuda.current_stream().wait_stream(side)
-            for t, v in zip((self.opt_e.flat, self.opt_e.m, self.opt_e.v, self.opt_e.step_t), snap):
-                t.copy_(v)                                 # the warm-up must not count as a training step
-            self.opt_e.steps = int(self.opt_e.step_t.item())
-            self.pE.cache.refresh()
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                res = self._step(st_x, st_a)
-            ent = self._graphs[key] = (graph, st_x, st_a, res)
-        graph, st_x, st_a, res = ent
-        st_x.copy_(x)
-        for k, v in a.items():
-            st_a[k].copy_(v)
-        graph.replay()
-        return res
+        if key not in self._graphs:
+            snap = self._snapshot()
+            ent = _Graphed((x, a), self._step, lambda: self._restore(snap))
+            ent.out = ent.capture(self._step, *ent.inputs)
+            self._graphs[key] = ent
+        return self._graphs[key](x, a)
+
+    def _state_tensors(self):
+        return [self.opt_e.flat, self.opt_e.m, self.opt_e.v, self.opt_e.step_t]
+
+    def _snapshot(self):
+        return [t.clone() for t in self._state_tensors()]
+
+    def _restore(self, snap):
+        for t, v in zip(self._state_tensors(), snap):
+            t.copy_(v)
+        self.opt_e.steps = int(self.opt_e.step_t.item())
+        self.pE.cache.refresh()
 
     def _step(self, x, a):
         fam = self.family
@@ -1024,24 +1020,11 @@ class GeneratorSampler:
             return self._forward(zs, a)
         self._sync()
         key = (tuple(zs.shape), tuple((k, tuple(v.shape), v.dtype) for k, v in sorted(a.items())), self.G.training)
-        ent = self._graphs.get(key)
-        if ent is None:
-            st_z, st_a = zs.clone(), {k: v.clone() for k, v in a.items()}
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                self._forward(st_z, st_a)                  # warm-up: weight packs, workspace
-            torch.cuda.current_stream().wait_stream(side)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                res = self._forward(st_z, st_a)
-            ent = self._graphs[key] = (graph, st_z, st_a, res)
-        graph, st_z, st_a, res = ent
-        st_z.copy_(zs)
-        for k, v in a.items():
-            st_a[k].copy_(v)
-        graph.replay()
-        return res
+        if key not in self._graphs:
+            ent = _Graphed((zs, a), self._forward)
+            ent.out = ent.capture(self._forward, *ent.inputs)
+            self._graphs[key] = ent
+        return self._graphs[key](zs, a)
 
 
 def _mnist_family_eg(E, G):
