@@ -1054,8 +1054,14 @@ def g_input_table_grad(onehot, g, off, out):
 
 
 def adam(p, g, m, v, lr, beta1, beta2, eps, step, dev_step=None, grad_scale=1.0, arrive=None, p16=None):
-    """``arrive`` (zeroed int32 device tensor): ``dev_step`` counts COMPLETED steps and the launch advances it itself;
-    ``p16`` (fp16, same numel): the launch also leaves the fp16 twin of the updated parameters (include/ali_hip.h: ali_adam)."""
+    """One torch.optim.Adam step over a flat fp32 segment; the gradient is read as ``grad_scale * g``.
+    Step conventions (include/ali_hip.h: ali_adam):
+    - ``dev_step`` None: ``step`` is the 1-based number of this step (>= 1);
+    - ``dev_step`` without ``arrive``: the int32 device scalar holds the 1-based number of this step and is left as it
+      is.  It must be >= 1: a count of completed steps (0 before the first) would give bias correction 1 - beta1^0 = 0;
+    - ``dev_step`` with ``arrive`` (zeroed int32 device tensor, left at zero): ``dev_step`` counts COMPLETED steps, the
+      launch runs step ``dev_step + 1`` and stores that value back itself.
+    ``p16`` (fp16, same numel): the launch also leaves the fp16 twin of the updated parameters."""
     lib = _lib.load()
     ds = ar = None
     if dev_step is not None:
@@ -1070,7 +1076,8 @@ def adam(p, g, m, v, lr, beta1, beta2, eps, step, dev_step=None, grad_scale=1.0,
 
 
 def add_i64_multi(counters, incs):
-    """counters[i] += incs[i] for int64 device scalars, one launch (include/ali_hip.h: ali_add_i64_multi)"""
+    """counters[i] += incs[i] for int64 device scalars, one launch per 16 counters (include/ali_hip.h:
+    ali_add_i64_multi); a counter named twice receives both increments"""
     n = len(counters)
     if n == 0:
         return

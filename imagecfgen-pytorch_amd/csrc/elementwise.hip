@@ -789,11 +789,13 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
 }
 
 // several int64 counters += their increments in one launch (num_batches_tracked of every BatchNorm2d, the iteration counter)
+// One thread applies the <= 16 jobs in order, so a counter named twice receives both increments (one lane per job
+// would read the same old value twice and lose one of them).
 constexpr int kAddJobs = 16;
 struct AddJobs { int n; long long* ptr[kAddJobs]; long long inc[kAddJobs]; };
 __global__ void add_i64_multi_kernel(const AddJobs jobs) {
-  const int i = threadIdx.x;
-  if (i < jobs.n) jobs.ptr[i][0] += jobs.inc[i];
+  if (threadIdx.x != 0) return;
+  for (int i = 0; i < jobs.n; ++i) jobs.ptr[i][0] += jobs.inc[i];
 }
 
 
@@ -1488,7 +1490,7 @@ extern "C" int ali_add_i64_multi(int32_t n, int64_t* const* ptrs, const int64_t*
       aj.ptr[aj.n] = reinterpret_cast<long long*>(ptrs[i]);
       aj.inc[aj.n++] = incs[i];
     }
-    hipLaunchKernelGGL(add_i64_multi_kernel, dim3(1), dim3(64), 0, ST(stream), aj);
+    hipLaunchKernelGGL(add_i64_multi_kernel, dim3(1), dim3(1), 0, ST(stream), aj);
     int rc = check_launch("add_i64_multi_kernel");
     if (rc) return rc;
   }

@@ -345,7 +345,8 @@ int ali_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, 
              float eps, int32_t step, int32_t* dev_step, int32_t* arrive, float grad_scale, void* p16,
              ali_stream_t stream);
 /* counters[i][0] += incs[i] for n device int64 counters in one launch (nn.BatchNorm2d.num_batches_tracked of every
- * layer, mnist.py:111-123 forward in train mode; the stepper's iteration counter). */
+ * layer, mnist.py:111-123 forward in train mode; the stepper's iteration counter).  A counter may be named more than
+ * once: it receives every increment. */
 int ali_add_i64_multi(int32_t n, int64_t* const* counters, const int64_t* incs, ali_stream_t stream);
 
 /* BCEWithLogitsLoss of two passes batched along the rows, rows [0,B) against target_a and [B,2B) against target_b
