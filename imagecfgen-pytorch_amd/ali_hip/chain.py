@@ -9,10 +9,12 @@ and executed as ONE autograd node: forward runs the NHWC kernels stage by stage,
 backward is hand scheduled -- the activation derivative of stage i-1 (and the
 Dropout2d mask in front of stage i) is folded into the epilogue of stage i's
 data-gradient GEMM, BatchNorm backward is fused with the LeakyReLU derivative.
+Which kernel serves a stage -- forward, weight gradient, data gradient -- is decided in one place (``route``).
 The ``nn`` modules only own the parameters (reference layouts, reference
 ``state_dict`` keys); their own ``forward`` is never called on CUDA tensors.
 """
 import weakref
+from collections import namedtuple
 from typing import List, Optional
 
 import torch
@@ -28,11 +30,17 @@ def _pad4(c: int) -> int:
 
 
 class Stage:
-    __slots__ = ("kind", "mod", "act", "slope", "pre", "unflat", "index")
+    """One convolution (or Linear) of the stack with what sits in front of it (``pre``: ("drop", p) / ("bn", module)
+    in module order; ``pattern``: their kinds) and the activation behind it."""
+    __slots__ = ("kind", "mod", "act", "slope", "pre", "pattern", "has_drop", "drop_p", "bn", "unflat", "index")
 
     def __init__(self, kind, mod, pre, index):
         self.kind, self.mod, self.pre, self.index = kind, mod, pre, index
         self.act, self.slope, self.unflat = ACT_NONE, 0.0, None
+        self.pattern = [k for k, _ in pre]
+        self.has_drop = "drop" in self.pattern
+        self.drop_p = next((a for k, a in pre if k == "drop"), None)
+        self.bn = next((a for k, a in pre if k == "bn"), None)
 
 
 class PackCache:
@@ -108,16 +116,19 @@ class ChainPlan:
         if pre:
             raise NotImplementedError("trailing Dropout2d/BatchNorm2d without a convolution")
         for st in self.stages:
-            kinds = [p[0] for p in st.pre]
-            if kinds not in ([], ["drop"], ["bn"], ["drop", "bn"], ["bn", "drop"]):
-                raise NotImplementedError(f"unsupported pre-op pattern {kinds}")
+            if st.pattern not in ([], ["drop"], ["bn"], ["drop", "bn"], ["bn", "drop"]):
+                raise NotImplementedError(f"unsupported pre-op pattern {st.pattern}")
+
+    @property
+    def out_channels(self) -> int:
+        """channels of the last stage's output"""
+        return _out_shape(self.stages[-1], 1, 1, 1, 1)[3]
 
     def params(self) -> List[torch.Tensor]:
         out = []
         for st in self.stages:
-            for kind, m in st.pre:
-                if kind == "bn":
-                    out += [m.weight, m.bias]
+            if st.bn is not None:
+                out += [st.bn.weight, st.bn.bias]
             out.append(st.mod.weight)
             if st.mod.bias is not None:
                 out.append(st.mod.bias)
@@ -246,45 +257,74 @@ def _geom(st: Stage, xin_shape, out_shape):
     return ops.geom(B, 1, 1, C, 1, 1, P * Q * K, 1, 1, 1, 0)
 
 
-def _is_tconv1(st: Stage, cin_stride: int) -> bool:
-    """ConvTranspose2d(C -> 1), stride 1, no output padding: served by the direct one-channel kernels."""
-    m = st.mod
-    return (st.kind == "convT" and m.out_channels == 1 and m.stride[0] == 1 and m.output_padding[0] == 0
-            and m.kernel_size[0] <= 5 and cin_stride in (32, 64, 128, 256) and st.act in (ACT_NONE, ACT_LEAKY, ACT_TANH))
+class Route(namedtuple("Route", "fwd wgrad wgrad_fold dgrad planes fold_ok bn_leave bn_reduce")):
+    """Which kernels serve one stage: decided once by ``route`` from the stage, its input shape and its logical input
+    channels, saved by the forward pass and read by the backward pass.  What only a call knows (a mask that was folded,
+    a FoldQueue, strided or non-contiguous operands, the workspace size) stays at the call, once per fact.
+
+    fwd         "head" (GEMV) | "tconv1" (direct one-channel kernel) | "scatter" (scatter form, one launch) |
+                "scatter_gemm" (1x1 GEMM + col2im) | "convT" | "conv" (implicit GEMMs; a Linear is a 1x1 "conv").  Only
+                the GEMMs have an epilogue: a "head" / "scatter*" stage that has to fold the next stage's mask or leave
+                BatchNorm partials runs the GEMM of its kind instead.
+    wgrad       (weight-gradient path, bias-gradient path): "head" | "first_direct" (ali_tconv1_wgrad over the <= 8
+                input planes) | "conv" | "tconv1" | "convT_scatter" (pixel contraction; the GEMM when the operands or
+                the workspace do not allow it) | "convT" | "linear" | "linear_repack"; the bias gradient is "fused"
+                into that launch, a "colsum" of its own, the "unflat" column sum in Unflatten order, or None (no bias).
+    wgrad_fold  the same when the launches are deferred to a FoldQueue: a "first_direct" stage with 4-aligned channels
+                then rides the pass's combined weight-gradient launch as one more GEMM job (its 200 x 32 GEMM fills gaps
+                there and the bias gradient comes along: measured 7.15 -> 7.08 ms per MNIST iteration).
+    dgrad       "tconv1" (direct; the "convT" GEMM when a mask or BatchNorm sits in front) | "convT" | "conv"
+    planes      first stage asked for a few input planes only (``gx_planes``): "direct" (one ali_tconv1_fwd per plane) |
+                "scatter" (scatter form, when the plane count allows it: ``_plane_grads``) | None (full data gradient)
+    fold_ok     the forward may apply a lone Dropout2d mask of the next stage in its epilogue
+    bn_leave    the forward GEMM may leave the partial sums of a BatchNorm behind it
+    bn_reduce   the data-gradient GEMM may leave the partial sums of the BatchNorm backward in front of it"""
 
 
-def _is_head(st: Stage, in_shape) -> bool:
-    """Conv2d(C, 1, 1) on a 1x1 map without activation (the Discriminator's last layer, mnist.py:127): a GEMV"""
-    m = st.mod
-    return (st.kind == "conv" and m.out_channels == 1 and tuple(m.kernel_size) == (1, 1) and m.stride[0] == 1
-            and m.padding[0] == 0 and in_shape[1] == 1 and in_shape[2] == 1 and in_shape[3] % 4 == 0
-            and st.act == ACT_NONE)
-
-
-def _scatter_fwd(st: Stage, cin_stride: int) -> bool:
-    """ConvTranspose2d with one or two output channels that the direct kernels do not cover (stride 2 Generator tails of
-    the spectrogram models): per-input-pixel tap contributions by a 1x1 GEMM with N = Cout*R*S columns, then
-    ali_col2im -- an implicit GEMM over the output pixels would use 1/32 of every MFMA tile."""
-    m = st.mod
-    return (st.kind == "convT" and m.out_channels <= 2 and m.out_channels * m.kernel_size[0] * m.kernel_size[1] <= 64
-            and cin_stride % 4 == 0)
-
-
-def _scatter_dgrad(st: Stage, planes) -> bool:
-    """The few consumed input planes of a first Conv2d's data gradient, same scatter form.  The contribution tensor
-    (planes * taps floats per pixel, written and read once) makes it HBM bound: measured break-even with the implicit
-    GEMM at about 6 planes of a 5x5 filter, a clear win below."""
-    m = st.mod
-    return (st.kind == "conv" and planes is not None and 1 <= len(planes) <= 8 and m.out_channels % 4 == 0
-            and len(planes) * m.kernel_size[0] * m.kernel_size[1] <= 128)
-
-
-def _first_conv_direct(st: Stage, c_in_log: int) -> bool:
-    """First Conv2d of a stack (<= 8 real input channels, stride 1): per-channel direct weight gradient and
-    single-plane data gradient (ali_tconv1_*)."""
-    m = st.mod
-    return (st.kind == "conv" and m.stride[0] == 1 and c_in_log <= 8 and m.out_channels in (32, 64, 128, 256)
-            and m.kernel_size[0] <= 5)
+def route(st: Stage, in_shape, c_log: int) -> Route:
+    """The stage's Route for an input [B,H,W,Cp] = ``in_shape`` with ``c_log`` real channels (B does not matter)."""
+    m, Cp = st.mod, in_shape[3]
+    taps = m.kernel_size[0] * m.kernel_size[1] if st.kind != "linear" else 1
+    # ConvTranspose2d(C -> 1), stride 1, no output padding: served by the direct one-channel kernels
+    tconv1 = (st.kind == "convT" and m.out_channels == 1 and m.stride[0] == 1 and m.output_padding[0] == 0
+              and m.kernel_size[0] <= 5 and Cp in (32, 64, 128, 256))
+    # first Conv2d of a stack (<= 8 real input channels, stride 1): per-channel direct weight gradient and single-plane
+    # data gradient (ali_tconv1_*)
+    first_direct = (st.index == 0 and st.kind == "conv" and m.stride[0] == 1 and c_log <= 8
+                    and m.out_channels in (32, 64, 128, 256) and m.kernel_size[0] <= 5)
+    gemm = "convT" if st.kind == "convT" else "conv"
+    if (st.kind == "conv" and m.out_channels == 1 and taps == 1 and m.stride[0] == 1 and m.padding[0] == 0
+            and tuple(in_shape[1:3]) == (1, 1) and Cp % 4 == 0 and st.act == ACT_NONE):
+        fwd = "head"      # Conv2d(C, 1, 1) on a 1x1 map without activation (the Discriminator's last layer, mnist.py:127)
+    elif tconv1:          # (the register-blocked tconv1_fwd beats the scatter form on the MNIST tail by 17 us per launch)
+        fwd = "tconv1"
+    elif st.kind == "convT" and m.out_channels <= 2 and m.out_channels * taps <= 64 and Cp % 4 == 0:
+        # one or two output channels that the direct kernels do not cover (stride 2 Generator tails of the spectrogram
+        # models): per-input-pixel tap contributions by a 1x1 GEMM with N = Cout*R*S columns, then ali_col2im -- an
+        # implicit GEMM over the output pixels would use 1/32 of every MFMA tile -- or, contributions kept in LDS per
+        # output tile, one launch and no [pixels][taps] tensor
+        fwd = "scatter" if ops.tconv_scatter_ok(Cp, m.out_channels, *m.kernel_size, m.stride[0]) else "scatter_gemm"
+    else:
+        fwd = gemm
+    bias = None if m.bias is None else "colsum"
+    if st.kind == "linear":
+        wgrad = ("linear" if not st.unflat or st.unflat[1] * st.unflat[2] == 1 else "linear_repack",
+                 bias and ("unflat" if st.unflat else "colsum"))
+    elif st.kind == "convT":      # (one-channel stride-2 tail of 64 channels: ali_tconv_scatter_wgrad)
+        wgrad = ("tconv1" if tconv1 else "convT_scatter" if (m.out_channels, Cp, c_log) == (1, 64, 64) else "convT", bias)
+    else:   # Conv2d: the bias gradient is the column sum of the dense wgrad operand -> fused into that launch
+        wgrad = ("head" if fwd == "head" else "conv", bias and "fused")
+    wgrad_fold = wgrad
+    if first_direct:
+        wgrad = ("first_direct", bias)
+        if Cp % 4 != 0:                   # (no GEMM job for the combined launch either)
+            wgrad_fold = wgrad
+    planes = None
+    if st.index == 0 and st.bn is None and st.kind == "conv":
+        planes = "direct" if first_direct else "scatter" if m.out_channels % 4 == 0 else None
+    return Route(fwd, wgrad, wgrad_fold, dgrad="tconv1" if tconv1 else gemm, planes=planes,
+                 fold_ok=st.kind != "linear" and st.act in (ACT_NONE, ACT_LEAKY) and not tconv1,
+                 bn_leave=st.kind == "conv", bn_reduce=st.kind != "linear" and not tconv1)
 
 
 _NBT = {"pending": None}
@@ -328,7 +368,9 @@ def flush_batch_counts(extra=()):
 
 
 class _Saved:
-    __slots__ = ("x_in", "t", "y", "mask", "bn_stats", "bn", "pattern", "geom", "in_shape", "out_shape", "training")
+    """what the forward pass keeps of one stage for the backward pass"""
+    __slots__ = ("x_in", "t", "y", "mask", "bn_stats", "bn", "pattern", "geom", "route", "c_log", "in_shape", "out_shape",
+                 "training")
 
 
 def slice_saved(saved, group: int, groups: int):
@@ -341,7 +383,7 @@ def slice_saved(saved, group: int, groups: int):
         s2 = _Saved()
         s2.x_in, s2.t, s2.y = sv.x_in[lo:hi], sv.t[lo:hi], sv.y[lo:hi]
         s2.mask = None if sv.mask is None else sv.mask[lo:hi]
-        s2.bn, s2.pattern, s2.training = sv.bn, sv.pattern, sv.training
+        s2.bn, s2.pattern, s2.training, s2.route, s2.c_log = sv.bn, sv.pattern, sv.training, sv.route, sv.c_log
         s2.bn_stats = None if sv.bn_stats is None else (sv.bn_stats[group] if isinstance(sv.bn_stats, list)
                                                         else sv.bn_stats)
         s2.in_shape, s2.out_shape = (B,) + tuple(sv.in_shape[1:]), (B,) + tuple(sv.out_shape[1:])
@@ -363,7 +405,7 @@ def _fwd_pack_strides(st: Stage):
         return (R * S * C, 1, S * C, C) if C % 4 == 0 else None
     if st.kind == "convT":
         Ci, Co, R, S = w.shape
-        if Ci % 32 != 0 or _is_tconv1(st, Ci) or _scatter_fwd(st, Ci):
+        if Ci % 32 != 0 or route(st, (1, 1, 1, Ci), Ci).fwd != "convT":     # (a ConvT's route does not look at H, W)
             return None
         return (1, R * S * Ci, S * Ci, Ci)
     return None
@@ -442,6 +484,99 @@ def chain_backward(*args, **kwargs):
     return drive(chain_backward_gen(*args, **kwargs))
 
 
+def _pre_ops(st: Stage, sv, bn_part, mask_applied: bool, groups: int):
+    """What sits in front of the stage's convolution: the Dropout2d mask ``sv.mask`` (unless the producer applied it)
+    and / or BatchNorm -- batch statistics from the partial sums ``bn_part`` = (partials, slots) the producing conv
+    left behind, else by a pass of their own.  Sets ``sv.bn_stats`` and returns the convolution's input."""
+    cur, mask, bn = sv.x_in, sv.mask, st.bn
+    B, H, W, Cp = sv.in_shape
+    rows = H * W
+    sv.bn_stats = None
+    if bn is None:
+        return ops.rowmask_mul(cur, mask, B, rows, Cp) if (mask is not None and not mask_applied) else cur
+    mask_in = mask if st.pattern == ["drop", "bn"] else None
+    mask_post = mask if st.pattern == ["bn", "drop"] else None
+    use_batch = sv.training or bn.running_mean is None
+    momentum = bn.momentum if bn.momentum is not None else 0.1
+    if bn_part is not None:
+        stg = ops.bn_stats_from_partials(bn_part[0], bn_part[1], groups, Cp, (B // groups) * rows, bn.weight.detach(),
+                                         bn.bias.detach(), bn.running_mean, bn.running_var, momentum, bn.eps)
+    else:                       # per-pass statistics / running-stat updates, one launch for all passes
+        stg = ops.bn_stats(cur, mask_in, B, rows, Cp, bn.weight.detach(), bn.bias.detach(), bn.running_mean,
+                           bn.running_var, momentum, bn.eps, use_batch, groups=groups)
+    if use_batch and bn.num_batches_tracked is not None:
+        for _ in range(groups):
+            _count_batch(bn)
+    sv.bn_stats = stg if groups == 1 else [stg[gi] for gi in range(groups)]
+    return ops.bn_apply(cur, stg, mask_in, mask_post, B, rows, Cp, groups=groups)
+
+
+def _for_next_stage(nxt: Stage, sv, groups: int, lane):
+    """What this stage's GEMM epilogue does for the pre-ops of the next stage: (folded, early, bn_fwd).
+    ``folded``: a lone Dropout2d in front of the next stage multiplies this stage's output by a per-(sample, channel)
+    mask: the GEMM epilogue does it (act(.)*mask), so y is stored masked.  LeakyReLU'(y) only needs the sign of y,
+    which the kept entries preserve and the dropped ones do not need (their gradient is masked to 0).
+    ``bn_fwd``: the batch statistics of a BatchNorm behind this conv are column sums of this stage's output --
+    accumulated per M-tile by the GEMM epilogue (times the Dropout2d mask ``early`` that may sit in between, which is
+    drawn here for that), no extra pass."""
+    B, P, Q, K = sv.out_shape
+    draw = lambda: _dropout.next_mask(B, K, nxt.drop_p, sv.x_in.device, K, lane=lane)      # noqa: E731
+    if sv.training and nxt.pattern == ["drop"] and sv.route.fold_ok:
+        return draw(), None, None
+    early = bn_fwd = None
+    if nxt.bn is not None and sv.route.bn_leave and (sv.training or nxt.bn.running_mean is None):
+        if sv.training and nxt.pattern == ["drop", "bn"]:
+            early = draw()
+        slots, tile_rows, pixel_major = ops.conv_mtiles(sv.geom, 0)
+        rows_g = (B // groups) * (1 if pixel_major else P * Q)
+        if slots > 0 and (groups == 1 or (B % groups == 0 and rows_g % tile_rows == 0
+                                          and (not pixel_major or B % tile_rows == 0))):
+            part = torch.empty(2 * K * slots, dtype=torch.float32, device=sv.x_in.device)
+            bn_fwd = (part, groups, early, slots)
+    return None, early, bn_fwd
+
+
+def _launch_fwd(plan: ChainPlan, st: Stage, sv, folded, bn_fwd, out_ld: int, jmask, alloc):
+    """The stage's convolution sv.t -> sv.y on the kernel of its route (generator: yields after a GEMM request)."""
+    t, y, m, c_log = sv.t, sv.y, st.mod, sv.c_log
+    B, H, W, Cp = sv.in_shape
+    _, P, Q, K = sv.out_shape
+    bias = plan.packed_bias(st)
+    path = sv.route.fwd
+    if path in ("head", "scatter", "scatter_gemm") and (folded is not None or bn_fwd is not None):
+        path = st.kind                    # these kernels have no epilogue: the GEMM of the stage's kind does the work
+    if path == "scatter" and not t.is_contiguous():
+        path = "scatter_gemm"
+    if path == "head":                    # (never the end of a join: join_ok needs K % 4 == 0, so out_ld == 0)
+        ops.head_fwd(t.reshape(B, Cp), plan.packed(st, "fwd", Cp).reshape(-1), bias, y.reshape(B))
+    elif path == "tconv1":
+        ops.tconv1_fwd(t, plan.packed(st, "fwd", Cp), bias, y, B, H, W, Cp, m.kernel_size[0], m.kernel_size[1],
+                       m.padding[0], 1, st.act, st.slope)
+    elif path == "scatter":
+        ops.tconv_scatter(t, plan.packed(st, "scatter", Cp), bias, y, B, H, W, Cp, P, Q, K, K, *m.kernel_size,
+                          m.stride[0], m.padding[0], st.act, st.slope)
+    elif path == "scatter_gemm":
+        R, S = m.kernel_size
+        contrib = (alloc(("contrib", st.index), (B, H, W, K * R * S)) if alloc is not None
+                   else torch.empty(B, H, W, K * R * S, dtype=torch.float32, device=t.device))
+        ops.conv_fwd(ops.geom(B, H, W, Cp, H, W, K * R * S, 1, 1, 1, 0), t, plan.packed(st, "scatter", Cp), contrib,
+                     ops.epilogue(), live=(c_log, None))
+        yield
+        ops.col2im(contrib, K * R * S, bias, y, B, H, W, P, Q, K, K, R, S, m.stride[0], m.padding[0], st.act, st.slope)
+    else:
+        ep = ops.epilogue(bias=bias, act=st.act, slope=st.slope, mask=folded, bn_fwd=bn_fwd)
+        if jmask is not None:
+            ep.mask, ep.mask_ld = jmask.data_ptr(), jmask.stride(0)
+            ep.refs["mask"] = jmask
+        if st.index == 0 and st.kind == "conv" and c_log < Cp:
+            ep.in_ch_live = c_log          # channel padding of a first layer: kernels that can skip it do
+        if path == "convT":
+            ops.conv_bwd_data(sv.geom, t, plan.packed(st, "fwd", Cp), y, ep, live=(None, c_log))
+        else:
+            ops.conv_fwd(sv.geom, t, plan.packed(st, "fwd", Cp), y, ep, out_ld=out_ld, live=(c_log, None))
+        yield
+
+
 def chain_forward_gen(plan: ChainPlan, x: torch.Tensor, training: bool, c_log_in: int, save: bool, groups: int = 1,
                       join=None, first_mask_applied: bool = False, lane=None, alloc=None):
     """Generator form of the forward pass (see ``run_parallel``): yields after every GEMM request.
@@ -460,145 +595,190 @@ def chain_forward_gen(plan: ChainPlan, x: torch.Tensor, training: bool, c_log_in
     convolutions run once over all of them; BatchNorm takes its batch statistics -- and updates the running ones --
     pass by pass, in order, exactly as separate calls would."""
     saved = []
-    cur = x
-    c_log = c_log_in
+    cur, c_log = x, c_log_in
     folded = None        # mask of the coming stage, already applied by the previous stage's GEMM epilogue
     early = None         # mask of the coming stage, requested early (its BatchNorm statistics needed it), not applied
-    bn_part = None       # (partials, slots) of the coming stage's BatchNorm, left by the previous stage's GEMM epilogue
+    bn_fwd = None        # (partials, groups, early, slots) of the coming stage's BatchNorm, left by the previous GEMM
     for si, st in enumerate(plan.stages):
         B, H, W, Cp = cur.shape
-        rows = H * W
-        kinds = [p[0] for p in st.pre]
-        mask = None
-        bn = None
-        mask_applied = folded is not None or (si == 0 and first_mask_applied)
-        if folded is not None:
-            mask, folded = folded, None
-        elif early is not None:
-            mask, early = early, None
-        for kind, arg in st.pre:
-            if kind == "drop" and training and mask is None:
-                mask = _dropout.next_mask(B, c_log, arg, cur.device, Cp, lane=lane)
-            elif kind == "bn":
-                bn = arg
-        sv = _Saved()
-        sv.x_in, sv.mask, sv.bn, sv.training = cur, mask, bn, training
-        sv.pattern = kinds
-        sv.bn_stats = None
-        t = cur
-        if bn is not None:
-            mask_in = mask if kinds == ["drop", "bn"] else None
-            mask_post = mask if kinds == ["bn", "drop"] else None
-            use_batch = training or bn.running_mean is None
-            momentum = bn.momentum if bn.momentum is not None else 0.1
-            if bn_part is not None:     # batch statistics from the partial sums the producing conv left behind
-                part, slots = bn_part
-                bn_part = None
-                stg = ops.bn_stats_from_partials(part, slots, groups, Cp, (B // groups) * rows, bn.weight.detach(),
-                                                 bn.bias.detach(), bn.running_mean, bn.running_var, momentum, bn.eps)
-            else:                       # per-pass statistics / running-stat updates, one launch for all passes
-                stg = ops.bn_stats(cur, mask_in, B, rows, Cp, bn.weight.detach(), bn.bias.detach(), bn.running_mean,
-                                   bn.running_var, momentum, bn.eps, use_batch, groups=groups)
-            if use_batch and bn.num_batches_tracked is not None:
-                for _ in range(groups):
-                    _count_batch(bn)
-            t = ops.bn_apply(cur, stg, mask_in, mask_post, B, rows, Cp, groups=groups)
-            sv.bn_stats = stg if groups == 1 else [stg[gi] for gi in range(groups)]
-        elif mask is not None and not mask_applied:
-            t = ops.rowmask_mul(cur, mask, B, rows, Cp)
-        out_shape = _out_shape(st, B, H, W, Cp)
-        g = _geom(st, (B, H, W, Cp), out_shape)
         nxt = plan.stages[si + 1] if si + 1 < len(plan.stages) else None
-        out_ld = 0
-        jmask = None
+        sv = _Saved()
+        sv.x_in, sv.bn, sv.pattern, sv.training, sv.c_log = cur, st.bn, st.pattern, training, c_log
+        sv.in_shape, sv.out_shape = (B, H, W, Cp), _out_shape(st, B, H, W, Cp)
+        sv.geom, sv.route = _geom(st, sv.in_shape, sv.out_shape), route(st, sv.in_shape, c_log)
+        sv.mask = folded if folded is not None else early
+        if sv.mask is None and st.has_drop and training:
+            sv.mask = _dropout.next_mask(B, c_log, st.drop_p, cur.device, Cp, lane=lane)
+        sv.t = _pre_ops(st, sv, bn_fwd and (bn_fwd[0], bn_fwd[3]), folded is not None or (si == 0 and first_mask_applied),
+                        groups)
+        K = sv.out_shape[3]
+        out_ld, jmask = 0, None
         if nxt is None and join is not None:
             joint, joff, jm = join
-            if out_shape[1] != 1 or out_shape[2] != 1 or joint.shape[0] != B or not join_ok(plan):
+            if sv.out_shape[1:3] != (1, 1) or joint.shape[0] != B or not join_ok(plan):
                 raise ValueError("chain_forward(join=...): the last stage must be a plain conv GEMM onto a 1x1 map")
             out_ld = joint.shape[1]
-            y = joint[:, joff:joff + out_shape[3]].unflatten(1, (1, 1, out_shape[3]))     # [B,1,1,K] view, rows out_ld apart
-            jmask = None if jm is None else jm[:, joff:joff + out_shape[3]]
+            sv.y = joint[:, joff:joff + K].unflatten(1, (1, 1, K))     # [B,1,1,K] view, rows out_ld apart
+            jmask = None if jm is None else jm[:, joff:joff + K]
         else:
-            y = (alloc(("y", si), out_shape) if alloc is not None
-                 else torch.empty(out_shape, dtype=torch.float32, device=cur.device))
-        nk = [p[0] for p in nxt.pre] if nxt is not None else []
-        plain_gemm = st.kind in ("conv", "convT") and not _is_tconv1(st, Cp) and not _scatter_fwd(st, Cp)
-        # A lone Dropout2d in front of the next stage multiplies this stage's output by a per-(sample, channel)
-        # mask: the GEMM epilogue does it (act(.)*mask), so y is stored masked.  LeakyReLU'(y) only needs the sign
-        # of y, which the kept entries preserve and the dropped ones do not need (their gradient is masked to 0).
-        if (training and nk == ["drop"] and st.act in (ACT_NONE, ACT_LEAKY) and st.kind in ("conv", "convT")
-                and not _is_tconv1(st, Cp)):
-            folded = _dropout.next_mask(B, out_shape[3], nxt.pre[0][1], cur.device, out_shape[3], lane=lane)
-        # A BatchNorm behind this conv: its batch statistics are column sums of this stage's output -- accumulated
-        # per M-tile by the GEMM epilogue (times the Dropout2d mask that may sit in between), no extra pass
-        bn_fwd = None
-        if "bn" in nk and st.kind == "conv" and plain_gemm and folded is None:
-            nbn = [a for k, a in nxt.pre if k == "bn"][0]
-            if training or nbn.running_mean is None:
-                if training and nk == ["drop", "bn"]:
-                    early = _dropout.next_mask(B, out_shape[3], nxt.pre[0][1], cur.device, out_shape[3], lane=lane)
-                slots, tile_rows, pixel_major = ops.conv_mtiles(g, 0)
-                rows_g = (B // groups) * (1 if pixel_major else out_shape[1] * out_shape[2])
-                if slots > 0 and (groups == 1 or (B % groups == 0 and rows_g % tile_rows == 0
-                                                  and (not pixel_major or B % tile_rows == 0))):
-                    part = torch.empty(2 * out_shape[3] * slots, dtype=torch.float32, device=cur.device)
-                    bn_part = (part, slots)
-                    bn_fwd = (part, groups, early, slots)
-        ep = ops.epilogue(bias=plan.packed_bias(st), act=st.act, slope=st.slope, mask=folded, bn_fwd=bn_fwd)
-        if jmask is not None:
-            ep.mask, ep.mask_ld = jmask.data_ptr(), jmask.stride(0)
-            ep.refs["mask"] = jmask
-        if si == 0 and st.kind == "conv" and c_log < Cp:
-            ep.in_ch_live = c_log          # channel padding of a first layer: kernels that can skip it do
-        # (the register-blocked tconv1_fwd beats the scatter form on the MNIST tail by 17 us per launch; the scatter
-        # form serves the stride-2 / two-channel tails of the spectrogram Generators)
-        if _is_head(st, (B, H, W, Cp)) and folded is None and bn_fwd is None and not out_ld:
-            ops.head_fwd(t.reshape(B, Cp), plan.packed(st, "fwd", Cp).reshape(-1), plan.packed_bias(st), y.reshape(B))
-        elif _scatter_fwd(st, Cp) and folded is None and not _is_tconv1(st, Cp):
-            m = st.mod
-            R, S = m.kernel_size
-            Co = m.out_channels
-            if ops.tconv_scatter_ok(Cp, Co, R, S, m.stride[0]) and t.is_contiguous():
-                # contributions kept in LDS per output tile: one launch, no [pixels][taps] tensor
-                ops.tconv_scatter(t, plan.packed(st, "scatter", Cp), plan.packed_bias(st), y, B, H, W, Cp, out_shape[1],
-                                  out_shape[2], Co, Co, R, S, m.stride[0], m.padding[0], st.act, st.slope)
-            else:
-                contrib = (alloc(("contrib", si), (B, H, W, Co * R * S)) if alloc is not None
-                           else torch.empty(B, H, W, Co * R * S, dtype=torch.float32, device=cur.device))
-                ops.conv_fwd(ops.geom(B, H, W, Cp, H, W, Co * R * S, 1, 1, 1, 0), t, plan.packed(st, "scatter", Cp),
-                             contrib, ops.epilogue(), live=(c_log, None))
-                yield
-                ops.col2im(contrib, Co * R * S, plan.packed_bias(st), y, B, H, W, out_shape[1], out_shape[2], Co, Co, R,
-                           S, m.stride[0], m.padding[0], st.act, st.slope)
-        elif _is_tconv1(st, Cp):
-            m = st.mod
-            ops.tconv1_fwd(t, plan.packed(st, "fwd", Cp), plan.packed_bias(st), y, B, H, W, Cp, m.kernel_size[0],
-                           m.kernel_size[1], m.padding[0], 1, st.act, st.slope)
-        elif st.kind == "convT":
-            ops.conv_bwd_data(g, t, plan.packed(st, "fwd", Cp), y, ep, live=(None, c_log))
-            yield
-        else:
-            ops.conv_fwd(g, t, plan.packed(st, "fwd", Cp), y, ep, out_ld=out_ld, live=(c_log, None))
-            yield
-        sv.t, sv.y, sv.geom, sv.in_shape, sv.out_shape = t, y, g, (B, H, W, Cp), out_shape
+            sv.y = (alloc(("y", si), sv.out_shape) if alloc is not None
+                    else torch.empty(sv.out_shape, dtype=torch.float32, device=cur.device))
+        folded, early, bn_fwd = _for_next_stage(nxt, sv, groups, lane) if nxt is not None else (None, None, None)
+        yield from _launch_fwd(plan, st, sv, folded, bn_fwd, out_ld, jmask, alloc)
         if save:
             saved.append(sv)
-        cur = y
-        c_log = out_shape[3]
+        cur, c_log = sv.y, K
     return cur, saved
 
 
 def wgrad_geoms(plan: ChainPlan, saved):
-    """geometries of the weight-gradient GEMMs chain_backward(plan, saved, ..., need_params=True) launches"""
-    return [sv.geom for st, sv in zip(plan.stages, saved) if not _is_tconv1(st, sv.in_shape[3])]
+    """Geometries for ``FoldQueue.expect`` (they set how far each weight gradient is split): one per stage that is not
+    on the direct ``tconv1`` weight-gradient path.  This is the parent's over-count, kept on purpose (the list as it was
+    before stages had routes): the "head", "first_direct" and "convT_scatter" paths launch no weight-gradient GEMM
+    either, but dropping them changes the split and with it the summation order -- the bits -- of every weight gradient."""
+    return [sv.geom for sv in saved if sv.route.wgrad[0] != "tconv1"]
+
+
+def _param_grads(st: Stage, sv, g_pre, ld: int, grads, grad_dst, fold):
+    """Weight and bias gradient of the stage's module (nothing in the chain reads them: no yield) into ``grads``."""
+    m, g = st.mod, sv.geom
+    B, H, W, Cp = sv.in_shape
+    _, P, Q, K = sv.out_shape
+    c_in = sv.c_log
+    path, db_path = sv.route.wgrad if fold is None else sv.route.wgrad_fold
+    fused_db = None
+    if db_path == "unflat":
+        Cc, hh, ww = st.unflat
+        db = ops.colsum(B, hh * ww * Cc, hh * ww * Cc, g_pre).reshape(hh * ww, Cc).t().reshape(-1)
+        grads[id(m.bias)] = grad_dst[id(m.bias)].copy_(db) if id(m.bias) in grad_dst else db
+    elif db_path == "fused":
+        fused_db = grad_dst.get(id(m.bias))
+        if fused_db is None:
+            fused_db = torch.empty(K, dtype=torch.float32, device=g_pre.device)
+        grads[id(m.bias)] = fused_db
+    elif db_path == "colsum":
+        grads[id(m.bias)] = ops.colsum(B * P * Q, K, K, g_pre, out=grad_dst.get(id(m.bias)))
+    dw = grads[id(m.weight)] = grad_dst[id(m.weight)] if id(m.weight) in grad_dst else torch.empty_like(m.weight)
+    R, S = m.kernel_size if st.kind != "linear" else (1, 1)
+    if path == "convT_scatter" and sv.t.is_contiguous() and g_pre.is_contiguous() and dw.stride(2) == S * dw.stride(3):
+        # one-channel tail (stride 2): pixel-contraction kernel instead of a GEMM with one gathered channel
+        if ops.tconv_scatter_wgrad(sv.t, g_pre, 1, dw, dw.stride(0), dw.stride(3), B, H, W, Cp, P, Q, R, S, m.stride[0],
+                                   m.padding[0]) is not None:
+            return
+    if path == "head":                    # (a head never joins: ld == 0)
+        ops.head_wgrad(sv.t.reshape(B, Cp)[:, :c_in], g_pre.reshape(B), dw.reshape(-1), db=fused_db)
+    elif path == "first_direct":
+        # dW[k][c][tap] = sum big=g_pre[..,k] * small=t[..,c], all input channels in one launch
+        ops.tconv1_wgrad(g_pre, sv.t, Cp, c_in, dw, c_in * R * S, 1, R * S, B, P, Q, K, R, S, m.padding[0])
+    elif path == "conv":
+        ops.conv_bwd_weight(g, sv.t, g_pre, dw, c_in, K, dw.stride(0), dw.stride(1), dw.stride(3), db=fused_db,
+                            dy_ld=ld, defer=fold)
+    elif path == "tconv1":
+        ops.tconv1_wgrad(sv.t, g_pre, 1, 1, dw, R * S, 1, 0, B, H, W, Cp, R, S, m.padding[0])
+    elif path in ("convT", "convT_scatter"):
+        # gathered operand = convT output-grad (channels K), dense = convT input (channels Cp)
+        ops.conv_bwd_weight(g, g_pre, sv.t, dw, K, c_in, dw.stride(0), dw.stride(1), dw.stride(3), defer=fold)
+    elif path == "linear":
+        ops.conv_bwd_weight(g, sv.t, g_pre, dw, m.in_features, m.out_features, m.in_features, 1, 0, defer=fold)
+    else:                                 # Linear + Unflatten(C, h, w): rows in n' = t*C + co order, re-packed right away
+        (O, I), (Cc, hh, ww) = m.weight.shape, st.unflat
+        tmp = torch.empty(O, I, device=dw.device)
+        ops.conv_bwd_weight(g, sv.t, g_pre, tmp, I, O, I, 1, 0)      # (not deferred)
+        ops.pack_weights(tmp, dw, Cc, hh * ww, I, I, I, Cc * I, 1)
+
+
+def _plane_grads(plan: ChainPlan, st: Stage, sv, g_pre, gx_planes):
+    """First stage of the hand-scheduled step: only the input channels ``gx_planes`` of the data gradient, with the
+    input's Dropout2d mask columns applied, as [B,H,W,len(gx_planes)] -- or None when the route has no plane form
+    for them (generator: yields after a GEMM request)."""
+    m, NP = st.mod, len(gx_planes)
+    B, H, W, Cp = sv.in_shape
+    _, P, Q, K = sv.out_shape
+    R, S = m.kernel_size
+    form = sv.route.planes
+    # The scatter form's contribution tensor (planes * taps floats per pixel, written and read once) makes it HBM bound:
+    # measured break-even with the implicit GEMM at about 6 planes of a 5x5 filter, a clear win below
+    if form is None or (form == "scatter" and not (1 <= NP <= 8 and NP * R * S <= 128)):
+        return None
+    planes = torch.empty(B, H, W, NP, dtype=torch.float32, device=g_pre.device)
+    if form == "direct":
+        wd = plan.packed(st, "dgrad", Cp)                  # [Cpad][T][K]: row c is the [T][K] filter of plane c
+        for j, c in enumerate(gx_planes):     # (the input's Dropout2d mask column scales the plane in the same launch)
+            ops.tconv1_fwd(g_pre, wd[c], None, planes[..., j], B, P, Q, K, R, S, m.padding[0], NP, ACT_NONE, 0.0,
+                           rowscale=None if sv.mask is None else sv.mask[:, c])
+        return planes
+    wd = plan.packed(st, ("scatter_dgrad", tuple(gx_planes)), Cp)
+    if ops.tconv_scatter_ok(K, NP, R, S, m.stride[0]) and g_pre.is_contiguous():
+        ops.tconv_scatter(g_pre, wd, None, planes, B, P, Q, K, H, W, NP, NP, R, S, m.stride[0], m.padding[0])
+    else:
+        contrib = torch.empty(B, P, Q, NP * R * S, dtype=torch.float32, device=g_pre.device)
+        ops.conv_fwd(ops.geom(B, P, Q, K, P, Q, NP * R * S, 1, 1, 1, 0), g_pre, wd, contrib, ops.epilogue())
+        yield
+        ops.col2im(contrib, NP * R * S, None, planes, B, P, Q, H, W, NP, NP, R, S, m.stride[0], m.padding[0])
+    if sv.mask is not None:
+        cols = torch.cat([sv.mask[:, c:c + 1] for c in gx_planes], dim=1)
+        planes = planes * cols.reshape(B, 1, 1, -1)
+    return planes
+
+
+def _data_grad(plan: ChainPlan, st: Stage, sv, g_pre, ld: int, pact, pslope, want: bool, need_params: bool, grads,
+               grad_dst):
+    """Gradient of the pre-activation that produced the stage's input (activation ``pact``): the data-gradient GEMM
+    folded with what sits between the two -- Dropout2d mask and act' in its epilogue, BatchNorm backward (whose
+    parameter gradients go into ``grads``) fused with the LeakyReLU derivative.  Generator: yields after a GEMM
+    request.  ``want`` False: only the BatchNorm parameter gradients are needed (returns None)."""
+    m, g, bn, rt = st.mod, sv.geom, sv.bn, sv.route
+    B, H, W, Cp = sv.in_shape
+    dact_y = sv.x_in if pact != ACT_NONE else None
+    gt = torch.empty(sv.in_shape, dtype=torch.float32, device=g_pre.device)
+    bn_red = None
+    if bn is None:
+        ep = ops.epilogue(mask=sv.mask, dact_y=dact_y, dact=pact, dslope=pslope)
+    else:
+        # BatchNorm backward needs sum(g~ * xhat) and sum(g~) of the gradient this GEMM produces: its epilogue
+        # accumulates them per M-tile while the values are in registers
+        mask_in = sv.mask if sv.pattern == ["drop", "bn"] else None
+        mask_pre = sv.mask if sv.pattern == ["bn", "drop"] else None
+        slots = ops.conv_mtiles(g, 0 if rt.dgrad == "convT" else 1)[0] if rt.bn_reduce else 0
+        if slots > 0:
+            bn_red = (torch.empty(2 * Cp * slots, dtype=torch.float32, device=g_pre.device), slots)
+            ep = ops.epilogue(bn_bwd=(bn_red[0], sv.x_in, sv.bn_stats[0], sv.bn_stats[1], mask_in, mask_pre, slots))
+        else:
+            ep = ops.epilogue()
+    if rt.dgrad == "tconv1" and bn is None and sv.mask is None:
+        ops.tconv1_dgrad(g_pre, 1, plan.packed(st, "fwd", Cp), dact_y, pact, pslope, gt, B, H, W, Cp, m.kernel_size[0],
+                         m.kernel_size[1], m.padding[0])
+    elif st.kind == "convT":
+        ops.conv_fwd(g, g_pre, plan.packed(st, "dgrad", Cp), gt, ep, live=(None, sv.c_log))
+        yield
+    else:
+        ops.conv_bwd_data(g, g_pre, plan.packed(st, "dgrad", Cp), gt, ep, in_ld=ld, live=(sv.c_log, None))
+        yield
+    if bn is None:
+        return gt
+    use_batch = sv.training or bn.running_mean is None
+    slope = pslope if pact == ACT_LEAKY else -1.0
+    out = dict(want_gx=want, out_dgamma=grad_dst.get(id(bn.weight)) if need_params else None,
+               out_dbeta=grad_dst.get(id(bn.bias)) if need_params else None)
+    if bn_red is not None:
+        dgam, dbet, gprev = ops.bn_bwd_from_partials(bn_red[0], bn_red[1], sv.x_in, gt, mask_in, mask_pre, sv.bn_stats,
+                                                     bn.weight.detach(), B, H * W, Cp, use_batch, slope, **out)
+    else:
+        dgam, dbet, gprev = ops.bn_bwd(sv.x_in, gt, mask_in, mask_pre, sv.bn_stats, bn.weight.detach(), B, H * W, Cp,
+                                       use_batch, slope, **out)
+    if need_params:
+        grads[id(bn.weight)], grads[id(bn.bias)] = dgam, dbet
+    if pact == ACT_TANH and gprev is not None:
+        gprev = ops.act_bwd(gprev, sv.x_in, ACT_TANH, 0.0)
+    return gprev
 
 
 def chain_backward_gen(plan: ChainPlan, saved, gy: torch.Tensor, c_log_in: int, need_gx: bool, need_params: bool = True,
                        grad_dst=None, gx_planes=None, gy_ld: int = 0, gy_pre: bool = False, in_act=None, fold=None):
     """Generator form of the backward pass (see ``run_parallel``): yields after every data-gradient GEMM request (the
     weight gradients are deferred to ``fold`` or launched at once: nothing in the chain reads them).
-    Returns (gx or None, {param tensor id -> grad}).  ``grad_dst`` optionally maps id(param) to a
-    preallocated destination (a view of a flat gradient buffer) that the kernels write directly.
+    Returns (gx or None, {param tensor id -> grad}).  ``c_log_in``: the forward pass's.  ``grad_dst`` optionally maps
+    id(param) to a preallocated destination (a view of a flat gradient buffer) that the kernels write directly.
     ``gx_planes`` (hand-scheduled step only): instead of the full input gradient return only these input
     channels of it, as a [B,H,W,len(gx_planes)] tensor -- the first layer's data gradient is consumed one plane
     at a time (image plane towards G, embedding plane towards the digit table).
@@ -612,6 +792,7 @@ def chain_backward_gen(plan: ChainPlan, saved, gy: torch.Tensor, c_log_in: int, 
     grad_dst = grad_dst or {}
     n = len(plan.stages)
     last = plan.stages[-1]
+    assert saved[0].c_log == c_log_in, "chain_backward: c_log_in differs from the forward pass's"
     if gy_ld:
         if not (gy_pre or last.act == ACT_NONE) or not join_ok(plan):
             raise ValueError("chain_backward(gy_ld=...): needs join_ok(plan) and a pre-activation gradient")
@@ -619,165 +800,20 @@ def chain_backward_gen(plan: ChainPlan, saved, gy: torch.Tensor, c_log_in: int, 
     else:
         gy = gy.contiguous()
         g_pre = gy if (gy_pre or last.act == ACT_NONE) else ops.act_bwd(gy, saved[-1].y, last.act, last.slope)
-    gx = None
     for i in range(n - 1, -1, -1):
         st, sv = plan.stages[i], saved[i]
         assert not isinstance(sv.bn_stats, list), "grouped forward state: backpropagate slice_saved(saved, g, groups)"
-        B, H, W, Cp = sv.in_shape
-        _, P, Q, K = sv.out_shape
-        rows_out = B * P * Q
-        m = st.mod
-        g = sv.geom
         ld = gy_ld if i == n - 1 else 0          # pixel pitch of g_pre (0 = dense)
-        prev = plan.stages[i - 1] if i > 0 else None
-        c_in_log = prev.mod.out_channels if (prev is not None and prev.kind != "linear") else (
-            (prev.unflat[0] if prev.unflat else prev.mod.out_features) if prev is not None else c_log_in)
-        # a first conv's weight gradient (<= 8 input planes): direct per-channel kernel on its own, but as one more job of
-        # the pass's combined weight-gradient launch when there is one (its 200 x 32 GEMM fills gaps there, and the bias
-        # gradient comes along: measured 7.15 -> 7.08 ms per MNIST iteration)
-        gemm_first = fold is not None and Cp % 4 == 0 and K % 4 == 0
         if need_params:
-            # ---- parameter gradients of this stage
-            fused_db = None
-            if m.bias is not None:
-                if st.kind == "linear" and st.unflat:
-                    Cc, hh, ww = st.unflat
-                    db = ops.colsum(B, hh * ww * Cc, hh * ww * Cc, g_pre).reshape(hh * ww, Cc).t().reshape(-1)
-                    if id(m.bias) in grad_dst:
-                        db = grad_dst[id(m.bias)].copy_(db)
-                    grads[id(m.bias)] = db
-                elif st.kind == "conv" and not (i == 0 and _first_conv_direct(st, c_in_log) and not gemm_first):
-                    # Conv2d: the bias gradient is the column sum of the dense wgrad operand -> fused into that launch
-                    fused_db = grad_dst.get(id(m.bias))
-                    if fused_db is None:
-                        fused_db = torch.empty(K, dtype=torch.float32, device=gy.device)
-                    grads[id(m.bias)] = fused_db
-                else:
-                    grads[id(m.bias)] = ops.colsum(rows_out, K, K, g_pre, out=grad_dst.get(id(m.bias)))
-            dw = grad_dst[id(m.weight)] if id(m.weight) in grad_dst else torch.empty_like(m.weight)
-            if _is_head(st, sv.in_shape) and not ld:
-                ops.head_wgrad(sv.t.reshape(B, Cp)[:, :c_in_log], g_pre.reshape(B), dw.reshape(-1), db=fused_db)
-            elif st.kind == "conv" and i == 0 and _first_conv_direct(st, c_in_log) and not gemm_first:
-                T = m.kernel_size[0] * m.kernel_size[1]
-                # dW[k][c][tap] = sum big=g_pre[..,k] * small=t[..,c], all input channels in one launch
-                ops.tconv1_wgrad(g_pre, sv.t, Cp, c_in_log, dw, c_in_log * T, 1, T, B, P, Q, K,
-                                 m.kernel_size[0], m.kernel_size[1], m.padding[0])
-            elif st.kind == "conv":
-                T = m.kernel_size[0] * m.kernel_size[1]
-                ops.conv_bwd_weight(g, sv.t, g_pre, dw, c_in_log, K, dw.stride(0), dw.stride(1), dw.stride(3), db=fused_db,
-                                    dy_ld=ld, defer=fold)
-            elif _is_tconv1(st, Cp):
-                T = m.kernel_size[0] * m.kernel_size[1]
-                ops.tconv1_wgrad(sv.t, g_pre, 1, 1, dw, T, 1, 0, B, H, W, Cp, m.kernel_size[0], m.kernel_size[1],
-                                 m.padding[0])
-            elif st.kind == "convT":
-                T = m.kernel_size[0] * m.kernel_size[1]
-                done = None
-                if (m.out_channels == 1 and Cp == 64 and c_in_log == 64 and not ld and sv.t.is_contiguous()
-                        and g_pre.is_contiguous() and dw.stride(2) == m.kernel_size[1] * dw.stride(3)):
-                    # one-channel tail (stride 2): pixel-contraction kernel instead of a GEMM with one gathered channel
-                    done = ops.tconv_scatter_wgrad(sv.t, g_pre, 1, dw, dw.stride(0), dw.stride(3), B, H, W, Cp, P, Q,
-                                                   m.kernel_size[0], m.kernel_size[1], m.stride[0], m.padding[0])
-                if done is None:
-                    # gathered operand = convT output-grad (channels K), dense = convT input (channels Cp)
-                    ops.conv_bwd_weight(g, g_pre, sv.t, dw, K, c_in_log, dw.stride(0), dw.stride(1), dw.stride(3),
-                                        defer=fold)
-            else:
-                O, I = m.weight.shape
-                Cc, hh, ww = st.unflat if st.unflat else (O, 1, 1)
-                T = hh * ww
-                if T == 1:
-                    ops.conv_bwd_weight(g, sv.t, g_pre, dw, I, O, I, 1, 0, defer=fold)
-                else:
-                    tmp = torch.empty(O, I, device=dw.device)   # rows in n' = t*C + co order
-                    ops.conv_bwd_weight(g, sv.t, g_pre, tmp, I, O, I, 1, 0)      # (re-packed right away: not deferred)
-                    ops.pack_weights(tmp, dw, Cc, T, I, I, I, Cc * I, 1)
-            grads[id(m.weight)] = dw
-        # ---- data gradient, folded with what sits between y_{i-1} and this conv
-        if i == 0 and gx_planes is not None and sv.bn is None and _first_conv_direct(st, c_in_log):
-            planes = torch.empty(B, H, W, len(gx_planes), dtype=torch.float32, device=gy.device)
-            wd = plan.packed(st, "dgrad", Cp)                  # [Cpad][T][K]: row c is the [T][K] filter of plane c
-            for j, c in enumerate(gx_planes):     # (the input's Dropout2d mask column scales the plane in the same launch)
-                ops.tconv1_fwd(g_pre, wd[c], None, planes[..., j], B, P, Q, K, m.kernel_size[0], m.kernel_size[1],
-                               m.padding[0], len(gx_planes), ACT_NONE, 0.0,
-                               rowscale=None if sv.mask is None else sv.mask[:, c])
-            gx = planes
-            break
-        if i == 0 and sv.bn is None and _scatter_dgrad(st, gx_planes):
-            R, S = m.kernel_size
-            NP = len(gx_planes)
-            if ops.tconv_scatter_ok(K, NP, R, S, m.stride[0]) and g_pre.is_contiguous():
-                planes = torch.empty(B, H, W, NP, dtype=torch.float32, device=gy.device)
-                ops.tconv_scatter(g_pre, plan.packed(st, ("scatter_dgrad", tuple(gx_planes)), Cp), None, planes, B, P, Q, K,
-                                  H, W, NP, NP, R, S, m.stride[0], m.padding[0])
-                if sv.mask is not None:
-                    cols = torch.cat([sv.mask[:, c:c + 1] for c in gx_planes], dim=1)
-                    planes = planes * cols.reshape(B, 1, 1, -1)
-                gx = planes
-                break
-            contrib = torch.empty(B, P, Q, NP * R * S, dtype=torch.float32, device=gy.device)
-            ops.conv_fwd(ops.geom(B, P, Q, K, P, Q, NP * R * S, 1, 1, 1, 0), g_pre,
-                         plan.packed(st, ("scatter_dgrad", tuple(gx_planes)), Cp), contrib, ops.epilogue())
-            yield
-            planes = torch.empty(B, H, W, NP, dtype=torch.float32, device=gy.device)
-            ops.col2im(contrib, NP * R * S, None, planes, B, P, Q, H, W, NP, NP, R, S, m.stride[0], m.padding[0])
-            if sv.mask is not None:
-                cols = torch.cat([sv.mask[:, c:c + 1] for c in gx_planes], dim=1)
-                planes = planes * cols.reshape(B, 1, 1, -1)
-            gx = planes
-            break
-        if i == 0 and not need_gx and sv.bn is None:
-            break
-        pact, pslope = (prev.act, prev.slope) if prev is not None else (in_act or (ACT_NONE, 0.0))
-        gt = torch.empty(sv.in_shape, dtype=torch.float32, device=gy.device)
-        bn_red = None
-        if sv.bn is None:
-            ep = ops.epilogue(mask=sv.mask, dact_y=sv.x_in if pact != ACT_NONE else None, dact=pact, dslope=pslope)
-        else:
-            # BatchNorm backward needs sum(g~ * xhat) and sum(g~) of the gradient this GEMM produces: its epilogue
-            # accumulates them per M-tile while the values are in registers
-            mask_in = sv.mask if sv.pattern == ["drop", "bn"] else None
-            mask_pre = sv.mask if sv.pattern == ["bn", "drop"] else None
-            slots = ops.conv_mtiles(g, 0 if st.kind == "convT" else 1)[0]
-            if slots > 0 and st.kind in ("conv", "convT") and not _is_tconv1(st, Cp):
-                part = torch.empty(2 * Cp * slots, dtype=torch.float32, device=gy.device)
-                bn_red = (part, slots)
-                ep = ops.epilogue(bn_bwd=(part, sv.x_in, sv.bn_stats[0], sv.bn_stats[1], mask_in, mask_pre, slots))
-            else:
-                ep = ops.epilogue()
-        if _is_tconv1(st, Cp) and sv.bn is None and sv.mask is None:
-            ops.tconv1_dgrad(g_pre, 1, plan.packed(st, "fwd", Cp), sv.x_in if pact != ACT_NONE else None, pact, pslope,
-                             gt, B, H, W, Cp, m.kernel_size[0], m.kernel_size[1], m.padding[0])
-        elif st.kind == "convT":
-            ops.conv_fwd(g, g_pre, plan.packed(st, "dgrad", Cp), gt, ep, live=(None, c_in_log))
-            yield
-        else:
-            ops.conv_bwd_data(g, g_pre, plan.packed(st, "dgrad", Cp), gt, ep, in_ld=ld, live=(c_in_log, None))
-            yield
-        if sv.bn is not None:
-            bn = sv.bn
-            use_batch = sv.training or bn.running_mean is None
-            slope = pslope if pact == ACT_LEAKY else -1.0
-            want = (i > 0) or need_gx
-            out_dg = grad_dst.get(id(bn.weight)) if need_params else None
-            out_db = grad_dst.get(id(bn.bias)) if need_params else None
-            if bn_red is not None:
-                dgam, dbet, gprev = ops.bn_bwd_from_partials(bn_red[0], bn_red[1], sv.x_in, gt, mask_in, mask_pre,
-                                                             sv.bn_stats, bn.weight.detach(), B, H * W, Cp, use_batch,
-                                                             slope, want_gx=want, out_dgamma=out_dg, out_dbeta=out_db)
-            else:
-                dgam, dbet, gprev = ops.bn_bwd(sv.x_in, gt, mask_in, mask_pre, sv.bn_stats, bn.weight.detach(), B, H * W,
-                                               Cp, use_batch, slope, want_gx=want, out_dgamma=out_dg, out_dbeta=out_db)
-            if need_params:
-                grads[id(bn.weight)] = dgam
-                grads[id(bn.bias)] = dbet
-            if pact == ACT_TANH and gprev is not None:
-                gprev = ops.act_bwd(gprev, sv.x_in, ACT_TANH, 0.0)
-            gt = gprev
-        if i == 0:
-            gx = gt
-        else:
-            g_pre = gt
+            _param_grads(st, sv, g_pre, ld, grads, grad_dst, fold)
+        if i > 0:
+            g_pre = yield from _data_grad(plan, st, sv, g_pre, ld, plan.stages[i - 1].act, plan.stages[i - 1].slope, True,
+                                          need_params, grads, grad_dst)
+    # ---- the first stage's data gradient: a few planes of it, none of it, or all of it
+    gx = (yield from _plane_grads(plan, st, sv, g_pre, gx_planes)) if gx_planes is not None else None
+    if gx is None and (need_gx or sv.bn is not None):
+        gx = yield from _data_grad(plan, st, sv, g_pre, ld, *(in_act or (ACT_NONE, 0.0)), need_gx, need_params, grads,
+                                   grad_dst)
     return gx, grads
 
 

@@ -276,23 +276,22 @@ class AliStepper:
         self.bn_buffers = [b for n_, b in D.named_buffers() if "running" in n_]
         self.iter_t = torch.zeros(1, dtype=torch.int64, device=self.opt_d.flat.device)
         self._emb_planes = tuple(range(1, 1 + len(self.family.d_tables)))
-        self._n_drop = sum(1 for pl in (self.pDx, self.pDz, self.pDxz) for st in pl.stages
-                           if any(k == "drop" for k, _ in st.pre))
+        self._n_drop = sum(st.has_drop for pl in (self.pDx, self.pDz, self.pDxz) for st in pl.stages)
         # D's joint rows [dx | dz] (mnist.py:152-154): when both branches end in a plain conv GEMM + the same
         # activation and dxz starts with a lone Dropout2d, the branch ends write straight into the joint buffer
         # (masked), and dxz's first data gradient returns the branches' pre-activation gradients -- no torch.cat, no
         # mask pass, no slice copies, no act' passes around the join
         lx, lz, f0 = self.pDx.stages[-1], self.pDz.stages[-1], self.pDxz.stages[0]
         self._join = (_chain.join_ok(self.pDx) and _chain.join_ok(self.pDz) and (lx.act, lx.slope) == (lz.act, lz.slope)
-                      and f0.kind == "conv" and [k for k, _ in f0.pre] == ["drop"]
+                      and f0.kind == "conv" and f0.pattern == ["drop"]
                       and f0.mod.in_channels == lx.mod.out_channels + lz.mod.out_channels
                       and tuple(f0.mod.kernel_size) == (1, 1))
         self._fold = ops.FoldQueue(self.opt_d.flat.device) if self.opt_d.flat.is_cuda else None
         if self._fold is not None:
             self._fold.arena()
         self._join_act = (lx.act, lx.slope)
-        self._join_skip = sum(1 for pl in (self.pDx, self.pDz) for st in pl.stages if any(k == "drop" for k, _ in st.pre))
-        self._n_drop_dx = sum(1 for st in self.pDx.stages if any(k == "drop" for k, _ in st.pre))
+        self._join_skip = sum(st.has_drop for pl in (self.pDx, self.pDz) for st in pl.stages)
+        self._n_drop_dx = sum(st.has_drop for st in self.pDx.stages)
 
     # ------------------------------------------------------------------ pieces
     def _planes(self, X, idx, cont, tables, out=None, mask=None):
@@ -308,7 +307,7 @@ class AliStepper:
         ahead of its turn like the join's (None: not known yet, or no such layer) -- assemble_planes then applies it
         and no mask pass is needed."""
         st = self.pDx.stages[0]
-        if [k for k, _ in st.pre] != ["drop"]:
+        if st.pattern != ["drop"]:
             return None
         n_log = 1 + len(self.family.d_tables) + (0 if cont is None else cont.shape[1])
         return _dropout.peek_mask(0, B, n_log, st.pre[0][1], device, (n_log + 3) // 4 * 4)
@@ -416,7 +415,7 @@ class AliStepper:
                 lanes = (_dropout.Lane(base), _dropout.Lane(base + self._n_drop_dx))
         if pair:
             join = self._join_begin(B, x0.device)
-            n_dx = _chain._out_shape(self.pDx.stages[-1], B, 1, 1, 1)[3]
+            n_dx = self.pDx.out_channels
             (dx_pre, _), (dz, s_dz) = run_parallel(
                 self._dx_forward_gen(x0, n_log, save, groups, x_masked, join=join if join is not None else False,
                                      lane=lanes[0]),
