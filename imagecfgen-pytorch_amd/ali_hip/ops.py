@@ -844,6 +844,47 @@ def dropout_mask_multi(seed, dev_counter, seg_end, seg_p, seg_clog, seg_cpad, ou
     return out
 
 
+def normal_fill(seed, out, dev_counter=None, offset=0):
+    """out (contiguous fp32 CUDA, any shape, 4-byte aligned: slices are fine) <- N(0,1) draws ``offset .. offset +
+    numel`` of the latent stream keyed by (seed, *dev_counter) (include/ali_hip.h: ali_normal_fill;
+    ``ali_hip.source.normal_reference`` gives the same values on the host)."""
+    ctr = None
+    if dev_counter is not None:
+        assert dev_counter.is_cuda and dev_counter.dtype == torch.int64
+        ctr = c_void_p(dev_counter.data_ptr())
+    _lib.check(_lib.load().ali_normal_fill(int(seed) & (2 ** 64 - 1), ctr, int(offset), _chk(out, "out"), out.numel(),
+                                           _stream()), "ali_normal_fill")
+    return out
+
+
+def batch_gather(images, attrs, n_cls, index, lo, hi, out=None):
+    """One batch of a device-resident data set: rows ``index`` ([B] int64 CUDA) of ``images`` [N, H*W] (uint8 or fp32)
+    and ``attrs`` [N, n_cls + n_cont] fp32, scaled like ``image_scms.mnist._scale_batch`` -- (images [B, H*W], one-hot
+    rows [B, n_cls], idx [B, 1] int32, cont [B, n_cont] or None), one launch (include/ali_hip.h: ali_batch_gather).
+    ``out``: the same four tensors to write into."""
+    for t, dt, name in ((images, (torch.uint8, torch.float32), "images"), (attrs, (torch.float32,), "attrs"),
+                        (index, (torch.int64,), "index")):
+        if not (t.is_cuda and t.is_contiguous() and t.dtype in dt):
+            raise ValueError(f"batch_gather: {name} must be a contiguous CUDA tensor of dtype {dt}, got {t.dtype} "
+                             f"{t.device}")
+    N, HW = images.shape
+    B, n_cont = index.numel(), attrs.shape[1] - n_cls
+    if attrs.shape[0] != N or n_cls < 1 or n_cont < 0 or (n_cont and (lo.numel() != n_cont or hi.numel() != n_cont)):
+        raise ValueError("batch_gather: attrs / lo / hi do not fit the images and n_cls")
+    dev = images.device
+    if out is None:
+        out = (torch.empty(B, HW, dtype=torch.float32, device=dev), torch.empty(B, n_cls, dtype=torch.float32, device=dev),
+               torch.empty(B, 1, dtype=torch.int32, device=dev),
+               torch.empty(B, n_cont, dtype=torch.float32, device=dev) if n_cont else None)
+    x, onehot, idx, cont = out
+    _lib.check(_lib.load().ali_batch_gather(
+        c_void_p(images.data_ptr()), int(images.dtype == torch.uint8), _chk(attrs, "attrs"), attrs.shape[1],
+        c_void_p(index.data_ptr()), _chk(lo, "lo") if n_cont else None, _chk(hi, "hi") if n_cont else None, N, HW, n_cls,
+        n_cont, B, _chk(x, "out images"), _chk(onehot, "out one-hot"), c_void_p(idx.data_ptr()), _opt(cont, "out cont"),
+        _stream()), "ali_batch_gather")
+    return x, onehot, idx, cont
+
+
 def bn_stats(x, mask, B, rows_per_img, C, gamma, beta, running_mean, running_var, momentum, eps, training, groups=1):
     """Returns st [4, C] (mean, invstd, sc, sh), or [groups, 4, C] for ``groups`` batched passes."""
     lib = _lib.load()

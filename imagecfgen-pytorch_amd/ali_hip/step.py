@@ -26,6 +26,7 @@ import torch
 from . import dp
 from . import dropout as _dropout
 from . import ops
+from . import source as _source
 from . import chain as _chain
 from .chain import (chain_backward, chain_backward_gen, chain_forward, chain_forward_gen, drive, get_plan,
                     run_parallel, slice_saved)
@@ -236,13 +237,19 @@ def _allreduce_now(flat, pg):
 
 class AliStepper:
     def __init__(self, E, G, D, lr=1e-4, betas=(0.5, 0.999), eps=1e-8, family=None, process_group=None,
-                 capture=False, precision="f32", loss_scale=None, pipeline_reduce=False):
+                 capture=False, precision="f32", loss_scale=None, pipeline_reduce=False, z_seed=None):
         """``precision="f16"``: the convolutions' forward and data-gradient GEMMs contract fp16 operands on
         v_mfma_f32_32x32x16_f16 with fp32 accumulation (BASELINE config 5); activations, master weights, weight
         gradients' accumulation and Adam stay fp32.  The three losses' gradients are multiplied by ``loss_scale``
         (default 1024 for f16, 1 otherwise; a power of two) so that small gradients survive the fp16 rounding of the
-        GEMM operands, and Adam divides it out again."""
+        GEMM operands, and Adam divides it out again.
+
+        ``z_seed`` (default ``source.DEFAULT_Z_SEED``): seed of the device latent stream, used by ``step(images, c)``
+        without ``z`` and by ``step_indexed``: iteration t draws ``normal_fill(latent_seed, counter=t)`` -- on the host,
+        ``source.normal_reference(latent_seed, t, B * z_dim)``.  Data-parallel ranks mix their rank into it."""
         self.E, self.G, self.D = E, G, D
+        self.z_seed = _source.DEFAULT_Z_SEED if z_seed is None else int(z_seed)
+        self._z_used = False          # checkpoints carry z_seed only once the device stream has been drawn from
         # Data parallel only: overlap the LAST all-reduce of an iteration (D step b) with the NEXT iteration's E(x) / G(z)
         # forward passes, which need neither that reduction nor the D update behind it (SURVEY.md 8e).  ``step(...,
         # ahead=(images, c, z))`` names the next batch; its forward is computed into persistent buffers while the
@@ -267,6 +274,9 @@ class AliStepper:
             pl.cache.static = True
         self.pg = process_group
         self.world = torch.distributed.get_world_size(process_group) if process_group is not None else 1
+        self.rank = torch.distributed.get_rank(process_group) if process_group is not None else 0
+        m0 = self.pDz.stages[0].mod                # D.dz's first layer reads z
+        self.z_dim = m0.in_channels if hasattr(m0, "in_channels") else m0.in_features
         self.dist = process_group is not None      # a 1-rank group still issues every collective (tests the RCCL path)
         self.capture = capture
         self.segmented = False     # tests: force the data-parallel (segmented) replay on a single rank
@@ -496,15 +506,30 @@ class AliStepper:
         return ((g if self._join else g.contiguous()).unflatten(1, (1, 1, cols)),)
 
     # ------------------------------------------------------------------ the iteration, phase by phase
-    def _begin(self, images, c, z, do_eg=True, ahead=None):
+    @property
+    def latent_seed(self):
+        """the seed this rank's device latent stream is keyed with (rank 0 / one GPU: ``z_seed`` itself)"""
+        return _source.rank_seed(self.z_seed, self.rank)
+
+    def _draw_z(self, B):
+        return ops.normal_fill(self.latent_seed, torch.empty(B, self.z_dim, dtype=torch.float32, device=self.iter_t.device),
+                               dev_counter=self.iter_t)
+
+    def _begin(self, images, c, z, do_eg=True, ahead=None, source=None, index=None):
+        cond = None
+        if source is not None:         # device pipeline: the batch is assembled from the resident data set ...
+            images, onehot, idx, cont = source.gather(index)
+            cond = (idx, cont, [onehot])
         B = images.shape[0]
+        if z is None:                  # ... and the latents are drawn here, keyed by the iteration counter
+            z = self._draw_z(B)
         # (iter_t = iterations completed so far: it keys this iteration's Dropout2d masks and advances at the end of the
         # iteration, in the launch that also applies the BatchNorm batch counts)
         if self._fold is not None:
             self._fold.abandon()       # (nothing is pending after a completed iteration)
         _dropout.begin_iteration(self.iter_t, owner=self, tag=(B, bool(do_eg)))
         _chain.defer_batch_counts()
-        idx, cont, onehots = self.family.conditioning(c)
+        idx, cont, onehots = cond if cond is not None else self.family.conditioning(c)
         cx = {"images": images, "B": B, "idx": idx, "cont": cont, "onehots": onehots,
               "zin": z.reshape(B, -1).float().contiguous(), "out": {}}
         if self._pipelined(do_eg):     # the E(x) / G(z) forward computed ahead (_ensure_ahead), the next batch
@@ -710,10 +735,10 @@ class AliStepper:
         if self.dist:
             dp.average_buffers_(self.bn_buffers, self.pg)
 
-    def _iteration(self, images, c, z, do_eg=True, ahead=None):
+    def _iteration(self, images, c, z, do_eg=True, ahead=None, source=None, index=None):
         if self._pipelined(do_eg):
             self._ensure_ahead(images, c, z)    # (in front of _begin: it runs its own attribute plumbing)
-        cx = self._begin(images, c, z, do_eg, ahead)
+        cx = self._begin(images, c, z, do_eg, ahead, source, index)
         self._run_segments(cx, self._segments(do_eg, ahead is not None), dp.allreduce_sum_async_)
         return cx["out"]
 
@@ -777,6 +802,8 @@ class AliStepper:
               for n, m in (("E", self.E), ("G", self.G), ("D", self.D))}
         sd.update(optimizer_E=opt(self.opt_eg), optimizer_D=opt(self.opt_d), iteration=int(self.iter_t.item()),
                   dropout_seed=_dropout._state["seed"])
+        if self._z_used:
+            sd["z_seed"] = self.z_seed
         return sd
 
     def load_state_dict(self, sd):
@@ -804,6 +831,11 @@ class AliStepper:
                 _dropout._state["seed"] = int(sd["dropout_seed"])
                 self._graph.clear()
                 self.__dict__.pop("_mask_plans", None)
+            if "z_seed" in sd:         # (absent from checkpoints of runs that drew their latents on the host)
+                if int(sd["z_seed"]) != self.z_seed:
+                    self.z_seed = int(sd["z_seed"])     # a launch argument of the draw, like the dropout seed
+                    self._graph.clear()
+                self._z_used = True
             for pl in (self.pE, self.pG, self.pDx, self.pDz, self.pDxz):
                 pl.cache.refresh()
 
@@ -815,29 +847,57 @@ class AliStepper:
 
     # ------------------------------------------------------------------ public
     @torch.no_grad()
-    def step(self, images, c: Dict[str, torch.Tensor], z, do_eg=True, masks=None, ahead=None):
+    def step(self, images, c: Dict[str, torch.Tensor], z=None, do_eg=True, masks=None, ahead=None):
         """One iteration.  ``masks``: optional list of host-recorded Dropout2d masks (parity mode).
         ``ahead`` = (images, c, z) of the NEXT call (``pipeline_reduce``, data parallel only; ignored otherwise): pass
-        the very tensors the next call will be given."""
+        the very tensors the next call will be given.
+        ``z=None``: the latents are drawn on the device inside the iteration (``z_seed``; no host draw, no upload)."""
+        if z is None:
+            self._device_pipeline_ok(ahead)
+            self._z_used = True
         try:
             return self._step(images, c, z, do_eg, masks, ahead)
         finally:
             _chain.abort_batch_counts()     # no-op after a completed iteration
 
-    def _step(self, images, c, z, do_eg, masks, ahead=None):
-        with ops.precision(self.precision):
-            return self._step_impl(images, c, z, do_eg, masks, ahead)
+    @torch.no_grad()
+    def step_indexed(self, source, index, do_eg=True):
+        """One iteration on rows ``index`` ([B] int64 device tensor, e.g. ``source.batch(i)``) of a
+        ``source.DeviceDataset``: the batch assembly (one ``ali_batch_gather`` launch) and the latent draw are the
+        iteration's first launches -- under ``capture=True`` inside the graph, whose only loaded input is ``index``.
+        Equal, bit for bit, to ``step(images, c, z)`` on ``_scale_batch`` of the same rows with
+        ``z = normal_fill(latent_seed, counter=iteration)``."""
+        self._device_pipeline_ok(None)
+        if getattr(self.family, "name", None) != "mnist":
+            raise ValueError("step_indexed: the device batch assembly exists for the MorphoMNIST family only")
+        if not (torch.is_tensor(index) and index.is_cuda and index.dtype == torch.int64 and index.dim() == 1
+                and index.numel() > 0):
+            raise ValueError("step_indexed: index must be a non-empty 1-d int64 CUDA tensor")
+        self._z_used = True
+        try:
+            return self._step(None, None, None, do_eg, None, None, source, index.contiguous())
+        finally:
+            _chain.abort_batch_counts()
 
-    def _step_impl(self, images, c, z, do_eg, masks, ahead=None):
+    def _device_pipeline_ok(self, ahead):
+        if self.pipeline_reduce or ahead is not None:
+            raise ValueError("the device input pipeline (z=None / step_indexed) cannot be combined with "
+                             "pipeline_reduce / ahead=: the batch computed ahead is named by its host-made tensors")
+
+    def _step(self, images, c, z, do_eg, masks, ahead=None, source=None, index=None):
+        with ops.precision(self.precision):
+            return self._step_impl(images, c, z, do_eg, masks, ahead, source, index)
+
+    def _step_impl(self, images, c, z, do_eg, masks, ahead=None, source=None, index=None):
         if not self._pipelined(do_eg):
             ahead = None
         if masks is not None:
             with _dropout.injected_masks(masks):
-                return self._iteration(images, c, z, do_eg, ahead)
+                return self._iteration(images, c, z, do_eg, ahead, source, index)
         if not self.capture:
-            return self._iteration(images, c, z, do_eg, ahead)
+            return self._iteration(images, c, z, do_eg, ahead, source, index)
         try:
-            return self._replay(images, c, z, do_eg, ahead)
+            return self._replay(images, c, z, do_eg, ahead, source, index)
         except RuntimeError as e:  # graph capture refused (driver / RCCL combination): keep training, eagerly
             if self._graph or not any(w in str(e).lower() for w in ("captur", "graph")):
                 raise              # a failure of a graph that already ran, or an error that is not about capture
@@ -846,29 +906,40 @@ class AliStepper:
             self.capture = False
             if self._capture_snapshot is not None:
                 self._restore(self._capture_snapshot)
-            return self._iteration(images, c, z, do_eg)
+            return self._iteration(images, c, z, do_eg, None, source, index)
 
-    def _replay(self, images, c, z, do_eg, ahead=None):
+    def _replay(self, images, c, z, do_eg, ahead=None, source=None, index=None):
         """The iteration from HIP graphs.  One GPU: one graph over _begin and every segment (the launch sequence of
         _iteration).  Data parallel (or ``segmented``): one graph per segment, the gradient all-reduces in between
-        launched eagerly."""
+        launched eagerly.  The tensors a replay loads into the graphs' buffers: (images, c, z, next batch); without
+        the host-made ``z`` when it is drawn inside; the index slice alone for ``step_indexed``."""
         split, pipe = self.dist or self.segmented, self._pipelined(do_eg)
-        key = ("seg" if split else "one", tuple(images.shape), do_eg, pipe, ahead is not None)
+        key = ("seg" if split else "one", tuple(images.shape) if source is None else (source.key, index.numel()), do_eg,
+               pipe, ahead is not None) + (() if z is not None else ("z" if source is None else "indexed",))
+        loaded = (index,) if source is not None else (images, c) + (() if z is None else (z,)) + tuple(ahead or ())
+
+        def unpack(ins):                        # -> the arguments of _iteration / _begin behind do_eg
+            if source is not None:
+                return None, None, None, None, source, ins[0]
+            im, cc, *rest = ins
+            return im, cc, (None if z is None else rest.pop(0)), tuple(rest) or None, None, None
         if key not in self._graph:
             snap = self._capture_snapshot = self._snapshot()
 
-            def warm(im, cc, zz, *nxt):         # (collectives included: all ranks do this)
-                self._iteration(im, cc, zz, do_eg, nxt or None)
+            def warm(*ins):                     # (collectives included: all ranks do this)
+                im, cc, zz, nxt, src, ix = unpack(ins)
+                self._iteration(im, cc, zz, do_eg, nxt, src, ix)
                 if pipe and self._ahead is None:
                     self._prefetch(im, cc, zz)  # the persistent buffers the capture will name
-            ent = _Graphed((images, c, z, *(ahead or ())), warm, lambda: self._restore(snap))
-            im, cc, zz, *nxt = ent.inputs
+            ent = _Graphed(loaded, warm, lambda: self._restore(snap))
+            ent.source = source                 # (the graphs name its buffers)
+            im, cc, zz, nxt, src, ix = unpack(ent.inputs)
             segs = self._segments(do_eg, bool(nxt))
             if not split:                       # one graph: the launch sequence of _iteration
                 segs = [(lambda cx, ws=[w for w, _, _ in segs]: [w(cx) for w in ws], None, False)]
 
             def first(cx, w0=segs[0][0]):       # the first graph also starts the iteration
-                cx.update(self._begin(im, cc, zz, do_eg, tuple(nxt) or None))
+                cx.update(self._begin(im, cc, zz, do_eg, nxt, src, ix))
                 w0(cx)
             segs[0], cx = (first,) + segs[0][1:], {}
             self._run_segments(cx, [(lambda cx, w=w: ent.capture(w, cx), g, wt) for w, g, wt in segs], _allreduce_now)
@@ -878,7 +949,7 @@ class AliStepper:
             ent.out = cx["out"]
             self._graph[key] = ent, [(lambda cx, g=g: g.replay(), gr, wt) for g, (_, gr, wt) in zip(ent.graphs, segs)]
         ent, steps = self._graph[key]
-        ent.load((images, c, z, *(ahead or ())))
+        ent.load(loaded)
         if pipe:
             self._ensure_ahead(images, c, z, graphed=True)
         self._ahead = None

@@ -1025,6 +1025,125 @@ __global__ void __launch_bounds__(256) copy_multi_kernel(const CopyJobs jobs) {
   }
 }
 
+// ---- device-side input pipeline: the latent draw and the batch assembly of a training iteration ---------------------
+// z ~ N(0,1) from the counter RNG of the Dropout2d masks.  Element g = offset + i is one half of the Box-Muller pair
+// of hash g >> 1 (even g: cosine, odd g: sine), so a value depends on (seed, counter, g) only -- not on the launch
+// geometry, the split of a buffer over launches or the alignment of ``out``.  u1 in (0,1] and u2 in [0,1) are the
+// hash's bits 40..63 and 16..39.  kLatentStream separates the latents' keys from the masks' (one more mix64 round
+// over the masks' key).  ali_hip/source.py: normal_reference is the same recipe in fp64.
+constexpr uint64_t kLatentStream = 0x4C4154454E545A31ull;
+__device__ __forceinline__ void normal_pair(uint64_t key, uint64_t pair, float& c, float& s) {
+  const uint64_t r = mix64(key ^ pair);
+  const float u1 = (float)((uint32_t)(r >> 40) + 1u) * (1.f / 16777216.f);
+  const float u2 = (float)((uint32_t)(r >> 16) & 0xFFFFFFu) * (1.f / 16777216.f);
+  const float rad = sqrtf(-2.f * logf(u1));
+  float sn, cs;
+  sincospif(2.f * u2, &sn, &cs);        // (the angle 2*pi*u2 without rounding 2*pi*u2 itself)
+  c = rad * cs;
+  s = rad * sn;
+}
+__device__ __forceinline__ float normal_at(uint64_t key, uint64_t g) {
+  float c, s;
+  normal_pair(key, g >> 1, c, s);
+  return (g & 1) ? s : c;
+}
+// ``head`` elements in front of the first 16-byte boundary of ``out`` and the < 4 behind the last whole vector are
+// stored one by one by block 0; everything between as float4.
+__global__ void __launch_bounds__(kEwBlock)
+normal_fill_kernel(uint64_t seed, const long long* __restrict__ dev_counter, uint64_t offset, float* __restrict__ out,
+                   long long n, int head) {
+  const uint64_t key = mix64(mix64(mix64(seed) ^ (dev_counter ? (uint64_t)dev_counter[0] * 0xD1B54A32D192ED03ull : 0ull))
+                             ^ kLatentStream);
+  const long long nvec = (n - head) >> 2, tail0 = head + 4 * nvec;
+  const long long step = (long long)gridDim.x * blockDim.x;
+  for (long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += step) {
+    const long long i0 = head + 4 * v;
+    const uint64_t g = offset + (uint64_t)i0;
+    f32x4 r;
+    if ((g & 1) == 0) {                  // two whole pairs
+      float c0, s0, c1, s1;
+      normal_pair(key, g >> 1, c0, s0);
+      normal_pair(key, (g >> 1) + 1, c1, s1);
+      r = f32x4{c0, s0, c1, s1};
+    } else {                             // the sine of one pair, a whole pair, the cosine of a third
+      float c0, s0, c1, s1, c2, s2;
+      normal_pair(key, g >> 1, c0, s0);
+      normal_pair(key, (g >> 1) + 1, c1, s1);
+      normal_pair(key, (g >> 1) + 2, c2, s2);
+      r = f32x4{s0, c1, s1, c2};
+    }
+    *reinterpret_cast<f32x4*>(out + i0) = r;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < 8) {
+    const int t = threadIdx.x;
+    const long long i = t < 4 ? (long long)t : tail0 + (t - 4);
+    if (t < 4 ? t < head : i < n) out[i] = normal_at(key, offset + (uint64_t)i);
+  }
+}
+
+// One batch from a data set resident in HBM, one block per sample b, row r = index[b]:
+//   out_images[b, :]  = 2*x/255 - 1 of image row r (uint8 or fp32), the statement of image_scms/mnist.py:_scale_batch
+//                       as torch evaluates it on the device: a division by a Python scalar is a multiplication by
+//                       its fp32 reciprocal there, so that is what "bit-identical" asks for here;
+//   out_onehot[b, :]  = attrs[r, :n_cls];  out_idx[b] = first maximum of it (torch.argmax);
+//   out_cont[b, j]    = 2*(a - lo[j])/(hi[j] - lo[j]) - 1 of a = attrs[r, n_cls + j]: evaluated on the host by
+//                       _scale_batch, i.e. with IEEE division.
+// No contraction anywhere: every operation rounds on its own like the ATen kernels'.  A row index outside [0, N)
+// reads nothing and gives NaN images / attributes (the caller validates permutations on the host).
+__global__ void __launch_bounds__(256)
+batch_gather_kernel(const void* __restrict__ images, int images_u8, int vec, const float* __restrict__ attrs, int attr_ld,
+                    const long long* __restrict__ index, const float* __restrict__ lo, const float* __restrict__ hi,
+                    long long N, int HW, int n_cls, int n_cont, float* __restrict__ out_images,
+                    float* __restrict__ out_onehot, int* __restrict__ out_idx, float* __restrict__ out_cont) {
+#pragma clang fp contract(off)
+  const int b = blockIdx.x, t = threadIdx.x;
+  const long long r = index[b];
+  const bool ok = r >= 0 && r < N;
+  const float inv255 = 1.f / 255.f, nan = __builtin_nanf("");
+  float* o = out_images + (long long)b * HW;
+  const unsigned char* s8 = reinterpret_cast<const unsigned char*>(images) + (ok ? r : 0) * HW;
+  const float* s32 = reinterpret_cast<const float*>(images) + (ok ? r : 0) * HW;
+  if (vec) {
+    for (int q = t; q < (HW >> 2); q += 256) {
+      f32x4 x;
+      if (!ok) {
+        x = f32x4{nan, nan, nan, nan};
+      } else if (images_u8) {
+        const unsigned w = reinterpret_cast<const unsigned*>(s8)[q];
+        x = f32x4{(float)(w & 255u), (float)((w >> 8) & 255u), (float)((w >> 16) & 255u), (float)(w >> 24)};
+      } else {
+        x = reinterpret_cast<const f32x4*>(s32)[q];
+      }
+      if (ok) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) x[k] = (2.f * x[k]) * inv255 - 1.f;
+      }
+      reinterpret_cast<f32x4*>(o)[q] = x;
+    }
+  } else {
+    for (int q = t; q < HW; q += 256) {
+      const float x = images_u8 ? (float)s8[q] : s32[q];
+      o[q] = ok ? (2.f * x) * inv255 - 1.f : nan;
+    }
+  }
+  const float* a = attrs + (ok ? r : 0) * attr_ld;
+  if (t < n_cls) out_onehot[(long long)b * n_cls + t] = ok ? a[t] : 0.f;
+  if (t == 0 && n_cls > 0) {
+    int best = 0;
+    if (ok) {
+      float bv = a[0];
+      for (int n = 1; n < n_cls; ++n) {
+        const float v = a[n];
+        if (v > bv) { bv = v; best = n; }
+      }
+    }
+    out_idx[b] = best;
+  }
+  const int j = t - 64;                  // (a wave of its own: not behind thread 0's arg-max loop)
+  if (j >= 0 && j < n_cont)
+    out_cont[(long long)b * n_cont + j] = ok ? (2.f * (a[n_cls + j] - lo[j])) / (hi[j] - lo[j]) - 1.f : nan;
+}
+
 }  // namespace ali
 
 using namespace ali;
@@ -1187,6 +1306,35 @@ extern "C" int ali_dropout_mask(uint64_t seed, uint64_t offset, const int64_t* d
   hipLaunchKernelGGL(dropout_mask_kernel, dim3(ew_grid(n)), dim3(kEwBlock), 0, ST(stream), seed, offset,
                      reinterpret_cast<const long long*>(dev_counter), p, out, (long long)n);
   return check_launch("dropout_mask_kernel");
+}
+
+extern "C" int ali_normal_fill(uint64_t seed, const int64_t* dev_counter, uint64_t offset, float* out, int64_t n,
+                               ali_stream_t stream) {
+  if (!out || n <= 0 || (reinterpret_cast<uintptr_t>(out) & 3)) { set_error("ali_normal_fill: bad argument"); return ALI_ERR_BAD_ARG; }
+  long long head = (long long)((16 - (reinterpret_cast<uintptr_t>(out) & 15)) & 15) >> 2;
+  if (head > n) head = n;
+  hipLaunchKernelGGL(normal_fill_kernel, dim3(ew_grid(n, 4)), dim3(kEwBlock), 0, ST(stream), seed,
+                     reinterpret_cast<const long long*>(dev_counter), offset, out, (long long)n, (int)head);
+  return check_launch("normal_fill_kernel");
+}
+
+extern "C" int ali_batch_gather(const void* images, int32_t images_u8, const float* attrs, int32_t attr_ld,
+                                const int64_t* index, const float* lo, const float* hi, int64_t N, int32_t HW,
+                                int32_t n_cls, int32_t n_cont, int32_t B, float* out_images, float* out_onehot,
+                                int32_t* out_idx, float* out_cont, ali_stream_t stream) {
+  if (!images || !index || !out_images || N <= 0 || HW <= 0 || B <= 0 || n_cls < 0 || n_cls > 256 || n_cont < 0 ||
+      n_cont > 192 || attr_ld < n_cls + n_cont || (n_cls + n_cont > 0 && !attrs) || (n_cls > 0 && (!out_onehot || !out_idx)) ||
+      (n_cont > 0 && (!lo || !hi || !out_cont))) {
+    set_error("ali_batch_gather: bad argument");
+    return ALI_ERR_BAD_ARG;
+  }
+  // 4 pixels per lane (one 4-byte / 16-byte load, one 16-byte store) when every row starts on such a boundary
+  const uintptr_t src = reinterpret_cast<uintptr_t>(images), dst = reinterpret_cast<uintptr_t>(out_images);
+  const int vec = (HW & 3) == 0 && (dst & 15) == 0 && (src & (images_u8 ? 3 : 15)) == 0;
+  hipLaunchKernelGGL(batch_gather_kernel, dim3(B), dim3(256), 0, ST(stream), images, (int)images_u8, vec, attrs,
+                     (int)attr_ld, reinterpret_cast<const long long*>(index), lo, hi, (long long)N, (int)HW, (int)n_cls,
+                     (int)n_cont, out_images, out_onehot, reinterpret_cast<int*>(out_idx), out_cont);
+  return check_launch("batch_gather_kernel");
 }
 
 extern "C" int ali_dropout_mask_multi(uint64_t seed, const int64_t* dev_counter, const int64_t* seg_end,

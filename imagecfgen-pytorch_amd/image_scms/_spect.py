@@ -266,7 +266,7 @@ def spectrogram_statistics(stream_fn, device, clamp_variance=True):
 
 
 def run_training(E, G, D, data, stream_kwargs, attr_keys, n_epochs, l_rate, device, attr_cast=None,
-                 checkpoint_every=None, checkpoint_path=None, capture=True):
+                 checkpoint_every=None, checkpoint_path=None, capture=True, z_source="host", z_seed=None):
     """What ``audio_mnist.train`` / ``whalecalls.train`` / ``esrf_acoustic.train`` do once the dataset object exists
     (audio_mnist.py:343-420, whalecalls.py:426-499, esrf_acoustic.py:298-379): statistics pass, ``spect_to_img``,
     ALI iterations."""
@@ -284,7 +284,7 @@ def run_training(E, G, D, data, stream_kwargs, attr_keys, n_epochs, l_rate, devi
         E, G, D, oD, oE, _ = train_on_stream(E, G, D, stream, n_epochs=n_epochs, l_rate=l_rate, device=device,
                                              preprocess=prep, attr_keys=attr_keys, attr_cast=attr_cast,
                                              checkpoint_every=checkpoint_every, checkpoint_path=checkpoint_path,
-                                             capture=capture)
+                                             capture=capture, z_source=z_source, z_seed=z_seed)
     finally:
         if fused:
             data.fuse_spect_to_img(None)                # the caller's source streams log-spectrograms again
@@ -310,7 +310,7 @@ def save_checkpoint(path, E, G, D, stepper=None, opt_e=None, opt_d=None):
 
 def train_on_stream(E, G, D, stream_fn, n_batches_hint=None, n_epochs=1, l_rate=1e-4, device='cpu',
                     preprocess=None, attr_keys=(), use_stepper=None, family=None, capture=True, attr_cast=None,
-                    checkpoint_every=None, checkpoint_path=None):
+                    checkpoint_every=None, checkpoint_path=None, z_source="host", z_seed=None):
     """The training loop of audio_mnist.train / whalecalls.train / esrf_acoustic.train (audio_mnist.py:372-420 etc.)
     over any generator of batch dicts ``{"audio": [B,H,W], <attr>: one-hot ...}``.
 
@@ -319,16 +319,23 @@ def train_on_stream(E, G, D, stream_fn, n_batches_hint=None, n_epochs=1, l_rate=
     batch shape), otherwise the autograd ``ali_step``.  ``attr_cast``: dtype the attributes are cast to (the reference
     uses ``.float()``, whalecalls.py:455 ``.int()``).  ``checkpoint_every`` (epochs) + ``checkpoint_path``: periodic
     resumable state-dict checkpoints (``save_checkpoint``).
+    ``z_source="device"`` (CUDA + stepper only): no host draw and no 1 MB upload per iteration -- the stepper draws z
+    inside the (captured) iteration from the counter stream keyed by ``z_seed`` and the iteration number
+    (``ali_hip.source.normal_reference``); torch's host generator is left alone.
     Returns (E, G, D, optimizer_D, optimizer_E, epoch_scores)."""
     from .training_utils import ali_step
     dev = torch.device(device)
     if use_stepper is None:
         use_stepper = dev.type == "cuda"
+    if z_source not in ("host", "device"):
+        raise ValueError(f"z_source must be 'host' or 'device', got {z_source!r}")
+    if z_source == "device" and not (use_stepper and dev.type == "cuda"):
+        raise ValueError("z_source='device' needs a CUDA device and the stepper")
     scores = []
     stepper = None
     if use_stepper:
         from ali_hip.step import AliStepper
-        stepper = AliStepper(E, G, D, lr=l_rate, betas=(0.5, 0.9), family=family, capture=capture)
+        stepper = AliStepper(E, G, D, lr=l_rate, betas=(0.5, 0.9), family=family, capture=capture, z_seed=z_seed)
         opt_e, opt_d = stepper.opt_eg, stepper.opt_d
     else:
         opt_e = torch.optim.Adam(list(E.parameters()) + list(G.parameters()), lr=l_rate, betas=(0.5, 0.9))
@@ -347,8 +354,11 @@ def train_on_stream(E, G, D, stream_fn, n_batches_hint=None, n_epochs=1, l_rate=
             c = {k: torch.clone(batch[k]).to(cast).to(dev) for k in attr_keys}
             if preprocess is not None:
                 images = preprocess(images)
-            z_mean = torch.zeros((len(images), LATENT_DIM, 1, 1)).float()
-            z = torch.normal(z_mean, z_mean + 1).to(dev)
+            if z_source == "device":
+                z = None
+            else:
+                z_mean = torch.zeros((len(images), LATENT_DIM, 1, 1)).float()
+                z = torch.normal(z_mean, z_mean + 1).to(dev)
             if use_stepper:
                 r = stepper.step(images, c, z)
             else:

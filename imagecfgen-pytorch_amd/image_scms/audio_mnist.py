@@ -76,7 +76,9 @@ def train(path_to_zip,
           batch_size=128,
           image_output_path='',
           checkpoint_every=None,
-          checkpoint_path=None):
+          checkpoint_path=None,
+          z_source="host",
+          z_seed=None):
     """Reference signature (:321-327) and loop (:343-420): statistics pass over the training stream, ``spect_to_img``
     standardisation, ALI iterations with Adam betas (0.5, 0.9).
 
@@ -84,7 +86,8 @@ def train(path_to_zip,
     librosa, not part of this package -- raises ImportError) or a data source with the adapter's interface, e.g.
     ``_spect.WaveformData(waveforms, attrs, **STFT, device=device, runs=...)``: then the whole loop, spectrograms
     included, runs on the device.  The demo-image / wav dump of the reference (:422-480, matplotlib + Griffin-Lim) is
-    not part of the path."""
+    not part of the path.
+    ``z_source="device"`` / ``z_seed``: draw the latents on the device inside the iteration (``_spect.train_on_stream``)."""
     E, G, D = Encoder().to(device), Generator().to(device), Discriminator().to(device)
     for m in (E, G, D):
         m.apply(init_weights)
@@ -92,4 +95,4 @@ def train(path_to_zip,
     keys = [k for k in data.data if k in ATTRIBUTE_DIMS]
     return _spect.run_training(E, G, D, data, dict(batch_size=batch_size, excluded_runs=VALIDATION_RUNS), keys,
                                n_epochs, l_rate, device, checkpoint_every=checkpoint_every,
-                               checkpoint_path=checkpoint_path)
+                               checkpoint_path=checkpoint_path, z_source=z_source, z_seed=z_seed)

@@ -71,11 +71,14 @@ def train(path_to_wavs,
           validation_split=0.2,
           start_model_path=None,
           checkpoint_every=None,
-          checkpoint_path=None):
+          checkpoint_path=None,
+          z_source="host",
+          z_seed=None):
     """Reference signature (:263-272) and loop (:298-379).  ``start_model_path`` warm-starts from a pickled-module
     checkpoint (:280-284; optimiser state is not restored, as in the reference).  ``path_to_wavs`` may be a data
     source with the adapter's interface (``_spect.WaveformData(..., **STFT)``) instead of the wav directory, which
-    needs the reference's ``EsrfStation`` reader (torchaudio, pandas label tables; raises ImportError here)."""
+    needs the reference's ``EsrfStation`` reader (torchaudio, pandas label tables; raises ImportError here).
+    ``z_source="device"`` / ``z_seed``: draw the latents on the device inside the iteration (``_spect.train_on_stream``)."""
     E, G, D = Encoder().to(device), Generator().to(device), Discriminator().to(device)
     for m in (E, G, D):
         m.apply(init_weights)
@@ -88,4 +91,4 @@ def train(path_to_wavs,
         data = EsrfStation(path_to_wavs, path_to_labels, device=device, validation_split=validation_split)
     return _spect.run_training(E, G, D, data, dict(batch_size=batch_size, mode='train'), tuple(ATTRIBUTE_DIMS),
                                n_epochs, l_rate, device, checkpoint_every=checkpoint_every,
-                               checkpoint_path=checkpoint_path)
+                               checkpoint_path=checkpoint_path, z_source=z_source, z_seed=z_seed)

@@ -164,14 +164,27 @@ def train(x_train: torch.Tensor,
           d_updates_per_g_update=1,
           use_stepper=None,
           checkpoint_every=None,
-          checkpoint_path=None):
+          checkpoint_path=None,
+          input_pipeline="host",
+          z_seed=None):
     """Same signature, RNG order and return value as the reference's train (mnist.py:157-299).
     ``checkpoint_every`` (epochs) + ``checkpoint_path``: periodic resumable checkpoints in the state-dict format
     ``load_model`` reads, plus both Adam states (the reference only saves at the end, from its caller).
 
     On a CUDA device the iteration runs on the hand-scheduled ``AliStepper`` (HIP-graph replay; ``use_stepper=False``
     keeps the autograd schedule on the same kernels); the two returned optimisers are then its flat Adam groups
-    (``state_dict`` / ``zero_grad`` / ``step`` like ``torch.optim.Adam``).  CPU devices run the stock torch ops."""
+    (``state_dict`` / ``zero_grad`` / ``step`` like ``torch.optim.Adam``).  CPU devices run the stock torch ops.
+
+    ``input_pipeline="device"`` (CUDA + stepper only): the data set is uploaded once (uint8 stays uint8) and every
+    iteration assembles its batch and draws its latents on the device, inside the captured iteration
+    (``AliStepper.step_indexed``); per step the host only names a slice of the epoch's permutation, which still comes
+    from ``np.random.permutation``.  The latents are then the counter stream keyed by ``z_seed`` and the iteration
+    number (``ali_hip.source.normal_reference``) instead of torch's host generator, whose state this mode leaves
+    alone.  The default, ``"host"``, is the reference's order of host draws."""
+    if input_pipeline not in ("host", "device"):
+        raise ValueError(f"input_pipeline must be 'host' or 'device', got {input_pipeline!r}")
+    if input_pipeline == "device" and (torch.device(device).type != "cuda" or use_stepper is False):
+        raise ValueError("input_pipeline='device' needs a CUDA device and the stepper (use_stepper is not False)")
     E, G, D = Encoder().to(device), Generator().to(device), Discriminator().to(device)
     for m in (E, G, D):
         m.apply(init_weights)
@@ -180,35 +193,47 @@ def train(x_train: torch.Tensor,
     stepper = None
     if use_stepper:
         from ali_hip.step import AliStepper
-        stepper = AliStepper(E, G, D, lr=l_rate, betas=(0.5, 0.999), capture=True)
+        stepper = AliStepper(E, G, D, lr=l_rate, betas=(0.5, 0.999), capture=True, z_seed=z_seed)
         optimizer_E, optimizer_D = stepper.opt_eg, stepper.opt_d
     else:
         optimizer_E = torch.optim.Adam(list(E.parameters()) + list(G.parameters()), lr=l_rate, betas=(0.5, 0.999))
         optimizer_D = torch.optim.Adam(D.parameters(), lr=l_rate, betas=(0.5, 0.999))
     gan_loss = nn.BCEWithLogitsLoss()
+    source = None
+    if input_pipeline == "device":
+        from ali_hip.source import DeviceDataset
+        source = DeviceDataset(x_train, a_train, device, batch_size=batch_size)
 
     for epoch in range(n_epochs):
         for m in (D, E, G):
             m.train()
         perm = np.random.permutation(len(x_train))
-        img_batches = batchify(x_train[perm], batch_size=batch_size)
-        attr_batches = batchify_dict({k: v[perm] for k, v in a_train.items()}, batch_size=batch_size)
         attr_stats = {k: (v.min(dim=0).values, v.max(dim=0).values) for k, v in a_train.items() if k != "digit"}
         d_score = torch.zeros((), device=device)
         eg_score = torch.zeros((), device=device)
         num_batches = 0
-        for i, ((images,), attrs) in enumerate(zip(img_batches, attr_batches)):
-            num_batches += 1
-            images, c = _scale_batch(images, attrs, attr_stats, device)
-            z_mean = torch.zeros((len(images), LATENT_DIM, 1, 1)).float()
-            z = torch.normal(z_mean, z_mean + 1).to(device)               # sampled on the host like the reference
-            if stepper is not None:
-                r = stepper.step(images, c, z, do_eg=(i % d_updates_per_g_update == 0))
-            else:
-                r = ali_step(E, G, D, optimizer_E, optimizer_D, images, c, z,
-                             do_eg=(i % d_updates_per_g_update == 0), gan_loss=gan_loss)
-            d_score += r["dg"]                                            # accumulated on device: one sync per epoch
-            eg_score += r["de"]
+        if source is not None:
+            source.set_epoch(perm)
+            for i in range(source.n_batches):          # per batch the host names a slice of the uploaded permutation
+                num_batches += 1
+                r = stepper.step_indexed(source, source.batch(i), do_eg=(i % d_updates_per_g_update == 0))
+                d_score += r["dg"]
+                eg_score += r["de"]
+        else:
+            img_batches = batchify(x_train[perm], batch_size=batch_size)
+            attr_batches = batchify_dict({k: v[perm] for k, v in a_train.items()}, batch_size=batch_size)
+            for i, ((images,), attrs) in enumerate(zip(img_batches, attr_batches)):
+                num_batches += 1
+                images, c = _scale_batch(images, attrs, attr_stats, device)
+                z_mean = torch.zeros((len(images), LATENT_DIM, 1, 1)).float()
+                z = torch.normal(z_mean, z_mean + 1).to(device)           # sampled on the host like the reference
+                if stepper is not None:
+                    r = stepper.step(images, c, z, do_eg=(i % d_updates_per_g_update == 0))
+                else:
+                    r = ali_step(E, G, D, optimizer_E, optimizer_D, images, c, z,
+                                 do_eg=(i % d_updates_per_g_update == 0), gan_loss=gan_loss)
+                d_score += r["dg"]                                        # accumulated on device: one sync per epoch
+                eg_score += r["de"]
         print(d_score.item() / num_batches, eg_score.item() / num_batches)
 
         if save_images_every and (epoch + 1) % save_images_every == 0 and x_test is not None:

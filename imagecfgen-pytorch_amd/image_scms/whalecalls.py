@@ -70,11 +70,14 @@ def train(nocall_directory,
           image_output_path='',
           filter_length=None,
           checkpoint_every=None,
-          checkpoint_path=None):
+          checkpoint_path=None,
+          z_source="host",
+          z_seed=None):
     """Reference signature (:390-399) and loop (:426-499): statistics pass, ``spect_to_img``, BiGAN iterations with
     the attributes cast to int (:455).  ``nocall_directory`` may be a data source with the adapter's interface
     (``_spect.WaveformData(..., **STFT)``) instead of the three NARW recording directories, which need the reference's
-    ``WhaleCallData`` reader (torchaudio, scipy wav/mat files; raises ImportError here)."""
+    ``WhaleCallData`` reader (torchaudio, scipy wav/mat files; raises ImportError here).
+    ``z_source="device"`` / ``z_seed``: draw the latents on the device inside the iteration (``_spect.train_on_stream``)."""
     E, G, D = Encoder().to(device), Generator().to(device), Discriminator().to(device)
     for m in (E, G, D):
         m.apply(init_weights)
@@ -85,4 +88,4 @@ def train(nocall_directory,
                              filter_length=filter_length)
     return _spect.run_training(E, G, D, data, dict(batch_size=batch_size), _KEYS, n_epochs, l_rate, device,
                                attr_cast=torch.int32, checkpoint_every=checkpoint_every,
-                               checkpoint_path=checkpoint_path)
+                               checkpoint_path=checkpoint_path, z_source=z_source, z_seed=z_seed)

@@ -361,6 +361,29 @@ int ali_bce_logits_pair(const float* logit, int32_t B, float target_a, float tar
 int ali_attr_pack(const void* const* cat, const int32_t* n_classes, const int32_t* cat_is_int, int32_t n_cat,
                   const float* const* cont_in, int32_t n_cont, int32_t B, int32_t* idx, float* cont, ali_stream_t stream);
 
+/* Device-side input pipeline (opt-in: mnist.train(input_pipeline="device"), train_on_stream(z_source="device")).
+ *
+ * ali_normal_fill: out[i] ~ N(0,1), i < n, from the counter RNG of ali_dropout_mask under a key of its own (seed,
+ * *dev_counter and a latent-stream constant; dev_counter may be NULL).  Element g = offset + i is the cosine (g even)
+ * or sine (g odd) half of the Box-Muller pair of hash g >> 1, u1 in (0,1] and u2 in [0,1) being disjoint 24-bit
+ * fields of that hash: a value depends on (seed, counter, g) alone, so a buffer filled by one launch equals the same
+ * buffer filled piecewise, whatever the split or the alignment of out (4-byte aligned; 16-byte stores inside).
+ * ali_hip.source.normal_reference is the recipe in fp64.
+ *
+ * ali_batch_gather: one training batch from a data set resident in device memory, rows index[b] (device int64) of
+ * images [N][HW] (uint8 if images_u8, else fp32) and attrs [N][attr_ld] fp32 = [one-hot (n_cls) | continuous (n_cont)]:
+ *   out_images[b][:]  = 2*x/255 - 1 (mnist.py:204; the division as torch's device kernel performs it: times the fp32
+ *                       reciprocal of the scalar)
+ *   out_onehot[b][:]  = the one-hot row;  out_idx[b] = its first maximum (torch.argmax)
+ *   out_cont[b][j]    = 2*(a - lo[j])/(hi[j] - lo[j]) - 1 (mnist.py:206, IEEE division, nothing contracted)
+ * -- bit for bit what image_scms.mnist._scale_batch + MnistFamily.conditioning hand the stepper.  An index outside
+ * [0, N) reads nothing and yields NaN. */
+int ali_normal_fill(uint64_t seed, const int64_t* dev_counter, uint64_t offset, float* out, int64_t n,
+                    ali_stream_t stream);
+int ali_batch_gather(const void* images, int32_t images_u8, const float* attrs, int32_t attr_ld, const int64_t* index,
+                     const float* lo, const float* hi, int64_t N, int32_t HW, int32_t n_cls, int32_t n_cont, int32_t B,
+                     float* out_images, float* out_onehot, int32_t* out_idx, float* out_cont, ali_stream_t stream);
+
 /* Generator input (mnist.py:76-85; audio_mnist.py:250-256): out[b*ld + :] = [ z[b, :zdim] | onehot_j[b] @ tables[j]
  * ([n_classes[j]][256]) for j < n_emb | cont[b, :n_cont] | zeros ] -- a true sum over classes (soft attributes), the
  * zero padding brings the row to the GEMM's channel stride.  ali_g_input_table_grad: the gradient of one table,
