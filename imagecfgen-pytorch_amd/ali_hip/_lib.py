@@ -125,6 +125,10 @@ SIGNATURES = {
                          + [c_void_p]),
     "ali_tconv1_wgrad": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int64, c_int64, c_int64]
                          + [c_int32] * 7 + [c_void_p, c_size_t, c_void_p]),
+    "ali_ssim_fwd": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int32, c_float, c_float,
+                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "ali_ssim_bwd": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32,
+                               c_void_p, c_int32, c_void_p, c_void_p]),
     "ali_last_error": (c_char_p, []),
     "ali_head_fwd": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     "ali_head_wgrad": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),

@@ -1019,6 +1019,36 @@ def spect_post(y, B, T, F, out, mean=None, std=None, clip_k=3.0):
     return out
 
 
+def ssim_fwd(X, Y, win, C1, C2, want_maps=False):
+    """SSIM of the [planes,H,W] pairs X, Y (include/ali_hip.h: ali_ssim_fwd), ``win`` the 1-D window on the device.
+    Returns (ssim_pc [planes], maps [3,planes,Hm,Wm] = A, Bq, Cq for ``ssim_bwd``, or None)."""
+    lib = _lib.load()
+    planes, H, W = X.shape
+    n = win.numel()
+    if Y.shape != X.shape:
+        raise ValueError(f"ssim_fwd: shapes differ: {tuple(X.shape)} vs {tuple(Y.shape)}")
+    pc = torch.empty(planes, dtype=torch.float32, device=X.device)
+    maps = torch.empty((3, planes, max(H - n + 1, 0), max(W - n + 1, 0)), dtype=torch.float32,
+                       device=X.device) if want_maps else None
+    m = [None] * 3 if maps is None else [c_void_p(maps[i].data_ptr()) for i in range(3)]
+    ws = workspace(X.device)
+    _lib.check(lib.ali_ssim_fwd(_chk(X, "X"), _chk(Y, "Y"), planes, H, W, _chk(win, "win"), n, float(C1), float(C2),
+                                _chk(pc), m[0], m[1], m[2], c_void_p(ws.data_ptr()), ws.numel(), _stream()),
+               "ali_ssim_fwd")
+    return pc, maps
+
+
+def ssim_bwd(X, Y, maps, gpc, win, out=None):
+    """d sum(gpc * ssim_pc) / dY from the maps ``ssim_fwd(X, Y, ..., want_maps=True)`` left; gpc [planes] on the device."""
+    lib = _lib.load()
+    planes, H, W = X.shape
+    out = torch.empty_like(Y) if out is None else out
+    _lib.check(lib.ali_ssim_bwd(_chk(X, "X"), _chk(Y, "Y"), c_void_p(maps[0].data_ptr()), c_void_p(maps[1].data_ptr()),
+                                c_void_p(maps[2].data_ptr()), _chk(gpc, "gpc"), planes, H, W, _chk(win, "win"),
+                                win.numel(), _chk(out, "out"), _stream()), "ali_ssim_bwd")
+    return out
+
+
 def bce_logits(logit, target, gscale=1.0, want_grad=True):
     """returns (out2 = [loss, mean sigmoid] device tensor, glogit or None)."""
     lib = _lib.load()

@@ -27,6 +27,7 @@ from . import dp
 from . import dropout as _dropout
 from . import ops
 from . import source as _source
+from . import ssim
 from . import chain as _chain
 from .chain import (chain_backward, chain_backward_gen, chain_forward, chain_forward_gen, drive, get_plan,
                     run_parallel, slice_saved)
@@ -971,11 +972,20 @@ class FinetuneStepper:
     whole batch dict with extra keys (the whale script passes it as is).  ``x`` of shape [B,H,W] (the whale script
     never adds the channel axis) makes ``x - xr`` broadcast to all B*B pairs, exactly as in the reference; [B,1,H,W]
     is the ordinary per-sample error.  ``capture=True`` replays the step from a HIP graph per input shape.
-    ``step`` returns {"rec": mse, "latent": mean(codes^2)} as 0-d device tensors (no host sync)."""
+    ``metric="ssim"`` (finetune_mnist_bigan.py:75-76, finetune_audio_mnist_bigan.py:82-83) replaces the first term by
+    ``1 - ssim(x, xr, data_range=1.0).mean()`` on the kernels of csrc/ssim.hip, inside the same step (and graph); it
+    needs ``x`` as [B,1,H,W].
+    ``step`` returns {"rec": mse or 1 - ssim, "latent": mean(codes^2)} as 0-d device tensors (no host sync)."""
 
-    def __init__(self, E, G, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, family=None, capture=False):
+    def __init__(self, E, G, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, family=None, capture=False, metric="mse"):
+        if metric not in ("mse", "ssim"):
+            raise ValueError(f"Invalid metric {metric}")
+        self.metric = metric
+        self._ssim_cot = {}                     # (B, device) -> the constant cotangent -1/B of every plane's ssim
         self.E, self.G = E, G
         self.family = family or (SpectFamily(E, G, E) if hasattr(E, "cat_keys") else _mnist_family_eg(E, G))
+        if metric == "ssim" and min(self.family.hw) < 11:
+            raise ValueError(f"metric='ssim' needs images of at least 11x11 (the window), got {self.family.hw}")
         self.pE, self.pG = get_plan(E.layers), get_plan(G.layers)
         self.opt_e = FlatGroup(list(E.parameters()), lr, betas, eps)
         self.pE.cache.store.clear()
@@ -985,6 +995,8 @@ class FinetuneStepper:
 
     @torch.no_grad()
     def step(self, x, a):
+        if self.metric == "ssim" and x.dim() != 4:
+            raise ValueError(f"metric='ssim' needs x as [B,1,H,W], got {tuple(x.shape)}")
         a = self.family.used(a)
         if not (self.capture and x.is_cuda):
             return self._step(x, a)
@@ -1023,7 +1035,17 @@ class FinetuneStepper:
         gin, g_log = _g_input(fam, zin, onehots, cont)
         xr, sG = chain_forward(self.pG, gin, self.G.training, g_log, True)
         xf, xrf = x.reshape(B, -1).float(), xr.reshape(B, -1)
-        if pairwise:
+        if self.metric == "ssim":
+            # rec = 1 - mean_b ssim_pc[b]; its gradient is the backward launch with -1/B as every plane's cotangent
+            win = ssim.gaussian_window(11, 1.5, x.device)
+            cot = self._ssim_cot.get((B, x.device))
+            if cot is None:                         # (first made by the eager step / the warm-up pass, never in capture)
+                cot = self._ssim_cot[(B, x.device)] = torch.full((B,), -1.0 / B, device=x.device)
+            xi, xri = xf.reshape(B, H, W), xrf.reshape(B, H, W)
+            pc, maps = ops.ssim_fwd(xi, xri, win, 0.01 ** 2, 0.03 ** 2, want_maps=True)
+            rec = 1.0 - pc.mean()
+            g_xr = ops.ssim_bwd(xi, xri, maps, cot, win).reshape(xr.shape)
+        elif pairwise:
             # mean_{i,j,p} (x_jp - xr_ip)^2 and its gradient 2/(B*P) * (xr_ip - mean_j x_jp)
             xbar = xf.mean(dim=0, keepdim=True)
             rec = xrf.square().mean() - 2.0 * (xrf.mean(dim=0) * xbar[0]).mean() + xf.square().mean()

@@ -6,11 +6,10 @@ is ``ali_step`` so callers and tests can drive one iteration.
 import torch
 import torch.nn as nn
 
-try:  # only rec_loss(metric='ssim') needs it (reference training_utils.py:3,91)
+try:  # rec_loss(metric='ssim') (reference training_utils.py:3,91); an installed pytorch_msssim keeps precedence
     from pytorch_msssim import ssim
-except Exception:  # pragma: no cover
-    def ssim(*args, **kwargs):
-        raise ImportError("pytorch_msssim is not installed; use metric='mse'")
+except Exception:
+    from ali_hip.ssim import ssim  # same definition on the HIP kernels (CUDA tensors) / stock torch ops (CPU)
 
 
 def batchify(*tensors, batch_size=128, device='cpu'):

@@ -452,6 +452,26 @@ int ali_tconv_scatter_wgrad(const float* big, const float* small, int32_t sstrid
 int ali_spect_post(const float* y, int32_t B, int32_t T, int32_t F, const float* mean, const float* std, float clip_k,
                    float* out, ali_stream_t stream);
 
+/* SSIM of image pairs and its gradient (the --metric ssim loss of the encoder fine-tuning scripts,
+ * finetune_mnist_bigan.py:75-76; definition: pytorch_msssim.ssim).  X, Y are `planes` = B*C contiguous H x W planes,
+ * `win` the win_size taps g of the 1-D window on the device (win_size odd, <= ALI_SSIM_MAX_WIN, <= H, W).  With F the
+ * separable valid correlation with g along H and W (map Hm x Wm = (H-win_size+1) x (W-win_size+1)):
+ *   mu1 = F(X), mu2 = F(Y), s1 = F(X*X) - mu1^2, s2 = F(Y*Y) - mu2^2, s12 = F(X*Y) - mu1*mu2,
+ *   cs = (2*s12 + C2) / (s1 + s2 + C2),  S = (2*mu1*mu2 + C1) / (mu1^2 + mu2^2 + C1) * cs,
+ *   ssim_pc[plane] = mean over the map of S.
+ * mA/mB/mC (all three or none), each [planes][Hm][Wm], receive A = dS/dF(Y), Bq = dS/dF(Y*Y), Cq = dS/dF(X*Y).
+ * Planes larger than one 32x32 map tile put planes*tiles partial sums into the workspace (fixed-order fold). */
+#define ALI_SSIM_MAX_WIN 25
+int ali_ssim_fwd(const float* X, const float* Y, int64_t planes, int32_t H, int32_t W, const float* win,
+                 int32_t win_size, float C1, float C2, float* ssim_pc, float* mA, float* mB, float* mC, void* ws,
+                 size_t ws_bytes, ali_stream_t stream);
+/* dY[plane][p] = gpc[plane] / (Hm*Wm) * (Ft(A)[p] + 2*Y[p]*Ft(Bq)[p] + X[p]*Ft(Cq)[p]), Ft the transposed (full)
+ * filter and gpc[planes] the incoming gradient of ssim_pc on the device.  The metric is symmetric: the gradient
+ * w.r.t. X is the same pair of calls with X and Y exchanged. */
+int ali_ssim_bwd(const float* X, const float* Y, const float* mA, const float* mB, const float* mC, const float* gpc,
+                 int64_t planes, int32_t H, int32_t W, const float* win, int32_t win_size, float* dY,
+                 ali_stream_t stream);
+
 const char* ali_last_error(void);
 /* The Discriminator's one-output head, Conv2d(C, 1, 1) on a 1x1 map (mnist.py:127), as a GEMV:
  *   ali_head_fwd  : y[b] = bias[0] + sum_c x[b][c] * w[c]            (x rows ld floats apart, C % 4 == 0)
