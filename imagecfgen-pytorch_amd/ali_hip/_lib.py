@@ -129,6 +129,12 @@ SIGNATURES = {
                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "ali_ssim_bwd": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32,
                                c_void_p, c_int32, c_void_p, c_void_p]),
+    "ali_gl_init": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_float, c_float, c_void_p,
+                              c_void_p, c_int32, c_uint64, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p]),
+    "ali_gl_ola": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int64, c_int32,
+                             c_void_p, c_int32, c_void_p, c_void_p]),
+    "ali_gl_phase": (c_int32, [c_void_p, c_void_p, c_void_p, c_float, c_int64, c_int32, c_void_p, c_void_p]),
+    "ali_gl_check": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int64]),
     "ali_last_error": (c_char_p, []),
     "ali_head_fwd": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     "ali_head_wgrad": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),

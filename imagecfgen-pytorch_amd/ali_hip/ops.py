@@ -1019,6 +1019,57 @@ def spect_post(y, B, T, F, out, mean=None, std=None, clip_k=3.0):
     return out
 
 
+GL_SRC_IMAGE, GL_SRC_LOG, GL_SRC_SPEC = 0, 1, 2
+
+
+def _counter_ptr(t):
+    if t is None:
+        return None
+    if not (t.is_cuda and t.dtype == torch.int64 and t.numel() == 1):
+        raise ValueError("need a one-element int64 CUDA tensor as device counter")
+    return c_void_p(t.data_ptr())
+
+
+def gl_check(n_fft, win, hop, T, length=0):
+    """the window-envelope condition of ``torch.istft`` for T frames (include/ali_hip.h: ali_gl_check; host only):
+    True / False, ``ValueError`` unless 0 < hop <= win <= n_fft"""
+    rc = _lib.load().ali_gl_check(n_fft, win, hop, T, int(length or 0))
+    if rc < 0:
+        msg = _lib.load().ali_last_error()
+        raise ValueError(msg.decode() if msg else "ali_gl_check: bad argument")
+    return bool(rc)
+
+
+def gl_init(src, mode, mag, X, power=2.0, mean=None, std=None, stds_kept=3.0, angles0=None, rand_init=True, seed=0,
+            dev_counter=None, offset=0):
+    """src [B,F,T] -> mag [B*T,F], X [B*T,2F] (include/ali_hip.h: ali_gl_init); ``angles0`` = (re, im) planes [B,F,T]"""
+    B, F, T = src.shape
+    re, im = (None, None) if angles0 is None else angles0
+    _lib.check(_lib.load().ali_gl_init(_chk(src, "src"), B, F, T, mode, _opt(mean, "mean"), _opt(std, "std"),
+                                       float(stds_kept), float(power), _opt(re, "angles0.re"), _opt(im, "angles0.im"),
+                                       int(bool(rand_init)), int(seed) & (2 ** 64 - 1), _counter_ptr(dev_counter),
+                                       int(offset), _chk(mag, "mag"), _chk(X, "X"), _stream()), "ali_gl_init")
+    return mag, X
+
+
+def gl_ola(fr, renv, n_fft, hop, length, out, final=False, frames_per_block=0, advance=None):
+    """fr [B,T,win] inverse frames -> the next transform's frames [B,T,win] or (``final``) the waveform [B,length]
+    (include/ali_hip.h: ali_gl_ola)"""
+    B, T, win = fr.shape
+    _lib.check(_lib.load().ali_gl_ola(_chk(fr, "fr"), _chk(renv, "renv"), renv.numel(), B, T, n_fft, win, hop, int(length),
+                                      int(bool(final)), _chk(out, "out"), int(frames_per_block), _counter_ptr(advance),
+                                      _stream()), "ali_gl_ola")
+    return out
+
+
+def gl_phase(Y, tprev, mag, m, X):
+    """X = (Y - m*tprev) / (|.| + 1e-16) * mag over [rows,2F] spectra (include/ali_hip.h: ali_gl_phase)"""
+    rows, F = mag.shape
+    _lib.check(_lib.load().ali_gl_phase(_chk(Y, "Y"), _opt(tprev, "tprev"), _chk(mag, "mag"), float(m), rows, F,
+                                        _chk(X, "X"), _stream()), "ali_gl_phase")
+    return X
+
+
 def ssim_fwd(X, Y, win, C1, C2, want_maps=False):
     """SSIM of the [planes,H,W] pairs X, Y (include/ali_hip.h: ali_ssim_fwd), ``win`` the 1-D window on the device.
     Returns (ssim_pc [planes], maps [3,planes,Hm,Wm] = A, Bq, Cq for ``ssim_bwd``, or None)."""

@@ -71,6 +71,16 @@ constexpr size_t kWsReserved = ALI_WS_RESERVED;
 inline void* ws_payload(void* ws) { return ws ? static_cast<char*>(ws) + kWsReserved : nullptr; }
 inline size_t ws_payload_bytes(size_t bytes) { return bytes > kWsReserved ? bytes - kWsReserved : 0; }
 
+// splitmix64's finaliser: the hash of the counter RNG (Dropout2d masks, latents: elementwise.hip; Griffin-Lim phases:
+// griffinlim.hip).  A stream's key is mix64(mix64(seed) ^ counter * kCounterMul), one more round per stream constant.
+constexpr uint64_t kCounterMul = 0xD1B54A32D192ED03ull;
+__host__ __device__ __forceinline__ uint64_t mix64(uint64_t z) {
+  z += 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
 __device__ __forceinline__ float apply_act(float v, int act, float slope) {
   if (act == ALI_ACT_LEAKY) return v > 0.f ? v : v * slope;
   if (act == ALI_ACT_TANH) return tanhf(v);

@@ -204,13 +204,7 @@ __global__ void rowmask_mul_kernel(const float* __restrict__ x, const float* __r
   }
 }
 
-// splitmix64-based counter RNG: one draw per (seed, offset + i)
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
+// splitmix64-based counter RNG (mix64: ali_common.h): one draw per (seed, offset + i)
 __global__ void dropout_mask_kernel(uint64_t seed, uint64_t offset, const long long* __restrict__ dev_counter, float p,
                                     float* __restrict__ out, long long n) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;

@@ -182,7 +182,7 @@ class WaveformData:
     """
 
     def __init__(self, waveforms, attrs, n_fft, win_length, hop_length=None, pad=0, device="cpu", runs=None,
-                 subjects=None):
+                 subjects=None, griffin_lim=None):
         self.device = torch.device(device)
         self.wave = torch.as_tensor(waveforms).float().to(self.device)
         self.data = {"audio": self.wave}
@@ -192,6 +192,40 @@ class WaveformData:
         self.stft = dict(n_fft=n_fft, win_length=win_length, hop_length=hop_length or win_length // 2, pad=pad)
         self._front = None
         self._stats = None
+        # the way back (reference: torchaudio.transforms.GriffinLim next to the Spectrogram, audio_mnist.py:62-64,117):
+        # ``griffin_lim`` = its keyword arguments (the family files' GRIFFIN_LIM), default: the STFT's own settings
+        self.griffin_lim = dict(griffin_lim) if griffin_lim is not None else dict(
+            n_fft=n_fft, win_length=win_length, hop_length=self.stft["hop_length"])
+        self._back = None
+        self.inv_transforms = {k: (lambda x: x) for k in self.data}
+        self.inv_transforms["audio"] = self._inv_audio
+
+    def spectrogram_to_audio(self, spec, angles0=None):
+        """power spectrogram [..., F, T] -> waveform [..., length] by Griffin-Lim (32 iterations, momentum 0.99,
+        random initial phases unless ``angles0`` [..., F, T] complex is given): ``ali_hip.griffinlim.GriffinLim`` for
+        CUDA tensors, the ``torch.stft`` / ``torch.istft`` statement of the same algorithm for CPU tensors."""
+        from ali_hip import griffinlim as _gl
+        if not spec.is_cuda:
+            return _gl.griffinlim_torch(spec, angles0=angles0, **self.griffin_lim)
+        return self._griffinlim(spec.device)(spec, angles0)
+
+    def image_to_audio(self, log_spec, angles0=None):
+        """``spectrogram_to_audio(log_spec.exp())`` (whalecalls.py:59, esrf_acoustic.py:43)"""
+        if not log_spec.is_cuda:
+            return self.spectrogram_to_audio(log_spec.exp(), angles0)
+        return self._griffinlim(log_spec.device).from_log(log_spec, angles0)
+
+    def _griffinlim(self, device):
+        if self._back is None:
+            from ali_hip.griffinlim import GriffinLim
+            self._back = GriffinLim(device=device, **self.griffin_lim)
+        return self._back
+
+    def _inv_audio(self, x):
+        """``inv_transforms["audio"]`` (audio_mnist.py:117): a log-spectrogram, numpy or tensor, to audio on the
+        source's device"""
+        x = torch.from_numpy(x) if isinstance(x, np.ndarray) else x
+        return self.image_to_audio(x.to(self.device))
 
     def fuse_spect_to_img(self, mean, std=None, stds_kept=3.0):
         """``fuse_spect_to_img(None)`` returns the stream to plain log-spectrograms (what every other consumer of the
@@ -239,6 +273,11 @@ class WaveformData:
             if transform:
                 batch["audio"] = self.spectrogram(batch["audio"])
             yield batch
+
+
+def img_to_spect(img, mean, std, stds_kept=3):
+    """inverse of ``spect_to_img`` up to its clipping (audio_mnist.py:365-366): standardised image -> log-spectrogram"""
+    return img * stds_kept * (std + 1e-6) + mean
 
 
 def is_data_source(obj):

@@ -66,6 +66,8 @@ class Discriminator(_Family, _spect.SpectDiscriminator):
 
 
 STFT = dict(n_fft=255, win_length=128, pad=96)     # AudioMNISTData.audio_to_spectrogram (reference :59-61)
+GRIFFIN_LIM = dict(n_fft=255, win_length=128)      # AudioMNISTData.spectrogram_to_audio (:62-64): default hop 64;
+#                                                    ``_spect.WaveformData(..., **STFT, griffin_lim=GRIFFIN_LIM)``
 
 
 def train(path_to_zip,
@@ -85,8 +87,8 @@ def train(path_to_zip,
     ``path_to_zip`` is either the AudioMNIST zip (needs the reference's ``AudioMNISTData`` reader: torchaudio +
     librosa, not part of this package -- raises ImportError) or a data source with the adapter's interface, e.g.
     ``_spect.WaveformData(waveforms, attrs, **STFT, device=device, runs=...)``: then the whole loop, spectrograms
-    included, runs on the device.  The demo-image / wav dump of the reference (:422-480, matplotlib + Griffin-Lim) is
-    not part of the path.
+    included, runs on the device.  The demo-image / wav dump of the reference (:422-480, matplotlib) is
+    not part of the path; the Griffin-Lim transform it calls is the source's ``inv_transforms["audio"]``.
     ``z_source="device"`` / ``z_seed``: draw the latents on the device inside the iteration (``_spect.train_on_stream``)."""
     E, G, D = Encoder().to(device), Generator().to(device), Discriminator().to(device)
     for m in (E, G, D):

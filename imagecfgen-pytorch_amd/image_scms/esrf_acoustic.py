@@ -58,6 +58,8 @@ class Discriminator(_Family, _spect.SpectDiscriminator):
 
 
 STFT = dict(n_fft=1023, win_length=256, hop_length=79, pad=200)   # EsrfStation.audio_to_spectrogram (reference :36-39)
+GRIFFIN_LIM = dict(n_fft=1023, win_length=256, hop_length=79)     # EsrfStation.spectrogram_to_audio (:40-43);
+#                                                                   ``_spect.WaveformData(..., **STFT, griffin_lim=GRIFFIN_LIM)``
 
 
 def train(path_to_wavs,

@@ -57,6 +57,8 @@ class Discriminator(_Family, _spect.SpectDiscriminator):
 
 
 STFT = dict(n_fft=511, win_length=128, hop_length=24, pad=64)     # WhaleCallData.audio_to_spectrogram (reference :52-55)
+GRIFFIN_LIM = dict(n_fft=511, win_length=128, hop_length=24)      # WhaleCallData.spectrogram_to_audio (:56-59);
+#                                                                   ``_spect.WaveformData(..., **STFT, griffin_lim=GRIFFIN_LIM)``
 
 
 def train(nocall_directory,

@@ -472,6 +472,47 @@ int ali_ssim_bwd(const float* X, const float* Y, const float* mA, const float* m
                  int64_t planes, int32_t H, int32_t W, const float* win, int32_t win_size, float* dY,
                  ali_stream_t stream);
 
+/* Griffin-Lim phase reconstruction: torchaudio.transforms.GriffinLim as the reference builds it next to every
+ * Spectrogram (image_scms/audio_mnist.py:62-64,117; whalecalls.py:56-59; esrf_acoustic.py:40-43) and calls it on
+ * img_to_spect(G(...)).exp() (audio_mnist_reconstruction.py:64-67, audiomnist_generate.py:94).  F = n_fft/2 + 1 bins,
+ * T frames, left = (n_fft - win)/2, start = n_fft/2.  One iteration is
+ *   X [B*T][2F] --inverse DFT GEMM (ali_conv_fwd 1x1, [win x 2F] matrix)--> fr [B][T][win] --ali_gl_ola--> frames
+ *   [B][T][win] --forward DFT GEMM ([2F x win] matrix of the spectrogram front-end)--> Y [B*T][2F] --ali_gl_phase--> X.
+ *
+ * ali_gl_init: src [B][F][T] -> mag [B*T][F] and X [B*T][2F] = (re | im) of angles * mag.  mode says what src is:
+ *   ALI_GL_SRC_IMAGE  mag = exp((src * stds_kept * (std[t] + 1e-6) + mean[t]) / power)   (img_to_spect, audio_mnist.py:365-366,
+ *                     .exp() and ** (1/power) in one pass; mean / std per last index t)
+ *   ALI_GL_SRC_LOG    mag = exp(src / power)        ALI_GL_SRC_SPEC   mag = src ** (1/power)
+ * angles = a0_re + i*a0_im ([B][F][T] planes, both or none); else, with rand_init, re and im uniform in [0,1): the two
+ * disjoint 24-bit fields (bits 40..63 / 16..39) of hash offset + e, e = (b*F + f)*T + t, of the counter RNG of
+ * ali_dropout_mask under a key of its own (seed, *dev_counter -- may be NULL -- and a phase-stream constant): a draw
+ * depends on (seed, counter, offset + e) alone (ali_hip.griffinlim.uniform_reference is the host recipe); else 1 + 0i.
+ *
+ * ali_gl_ola: y[p] = (sum over the frames t that reach p, ascending, of fr[b][t][p - t*hop - left]) * renv[p], renv the
+ * reciprocal window envelope 1 / sum_t w^2 over the un-cut signal (n_renv entries, p >= n_renv reads 0): gather form,
+ * no atomics, bit-reproducible.  final_wave == 0: out [B][T][win] = the next transform's frames,
+ * out[b][t][j] = y[start + reflect(t*hop + left + j - start)], reflect the centre=True / pad_mode="reflect" map of a
+ * signal of `length` samples (which must have T frames); final_wave != 0: out [B][length] = y[start + i], zero behind
+ * the signal's end (torch.istft(length=)), and *advance (optional device counter) += 1.  A block owns frames_per_block
+ * consecutive frames of one clip (0: chosen so that its staged rows fit 48 KiB of LDS).
+ *
+ * ali_gl_phase: per bin of the `rows` x F spectra Y / tprev / X ([rows][2F], re | im) and mag ([rows][F]):
+ *   a = Y - m*tprev (tprev NULL or m == 0: a = Y), X = a * (1 / (|a| + 1e-16)) * mag; a == 0 gives 0, nothing gives NaN.
+ *
+ * ali_gl_check (host only): 1 when the window envelope exceeds 1e-11 over the kept range [start, start + length)
+ * (length <= 0: to the signal's end less start) -- the condition torch.istft checks --, 0 when it does not, ALI_ERR_BAD_ARG
+ * unless 0 < hop <= win <= n_fft. */
+typedef enum { ALI_GL_SRC_IMAGE = 0, ALI_GL_SRC_LOG = 1, ALI_GL_SRC_SPEC = 2 } AliGlSource;
+int ali_gl_init(const float* src, int32_t B, int32_t F, int32_t T, int32_t mode, const float* mean, const float* std,
+                float stds_kept, float power, const float* a0_re, const float* a0_im, int32_t rand_init, uint64_t seed,
+                const int64_t* dev_counter, uint64_t offset, float* mag, float* X, ali_stream_t stream);
+int ali_gl_ola(const float* fr, const float* renv, int32_t n_renv, int32_t B, int32_t T, int32_t n_fft, int32_t win,
+               int32_t hop, int64_t length, int32_t final_wave, float* out, int32_t frames_per_block, int64_t* advance,
+               ali_stream_t stream);
+int ali_gl_phase(const float* Y, const float* tprev, const float* mag, float m, int64_t rows, int32_t F, float* X,
+                 ali_stream_t stream);
+int32_t ali_gl_check(int32_t n_fft, int32_t win, int32_t hop, int32_t T, int64_t length);
+
 const char* ali_last_error(void);
 /* The Discriminator's one-output head, Conv2d(C, 1, 1) on a 1x1 map (mnist.py:127), as a GEMV:
  *   ali_head_fwd  : y[b] = bias[0] + sum_c x[b][c] * w[c]            (x rows ld floats apart, C % 4 == 0)
