@@ -719,6 +719,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_fast_multi_kernel(const WJobs jo
 // reads (pixel x (tap, c)), both one ds_read_b32 per MFMA.  Every block leaves a slab [tap * CL + c][k] (+ its
 // bias-gradient row) for the usual slab fold.
 constexpr int FW_GR = 4;
+constexpr int FW_RED = 256 * 4;     // floats of the bias-gradient fold laid over gch: one f32x4 per thread (launch: LDS size)
 template <int CL, int RS>
 __global__ __launch_bounds__(256) void conv_first_wgrad_kernel(const WDesc d) {
   extern __shared__ __attribute__((aligned(16))) float fw_smem[];
@@ -809,7 +810,7 @@ __global__ __launch_bounds__(256) void conv_first_wgrad_kernel(const WDesc d) {
   }
   if (d.db) {
     __syncthreads();
-    f32x4* red = reinterpret_cast<f32x4*>(gch);          // [32 thread groups][8 channel chunks]
+    f32x4* red = reinterpret_cast<f32x4*>(gch);          // [32 thread groups][8 channel chunks] = FW_RED floats
     red[(t >> 3) * 8 + (t & 7)] = dbacc;
     __syncthreads();
     if (t < 8) {
@@ -1072,7 +1073,11 @@ extern "C" int ali_conv_bwd_weight(const AliConvGeom* g, const float* x, const f
     d.splitk = S;
     d.db = db;
     d.dbws = d.ws + (size_t)S * d.slab;
-    const size_t lds = ((size_t)g->H * g->W * 5 + (size_t)2 * FW_GR * g->Q * 33) * sizeof(float);
+    // (behind the image: the two chunk buffers, reused at the end for the bias-gradient fold (FW_RED) -- which is the
+    // larger of the two on maps fewer than 4 output pixels wide)
+    size_t gch_floats = (size_t)2 * FW_GR * g->Q * 33;
+    if (gch_floats < (size_t)FW_RED) gch_floats = FW_RED;
+    const size_t lds = ((size_t)g->H * g->W * 5 + gch_floats) * sizeof(float);
     hipLaunchKernelGGL((conv_first_wgrad_kernel<5, 5>), dim3(S), dim3(256), lds, stream, d);
     int rc1 = check_launch("conv_first_wgrad_kernel");
     if (rc1) return rc1;

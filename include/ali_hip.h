@@ -44,7 +44,13 @@ typedef enum { ALI_ACT_NONE = 0, ALI_ACT_LEAKY = 1, ALI_ACT_TANH = 2 } AliAct;
 /* Geometry of one Conv2d (cross-correlation) y = conv(x, W):
  *   x [B,H,W,C] (channel stride C, may include zero padding channels)
  *   y [B,P,Q,K] (channel stride K)
- *   W [K][C][R][S] logically; square stride / padding.
+ *   W [K][C][R][S] logically; one stride and one padding for both axes.
+ * Maps and kernels may be rectangular: H != W, P != Q and R != S are supported by ali_conv_fwd, ali_conv_bwd_data
+ * and ali_conv_bwd_weight on every route (R, S <= 5; tests/test_gpu_conv_geometry.py), 1 x n and n x 1 maps included.
+ * The special first-layer kernels behind them (8 -> 32 channels, stride 1; 4 / 8 -> 64 channels, stride 2) take 3x3 /
+ * 5x5 kernels on rectangular maps; any other kernel shape runs on the general GEMM kernel.  ali_conv_fwd takes any
+ * stride, ali_conv_bwd_data strides 1 and 2 (ALI_ERR_BAD_ARG otherwise, dx untouched).  Of the direct one-channel
+ * entry points ali_tconv1_fwd needs a square kernel (R == S) and ali_tconv1_dgrad R*S in {1, 4, 9, 16, 25}.
  * A ConvTranspose2d (mnist.py:64-72, audio_mnist.py:216-242) is described by
  * the Conv2d it is the data-gradient of: x := its output, y := its input. */
 typedef struct {
@@ -189,7 +195,8 @@ int ali_conv_bwd_data(const AliConvGeom* g, const float* dy, const float* w_cxk,
 int ali_conv_bwd_weight(const AliConvGeom* g, const float* x, const float* dy, float* dst,
                         int32_t Cg_log, int32_t Cd_log, int64_t s_dc, int64_t s_gc, int64_t s_tap,
                         float* db /* optional: db[dc] = sum over pixels of dy (Conv2d bias gradient) */,
-                        const int32_t* pixtab /* optional: ali_wgrad_pixtab of the same geometry */,
+                        const int32_t* pixtab /* optional: ali_wgrad_pixtab of the same geometry; NULL = the kernel
+                                                 computes its gather addresses itself, same result bit for bit */,
                         int32_t mfma_f16 /* as AliEpilogue.mfma_f16 (needs pixtab); accumulation and slabs stay fp32 */,
                         const void* x16, const void* dy16 /* optional fp16 twins of x / dy (AliEpilogue.out16 of the
                                                              launches that produced them): read instead of x / dy */,
