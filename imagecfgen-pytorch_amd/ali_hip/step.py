@@ -19,6 +19,7 @@ one RCCL all-reduce per group.  Kernel-layout weight copies have fixed addresses
 re-packed right after the Adam launch that changed them, which makes the whole iteration
 capturable in a HIP graph (``capture=True``).
 """
+from collections import namedtuple
 from typing import Dict
 
 import torch
@@ -182,6 +183,12 @@ def _attr2d(t, B, as_float=False):
     return t.reshape(B, -1).contiguous()
 
 
+def _plane_count(tables, cont):
+    """conv input planes [image | one per embedding table | continuous attributes]: (logical count, padded to 4)"""
+    n_log = 1 + len(tables) + (0 if cont is None else cont.shape[1])
+    return n_log, (n_log + 3) // 4 * 4
+
+
 def _g_input(fam, z, onehots, cont, alloc=None):
     """[z | onehot @ table ... | cont | 0 pad] rows of the Generator's first layer (mnist.py:76-85), one launch;
     channel stride % 32 == 0 -> uniform-tap fast path of the GEMM kernel.  Returns ([B,1,1,ld], logical width)."""
@@ -195,6 +202,45 @@ def _g_input(fam, z, onehots, cont, alloc=None):
 
 def family_of(E, G, D):
     return SpectFamily(E, G, D) if hasattr(E, "cat_keys") else MnistFamily(E, G, D)
+
+
+class _Batch(namedtuple("_Batch", "images c z ahead source index", defaults=(None,) * 6)):
+    """What one AliStepper iteration runs on: the caller's tensors (``z`` None: drawn on the device) with ``ahead``, the
+    _Batch the NEXT call will bring (pipeline_reduce), or rows ``index`` of a resident ``source.DeviceDataset``.  What a
+    graph replay needs of a batch is derived here, side by side."""
+    __slots__ = ()
+
+    @classmethod
+    def host(cls, images, c, z=None, ahead=None):
+        return cls(images, c, z, None if ahead is None else cls(*ahead))    # (ahead: the public (images, c, z) tuple)
+
+    @classmethod
+    def indexed(cls, source, index):
+        return cls(source=source, index=index)
+
+    def tensors(self):
+        """what a replay loads: (images, c[, host-made z][, the next batch's images, c, z]), or the index slice alone"""
+        if self.source is not None:
+            return (self.index,)
+        return (self.images, self.c) + (() if self.z is None else (self.z,)) + (self.ahead or ())[:3]
+
+    def rebind(self, static):
+        """this batch on ``static``: the graphs' own copies of ``tensors()``, in that order"""
+        if self.source is not None:
+            return self._replace(index=static[0])
+        images, c, *rest = static
+        z = None if self.z is None else rest.pop(0)
+        return self._replace(images=images, c=c, z=z, ahead=None if self.ahead is None else _Batch(*rest))
+
+    def graph_key(self):
+        """the batch's part of a graph's key: (image shape | (source.key, rows), next batch announced[, "z" | "indexed"])"""
+        if self.source is not None:
+            return (self.source.key, self.index.numel()), self.ahead is not None, "indexed"
+        return (tuple(self.images.shape), self.ahead is not None) + (() if self.z is not None else ("z",))
+
+    def identity(self):
+        """address + shape of the host-made images and z: how an announced batch is recognised when it arrives"""
+        return (self.images.data_ptr(), tuple(self.images.shape), self.z.data_ptr(), tuple(self.z.shape))
 
 
 class _Graphed:
@@ -266,11 +312,12 @@ class AliStepper:
         # Master weights live in the forward GEMM's layout (FlatGroup.layouts; chain.packed then aliases them).  fp16 path:
         # the Adam launch also writes the fp16 twin of the flat buffer, so the forward packs need no launch either; the
         # data-gradient packs (transposes) are still re-packed, fp16 twins included.
-        lay = _chain.pack_layouts([self.pE, self.pG, self.pDx, self.pDz, self.pDxz])
+        self.plans = (self.pE, self.pG, self.pDx, self.pDz, self.pDxz)
+        lay = _chain.pack_layouts(list(self.plans))
         t16 = precision == "f16" and self.E is not None and next(E.parameters()).is_cuda
         self.opt_eg = FlatGroup(list(E.parameters()) + list(G.parameters()), lr, betas, eps, layouts=lay, twin16=t16)
         self.opt_d = FlatGroup(list(D.parameters()), lr, betas, eps, layouts=lay, twin16=t16)
-        for pl in (self.pE, self.pG, self.pDx, self.pDz, self.pDxz):
+        for pl in self.plans:
             pl.cache.store.clear()
             pl.cache.static = True
         self.pg = process_group
@@ -308,9 +355,9 @@ class AliStepper:
     def _planes(self, X, idx, cont, tables, out=None, mask=None):
         B = X.shape[0]
         H, W = self.family.hw
-        n_log = 1 + len(tables) + (0 if cont is None else cont.shape[1])
-        out = ops.assemble_planes(X.reshape(B, H, W), idx, [t.detach() for t in tables], cont, B, H, W,
-                                  (n_log + 3) // 4 * 4, out=out, mask=mask)
+        n_log, cpad = _plane_count(tables, cont)
+        out = ops.assemble_planes(X.reshape(B, H, W), idx, [t.detach() for t in tables], cont, B, H, W, cpad, out=out,
+                                  mask=mask)
         return out, n_log
 
     def _d_input_mask(self, B, device, cont):
@@ -320,8 +367,8 @@ class AliStepper:
         st = self.pDx.stages[0]
         if st.pattern != ["drop"]:
             return None
-        n_log = 1 + len(self.family.d_tables) + (0 if cont is None else cont.shape[1])
-        return _dropout.peek_mask(0, B, n_log, st.pre[0][1], device, (n_log + 3) // 4 * 4)
+        n_log, cpad = _plane_count(self.family.d_tables, cont)
+        return _dropout.peek_mask(0, B, n_log, st.pre[0][1], device, cpad)
 
     def _d_planes(self, X, idx, cont):
         """D's conv input for one pass: (x0, n_log, whether x0 already carries the first Dropout2d mask)"""
@@ -335,9 +382,9 @@ class AliStepper:
         B = Xa.shape[0]
         H, W = self.family.hw
         tables = self.family.d_tables
-        n_log = 1 + len(tables) + (0 if cont is None else cont.shape[1])
+        n_log, cpad = _plane_count(tables, cont)
         mask = self._d_input_mask(2 * B, Xa.device, cont)
-        buf = torch.empty(2 * B, H, W, (n_log + 3) // 4 * 4, dtype=torch.float32, device=Xa.device)
+        buf = torch.empty(2 * B, H, W, cpad, dtype=torch.float32, device=Xa.device)
         self._planes(Xa, idx, cont, tables, out=buf[:B], mask=None if mask is None else mask[:B])
         self._planes(Xb, idx, cont, tables, out=buf[B:], mask=None if mask is None else mask[B:])
         return buf, n_log, mask is not None
@@ -367,26 +414,22 @@ class AliStepper:
     def _eg_forward(self, images, idx, cont, onehots, zin, alloc_e=None, alloc_g=None):
         """E(x) and G(z) with their saved activations: independent chains, layer pairs share a launch"""
         fam = self.family
+        x0_shape = (images.shape[0],) + tuple(fam.hw) + _plane_count(fam.e_tables, cont)[1:]
         x0e, n_log = self._planes(images, idx, cont, fam.e_tables,
-                                  out=None if alloc_e is None else alloc_e("x0", (images.shape[0],) + tuple(fam.hw) + (
-                                      (1 + len(fam.e_tables) + (0 if cont is None else cont.shape[1]) + 3) // 4 * 4,)))
+                                  out=None if alloc_e is None else alloc_e("x0", x0_shape))
         gin, g_log = self._g_input(zin, onehots, cont, alloc_g)
         (ex, sE), (gz, sG) = run_parallel(chain_forward_gen(self.pE, x0e, True, n_log, True, alloc=alloc_e),
                                           chain_forward_gen(self.pG, gin, True, g_log, True, alloc=alloc_g))
         return ex, sE, gz, sG, n_log, g_log
 
-    @staticmethod
-    def _batch_key(images, z):
-        return (images.data_ptr(), tuple(images.shape), z.data_ptr(), tuple(z.shape))
-
-    def _prefetch(self, images, c, z):
+    def _prefetch(self, batch):
         """compute the E+G phase's forward passes for a batch ahead of its iteration, into persistent buffers"""
-        B = images.shape[0]
+        images, c, z = batch[:3]
         idx, cont, onehots = self.family.conditioning(c)
-        zin = z.reshape(B, -1).float().contiguous()
+        zin = z.reshape(images.shape[0], -1).float().contiguous()
         with ops.precision(self.precision):
             fwd = self._eg_forward(images, idx, cont, onehots, zin, self._arena_alloc("E"), self._arena_alloc("G"))
-        self._ahead = {"key": self._batch_key(images, z), "fwd": fwd}
+        self._ahead = {"key": batch.identity(), "fwd": fwd}
 
     def _join_begin(self, B, device):
         """(joint buffer [B, n_dx + nz], the Dropout2d mask of dxz's first stage) for a D forward that is about to
@@ -516,10 +559,10 @@ class AliStepper:
         return ops.normal_fill(self.latent_seed, torch.empty(B, self.z_dim, dtype=torch.float32, device=self.iter_t.device),
                                dev_counter=self.iter_t)
 
-    def _begin(self, images, c, z, do_eg=True, ahead=None, source=None, index=None):
-        cond = None
-        if source is not None:         # device pipeline: the batch is assembled from the resident data set ...
-            images, onehot, idx, cont = source.gather(index)
+    def _begin(self, batch, do_eg=True):
+        images, z, cond = batch.images, batch.z, None
+        if batch.source is not None:   # device pipeline: the batch is assembled from the resident data set ...
+            images, onehot, idx, cont = batch.source.gather(batch.index)
             cond = (idx, cont, [onehot])
         B = images.shape[0]
         if z is None:                  # ... and the latents are drawn here, keyed by the iteration counter
@@ -530,11 +573,11 @@ class AliStepper:
             self._fold.abandon()       # (nothing is pending after a completed iteration)
         _dropout.begin_iteration(self.iter_t, owner=self, tag=(B, bool(do_eg)))
         _chain.defer_batch_counts()
-        idx, cont, onehots = cond if cond is not None else self.family.conditioning(c)
+        idx, cont, onehots = cond if cond is not None else self.family.conditioning(batch.c)
         cx = {"images": images, "B": B, "idx": idx, "cont": cont, "onehots": onehots,
               "zin": z.reshape(B, -1).float().contiguous(), "out": {}}
         if self._pipelined(do_eg):     # the E(x) / G(z) forward computed ahead (_ensure_ahead), the next batch
-            cx["eg_fwd"], cx["ahead"], self._ahead = self._ahead["fwd"], ahead, None
+            cx["eg_fwd"], cx["ahead"], self._ahead = self._ahead["fwd"], batch.ahead, None
         return cx
 
     def _eg_grads(self, cx):
@@ -621,20 +664,21 @@ class AliStepper:
     # The two D phases are cut where their first dependence on the previous optimiser step sits, so that the
     # data-parallel all-reduce of that step's gradients overlaps with the part in front of the cut:
     # D.dx(x) needs neither E' nor a new D; G'(z) needs G' (already stepped) but not the D update in flight.
+    def _d_real_input(self, cx):
+        """D's conv input for the real batch, kept in ``cx`` for _d_real_rest: (x0d, n_log, first mask applied)"""
+        cx["x0d"], cx["n_log"], masked = self._d_planes(cx["images"], cx["idx"], cx["cont"])
+        return cx["x0d"], cx["n_log"], masked
+
     def _d_real_pre(self, cx):
         """D.dx on the real batch: independent of the E+G update whose gradients may still be in the all-reduce."""
-        fam, images, idx, cont = self.family, cx["images"], cx["idx"], cx["cont"]
-        x0d, n_log, masked = self._d_planes(images, idx, cont)
-        cx["x0d"], cx["n_log"] = x0d, n_log
+        x0d, n_log, masked = self._d_real_input(cx)
         cx["dx_pre"] = self._dx_forward(x0d, n_log, True, x_masked=masked)
 
     def _d_real_all(self, cx):
         """The whole D-real phase on one GPU: nothing has to hide an all-reduce, so E'(x) and D.dx(x) -- independent
         chains -- run side by side (chain.run_parallel) instead of one in front of the E+G optimiser step."""
-        fam, images, idx, cont = self.family, cx["images"], cx["idx"], cx["cont"]
-        x0d, n_log, masked = self._d_planes(images, idx, cont)
-        cx["x0d"], cx["n_log"] = x0d, n_log
-        x0e, _ = self._planes(images, idx, cont, fam.e_tables)
+        x0d, n_log, masked = self._d_real_input(cx)
+        x0e, _ = self._planes(cx["images"], cx["idx"], cx["cont"], self.family.e_tables)
         cx["dx_pre"], (cx["ex_pre"], _) = run_parallel(self._dx_forward_gen(x0d, n_log, True, x_masked=masked),
                                                        chain_forward_gen(self.pE, x0e, True, n_log, False))
         self._d_real_rest(cx)
@@ -711,16 +755,16 @@ class AliStepper:
         if ahead and self._pipelined(do_eg):
             # the NEXT iteration's E(x) / G(z) forward passes run under the all-reduce that was just issued: they need
             # neither it nor the D update behind it (pipeline_reduce)
-            segs.append((lambda cx: self._prefetch(*cx["ahead"]), None, False))
+            segs.append((lambda cx: self._prefetch(cx["ahead"]), None, False))
         segs.append((lambda cx: (self._apply_d(), self._phase_scores(cx, average_bn=False)), None, True))
         return segs
 
-    def _ensure_ahead(self, images, c, z, graphed=False):
+    def _ensure_ahead(self, batch, graphed=False):
         """pipeline_reduce: compute this batch's E(x) / G(z) forward now unless the previous ``step``'s tail computed it
         ahead -- eagerly (its tensors at hand) or, ``graphed``, by a replayed segment into the buffers the graphs name"""
         a = self._ahead
-        if a is None or a["key"] != self._batch_key(images, z) or (a["fwd"] is None and not graphed):
-            self._prefetch(images, c, z)
+        if a is None or a["key"] != batch.identity() or (a["fwd"] is None and not graphed):
+            self._prefetch(batch)
 
     def _run_segments(self, cx, steps, reduce):
         """Walk a (step, group, wait) list like ``_segments``'s: a step with ``wait`` first waits for the all-reduce in
@@ -736,11 +780,11 @@ class AliStepper:
         if self.dist:
             dp.average_buffers_(self.bn_buffers, self.pg)
 
-    def _iteration(self, images, c, z, do_eg=True, ahead=None, source=None, index=None):
+    def _iteration(self, batch, do_eg=True):
         if self._pipelined(do_eg):
-            self._ensure_ahead(images, c, z)    # (in front of _begin: it runs its own attribute plumbing)
-        cx = self._begin(images, c, z, do_eg, ahead, source, index)
-        self._run_segments(cx, self._segments(do_eg, ahead is not None), dp.allreduce_sum_async_)
+            self._ensure_ahead(batch)           # (in front of _begin: it runs its own attribute plumbing)
+        cx = self._begin(batch, do_eg)
+        self._run_segments(cx, self._segments(do_eg, batch.ahead is not None), dp.allreduce_sum_async_)
         return cx["out"]
 
     def _state_tensors(self):
@@ -758,8 +802,14 @@ class AliStepper:
         for t, v in zip(self._state_tensors(), vals):
             t.copy_(v)
         self.opt_eg.steps, self.opt_d.steps = se, sd
+        self._weights_changed()
+
+    def _weights_changed(self):
+        """The parameters were rewritten behind the Adam launches' back (_restore, load_state, load_state_dict): re-round
+        the fp16 twins, re-pack every plan's kernel-layout copies.  The forward computed ahead (``self._ahead``) is NOT
+        dropped here yet (ADVICE.md finding 1): that fix brings a test of its own, and this is the one place it goes."""
         self.opt_eg.sync16(), self.opt_d.sync16()
-        for pl in (self.pE, self.pG, self.pDx, self.pDz, self.pDxz):
+        for pl in self.plans:
             pl.cache.refresh()
 
     def load_state(self, E_src, G_src, D_src, opt_e=None, opt_d=None):
@@ -786,9 +836,7 @@ class AliStepper:
                     vv.zero_()
             group.steps = step
             group.step_t.fill_(step)
-        self.opt_eg.sync16(), self.opt_d.sync16()
-        for pl in (self.pE, self.pG, self.pDx, self.pDz, self.pDxz):
-            pl.cache.refresh()
+        self._weights_changed()
 
     # ------------------------------------------------------------------ checkpoints
     def state_dict(self):
@@ -826,7 +874,6 @@ class AliStepper:
                     g.steps = int(o["step"])
                 g.step_t.fill_(g.steps)
             self.iter_t.fill_(int(sd.get("iteration", 0)))
-            self.opt_eg.sync16(), self.opt_d.sync16()
             if "dropout_seed" in sd and int(sd["dropout_seed"]) != _dropout._state["seed"]:
                 # the seed is a launch argument of the mask kernel: graphs captured with the old one must go
                 _dropout._state["seed"] = int(sd["dropout_seed"])
@@ -837,8 +884,7 @@ class AliStepper:
                     self.z_seed = int(sd["z_seed"])     # a launch argument of the draw, like the dropout seed
                     self._graph.clear()
                 self._z_used = True
-            for pl in (self.pE, self.pG, self.pDx, self.pDz, self.pDxz):
-                pl.cache.refresh()
+            self._weights_changed()
 
     def _refresh_d(self):
         with ops.batched_packs():
@@ -857,7 +903,7 @@ class AliStepper:
             self._device_pipeline_ok(ahead)
             self._z_used = True
         try:
-            return self._step(images, c, z, do_eg, masks, ahead)
+            return self._step(_Batch.host(images, c, z, ahead), do_eg, masks)
         finally:
             _chain.abort_batch_counts()     # no-op after a completed iteration
 
@@ -876,7 +922,7 @@ class AliStepper:
             raise ValueError("step_indexed: index must be a non-empty 1-d int64 CUDA tensor")
         self._z_used = True
         try:
-            return self._step(None, None, None, do_eg, None, None, source, index.contiguous())
+            return self._step(_Batch.indexed(source, index.contiguous()), do_eg, None)
         finally:
             _chain.abort_batch_counts()
 
@@ -885,62 +931,51 @@ class AliStepper:
             raise ValueError("the device input pipeline (z=None / step_indexed) cannot be combined with "
                              "pipeline_reduce / ahead=: the batch computed ahead is named by its host-made tensors")
 
-    def _step(self, images, c, z, do_eg, masks, ahead=None, source=None, index=None):
+    def _step(self, batch, do_eg, masks):
         with ops.precision(self.precision):
-            return self._step_impl(images, c, z, do_eg, masks, ahead, source, index)
+            if not self._pipelined(do_eg):
+                batch = batch._replace(ahead=None)
+            if masks is not None:
+                with _dropout.injected_masks(masks):
+                    return self._iteration(batch, do_eg)
+            if not self.capture:
+                return self._iteration(batch, do_eg)
+            try:
+                return self._replay(batch, do_eg)
+            except RuntimeError as e:  # graph capture refused (driver / RCCL combination): keep training, eagerly
+                if self._graph or not any(w in str(e).lower() for w in ("captur", "graph")):
+                    raise              # a failure of a graph that already ran, or an error that is not about capture
+                import warnings
+                warnings.warn(f"AliStepper: HIP graph capture failed ({e!r}); continuing with eager launches")
+                self.capture = False
+                if self._capture_snapshot is not None:
+                    self._restore(self._capture_snapshot)
+                return self._iteration(batch._replace(ahead=None), do_eg)
 
-    def _step_impl(self, images, c, z, do_eg, masks, ahead=None, source=None, index=None):
-        if not self._pipelined(do_eg):
-            ahead = None
-        if masks is not None:
-            with _dropout.injected_masks(masks):
-                return self._iteration(images, c, z, do_eg, ahead, source, index)
-        if not self.capture:
-            return self._iteration(images, c, z, do_eg, ahead, source, index)
-        try:
-            return self._replay(images, c, z, do_eg, ahead, source, index)
-        except RuntimeError as e:  # graph capture refused (driver / RCCL combination): keep training, eagerly
-            if self._graph or not any(w in str(e).lower() for w in ("captur", "graph")):
-                raise              # a failure of a graph that already ran, or an error that is not about capture
-            import warnings
-            warnings.warn(f"AliStepper: HIP graph capture failed ({e!r}); continuing with eager launches")
-            self.capture = False
-            if self._capture_snapshot is not None:
-                self._restore(self._capture_snapshot)
-            return self._iteration(images, c, z, do_eg, None, source, index)
-
-    def _replay(self, images, c, z, do_eg, ahead=None, source=None, index=None):
+    def _replay(self, batch, do_eg):
         """The iteration from HIP graphs.  One GPU: one graph over _begin and every segment (the launch sequence of
         _iteration).  Data parallel (or ``segmented``): one graph per segment, the gradient all-reduces in between
-        launched eagerly.  The tensors a replay loads into the graphs' buffers: (images, c, z, next batch); without
-        the host-made ``z`` when it is drawn inside; the index slice alone for ``step_indexed``."""
+        launched eagerly.  A replay loads ``batch.tensors()`` into the graphs' static copies of them."""
         split, pipe = self.dist or self.segmented, self._pipelined(do_eg)
-        key = ("seg" if split else "one", tuple(images.shape) if source is None else (source.key, index.numel()), do_eg,
-               pipe, ahead is not None) + (() if z is not None else ("z" if source is None else "indexed",))
-        loaded = (index,) if source is not None else (images, c) + (() if z is None else (z,)) + tuple(ahead or ())
-
-        def unpack(ins):                        # -> the arguments of _iteration / _begin behind do_eg
-            if source is not None:
-                return None, None, None, None, source, ins[0]
-            im, cc, *rest = ins
-            return im, cc, (None if z is None else rest.pop(0)), tuple(rest) or None, None, None
+        where, *rest = batch.graph_key()
+        key = ("seg" if split else "one", where, do_eg, pipe, *rest)
         if key not in self._graph:
             snap = self._capture_snapshot = self._snapshot()
 
             def warm(*ins):                     # (collectives included: all ranks do this)
-                im, cc, zz, nxt, src, ix = unpack(ins)
-                self._iteration(im, cc, zz, do_eg, nxt, src, ix)
+                b = batch.rebind(ins)
+                self._iteration(b, do_eg)
                 if pipe and self._ahead is None:
-                    self._prefetch(im, cc, zz)  # the persistent buffers the capture will name
-            ent = _Graphed(loaded, warm, lambda: self._restore(snap))
-            ent.source = source                 # (the graphs name its buffers)
-            im, cc, zz, nxt, src, ix = unpack(ent.inputs)
-            segs = self._segments(do_eg, bool(nxt))
+                    self._prefetch(b)           # the persistent buffers the capture will name
+            ent = _Graphed(batch.tensors(), warm, lambda: self._restore(snap))
+            ent.source = batch.source           # (the graphs name its buffers)
+            static = batch.rebind(ent.inputs)
+            segs = self._segments(do_eg, static.ahead is not None)
             if not split:                       # one graph: the launch sequence of _iteration
                 segs = [(lambda cx, ws=[w for w, _, _ in segs]: [w(cx) for w in ws], None, False)]
 
             def first(cx, w0=segs[0][0]):       # the first graph also starts the iteration
-                cx.update(self._begin(im, cc, zz, do_eg, nxt, src, ix))
+                cx.update(self._begin(static, do_eg))
                 w0(cx)
             segs[0], cx = (first,) + segs[0][1:], {}
             self._run_segments(cx, [(lambda cx, w=w: ent.capture(w, cx), g, wt) for w, g, wt in segs], _allreduce_now)
@@ -950,13 +985,13 @@ class AliStepper:
             ent.out = cx["out"]
             self._graph[key] = ent, [(lambda cx, g=g: g.replay(), gr, wt) for g, (_, gr, wt) in zip(ent.graphs, segs)]
         ent, steps = self._graph[key]
-        ent.load(loaded)
+        ent.load(batch.tensors())
         if pipe:
-            self._ensure_ahead(images, c, z, graphed=True)
+            self._ensure_ahead(batch, graphed=True)
         self._ahead = None
         self._run_segments(None, steps, dp.allreduce_sum_async_)
-        if pipe and ahead is not None:          # the replayed prefetch segment left the next batch's forward in the buffers
-            self._ahead = {"key": self._batch_key(ahead[0], ahead[2]), "fwd": None}
+        if pipe and batch.ahead is not None:    # the replayed prefetch segment left the next batch's forward in the buffers
+            self._ahead = {"key": batch.ahead.identity(), "fwd": None}
         return ent.out
 
 
@@ -1027,9 +1062,9 @@ class FinetuneStepper:
         H, W = fam.hw
         pairwise = x.dim() == 3 and B > 1          # [B,H,W] - [B,1,H,W] broadcasts to [B,B,H,W] (whale script)
         idx, cont, onehots = fam.conditioning(a)
-        n_log = 1 + len(fam.e_tables) + (0 if cont is None else cont.shape[1])
+        n_log, cpad = _plane_count(fam.e_tables, cont)
         x0 = ops.assemble_planes(x.reshape(B, H, W).float().contiguous(), idx, [t.detach() for t in fam.e_tables],
-                                 cont, B, H, W, (n_log + 3) // 4 * 4)
+                                 cont, B, H, W, cpad)
         codes, sE = chain_forward(self.pE, x0, self.E.training, n_log, True)
         zin = codes.reshape(B, -1)
         gin, g_log = _g_input(fam, zin, onehots, cont)

@@ -280,7 +280,7 @@ def test_fp16_mfma_stepper_iteration_vs_fp32_oracle(family, d, B, scale, bench_t
     scores within the north_star's 1e-3, reconstructions G(E(x)) within 1e-3 relative, and the Adam step of every
     parameter (sign-like: +-lr) equal except where the gradient is at fp16-rounding level."""
     from ali_hip import ops
-    from ali_hip.step import AliStepper
+    from ali_hip.step import AliStepper, _Batch
     (Eo, Go, Do), (E, G, D), images, c, z = paired_models(family, d=d, B=B)
     for m in (Eo, Go, Do, E, G, D):
         m.train()
@@ -323,7 +323,7 @@ def test_fp16_mfma_stepper_iteration_vs_fp32_oracle(family, d, B, scale, bench_t
     sd_eg = [copy.deepcopy(m.state_dict()) for m in (Eo, Go, Do)]
     with torch.no_grad(), ops.precision("f16"):
         stepper.load_state(Eo, Go, Do, oe, od)
-        cx = stepper._begin(images.cuda(), to_dev(c), z.cuda())
+        cx = stepper._begin(_Batch.host(images.cuda(), to_dev(c), z.cuda()))
         w0 = weights((Eo, Go))
         stepper._phase_eg(cx)
     g_eg_hip = stepper.opt_eg.grad_logical().double().cpu() / stepper.loss_scale

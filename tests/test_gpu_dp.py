@@ -102,6 +102,8 @@ class _DropoutState:
 
 def _emulate(world, iters):
     """Single-process gradient-accumulation emulation of the ``world``-rank run (eager launches)."""
+    _paths()
+    from ali_hip.step import _Batch
     reps = []
     for r in range(world):
         st, D, data = _replica(r, None, False)
@@ -114,7 +116,7 @@ def _emulate(world, iters):
             cxs = []
             for st, D, (images, c, z), ds in reps:
                 with ds:
-                    cxs.append(st._begin(images, c, z, True))
+                    cxs.append(st._begin(_Batch.host(images, c, z), True))
             n_seg = len(reps[0][0]._segments(True))
             for i in range(n_seg):
                 group_attr = None
@@ -158,3 +160,43 @@ def test_stepper_two_ranks_own_shards_vs_emulation(tmp_path, capture, pipeline):
     assert digests[0] == digests[1]
     assert outs[0] == r0["out"] and outs[1] == r1["out"], (outs, r0["out"], r1["out"])
     assert digests[0] == r0["digest"], "2-rank data-parallel run != single-process gradient-accumulation emulation"
+
+
+def _distinct_batches(n):
+    """``n`` different BS-row batches (images, c, z) of one synthetic set, on the device"""
+    _paths()
+    import ali_oracle as orc
+    x, a = orc.synth_morphomnist(n * BS, seed=1)
+    stats = {k: (v.min(dim=0).values, v.max(dim=0).values) for k, v in a.items() if k != "digit"}
+    out = []
+    for i in range(n):
+        lo = i * BS
+        images, c = orc.mnist_scale_batch(x[lo:lo + BS], {k: v[lo:lo + BS] for k, v in a.items()}, stats)
+        z = torch.randn(BS, 512, 1, 1, generator=torch.Generator().manual_seed(3 + i))
+        out.append((images.cuda(), {k: v.cuda() for k, v in c.items()}, z.cuda()))
+    return out
+
+
+@pytest.mark.parametrize("capture", [False, True])
+def test_pipelined_schedule_distinct_batches(capture):
+    """pipeline_reduce over three DIFFERENT batches on one process (no group; ``segmented`` forces the data-parallel
+    schedule): an announced batch, an unannounced tail, a batch that arrives unannounced (eager ``_prefetch`` in front
+    of the iteration -- with ``capture`` in front of a replay) while announcing the next, and a final unannounced step.
+    Losses, scores, weights, Adam moments and D's buffers equal the plain segmented schedule's after every step, bit
+    for bit."""
+    plain, D1, _ = _replica(0, None, False)
+    plain.segmented = True
+    piped, D2, _ = _replica(0, None, capture, pipeline=True)
+    piped.segmented = True
+    b0, b1, b2 = _distinct_batches(3)       # (kept alive: an announced batch is recognised by its tensors' addresses)
+    for i, (batch, ahead) in enumerate(((b0, b1), (b1, None), (b2, b0), (b0, None))):
+        r1 = {k: v.item() for k, v in plain.step(*batch).items()}
+        r2 = {k: v.item() for k, v in piped.step(*batch, ahead=ahead).items()}
+        assert r1 == r2, (i, r1, r2)
+        for name in ("opt_eg.flat", "opt_d.flat", "opt_eg.m", "opt_d.v"):
+            group, buf = name.split(".")
+            assert torch.equal(getattr(getattr(plain, group), buf), getattr(getattr(piped, group), buf)), (i, name)
+        for (k, v1), (_, v2) in zip(D1.named_buffers(), D2.named_buffers()):
+            assert torch.equal(v1, v2), (i, k)
+    if capture:
+        assert len(piped._graph) == 2 and all(k[0] == "seg" for k in piped._graph)

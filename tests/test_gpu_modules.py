@@ -374,8 +374,9 @@ def test_hand_scheduled_stepper_vs_oracle(rescale, bs):
             g_eg = _flat_grads((Eo, Go))
             oe.step()
         from ali_hip import dropout as _dropout
+        from ali_hip.step import _Batch
         with _dropout.injected_masks(tape.masks), torch.no_grad():
-            cx = stepper._begin(images.cuda(), to_dev(c), z.cuda())
+            cx = stepper._begin(_Batch.host(images.cuda(), to_dev(c), z.cuda()))
             stepper._phase_eg(cx)
         assert abs(cx["out"]["loss_eg"].item() - l_eg.item()) <= 1e-5 * max(1, abs(l_eg.item()))
         assert _rel(stepper.opt_eg.grad_logical().double().cpu(), g_eg) <= 2e-3, (i, "EG grads")
