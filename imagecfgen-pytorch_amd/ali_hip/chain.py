@@ -3,7 +3,8 @@
 A stack (``Encoder.layers``, ``Generator.layers``, ``Discriminator.dx/dz/dxz``;
 reference image_scms/mnist.py:30-40,63-74,98-136) is parsed once into *stages*
 
-    [Dropout2d] [BatchNorm2d] [Dropout2d]  ->  Conv2d | ConvTranspose2d | Linear(+Unflatten)  ->  LeakyReLU | Tanh
+    [Dropout2d] [BatchNorm2d] [Dropout2d]  ->  Conv2d | ConvTranspose2d | Linear(+Unflatten) | Flatten+Linear
+                                           ->  LeakyReLU | Tanh
 
 and executed as ONE autograd node: forward runs the NHWC kernels stage by stage,
 backward is hand scheduled -- the activation derivative of stage i-1 (and the
@@ -32,11 +33,12 @@ def _pad4(c: int) -> int:
 class Stage:
     """One convolution (or Linear) of the stack with what sits in front of it (``pre``: ("drop", p) / ("bn", module)
     in module order; ``pattern``: their kinds) and the activation behind it."""
-    __slots__ = ("kind", "mod", "act", "slope", "pre", "pattern", "has_drop", "drop_p", "bn", "unflat", "index")
+    __slots__ = ("kind", "mod", "act", "slope", "pre", "pattern", "has_drop", "drop_p", "bn", "unflat", "index", "hw")
 
     def __init__(self, kind, mod, pre, index):
         self.kind, self.mod, self.pre, self.index = kind, mod, pre, index
         self.act, self.slope, self.unflat = ACT_NONE, 0.0, None
+        self.hw = None       # kind "flat": the map the Flatten sees, known at the first forward (``resolve_flat``)
         self.pattern = [k for k, _ in pre]
         self.has_drop = "drop" in self.pattern
         self.drop_p = next((a for k, a in pre if k == "drop"), None)
@@ -88,16 +90,26 @@ class ChainPlan:
         pre = []
         mods = list(seq)
         i = 0
+        flat = False          # an nn.Flatten() was seen: the Linear behind it is a "flat" stage
         while i < len(mods):
             m = mods[i]
             name = m.__class__.__name__
+            if flat and not isinstance(m, nn.Linear):
+                raise NotImplementedError("ali_hip.chain: unsupported layer Flatten (only in front of a Linear)")
             if isinstance(m, nn.Dropout2d) or name in ("Dropout2d", "TapedDropout2d"):
                 pre.append(("drop", float(m.p)))
             elif isinstance(m, nn.BatchNorm2d):
                 pre.append(("bn", m))
+            elif isinstance(m, nn.Flatten):
+                # Flatten -> Linear(C*h*w, O) on an NHWC [B,h,w,C] map: an unpadded stride-1 Conv2d(C, O, (h, w)) whose
+                # weight is the Linear's [O, C*h*w] storage viewed as [O, C, h, w] (classifiers/mnist.py:21-22)
+                if (m.start_dim, m.end_dim) != (1, -1):
+                    raise NotImplementedError("ali_hip.chain: unsupported layer Flatten (start_dim / end_dim not 1 / -1)")
+                flat = True
             elif isinstance(m, (nn.Conv2d, nn.ConvTranspose2d, nn.Linear)):
                 kind = "convT" if isinstance(m, nn.ConvTranspose2d) else ("conv" if isinstance(m, nn.Conv2d)
-                                                                          else "linear")
+                                                                          else "flat" if flat else "linear")
+                flat = False
                 st = Stage(kind, m, pre, len(self.stages))
                 pre = []
                 if kind == "linear" and i + 1 < len(mods) and isinstance(mods[i + 1], nn.Unflatten):
@@ -113,6 +125,8 @@ class ChainPlan:
             else:
                 raise NotImplementedError(f"ali_hip.chain: unsupported layer {name}")
             i += 1
+        if flat:
+            raise NotImplementedError("ali_hip.chain: unsupported layer Flatten (no Linear behind it)")
         if pre:
             raise NotImplementedError("trailing Dropout2d/BatchNorm2d without a convolution")
         for st in self.stages:
@@ -140,6 +154,7 @@ class ChainPlan:
         ('scatter_dgrad', planes): the 1x1 GEMM weights of the scatter-form transposed convolutions (ali_col2im)."""
         w = st.mod.weight
         dev = w.device
+        hw = st.hw
 
         def build(dst=None):
             def buf(*shape, zero=False):
@@ -162,6 +177,14 @@ class ChainPlan:
                 sel = torch.stack([w.detach()[:, c] for c in which[1]], dim=0)          # [NP][K][R][S], slices only
                 out = buf(R * S * len(which[1]), 1, K)
                 out[:, 0, :].copy_(sel.permute(2, 3, 0, 1).reshape(R * S * len(which[1]), K))
+                return out
+            if st.kind == "flat":             # the Linear's [O][C*h*w] storage read as a Conv2d weight [O][C][h][w]
+                O, T = w.shape[0], hw[0] * hw[1]
+                C = w.shape[1] // T
+                if which == "fwd":            # [O][T][Cpad]
+                    return ops.pack_weights(w.detach(), buf(O, T, cin_stride), O, T, C, cin_stride, C * T, 1, T)
+                out = buf(cin_stride, T, O, zero=True)             # [Cpad][T][O]; rows >= C stay zero
+                ops.pack_weights(w.detach(), out, C, T, O, O, T, 1, C * T)
                 return out
             if w.dim() == 4:
                 src = _storage_view(w)     # (weights may live in the forward pack's order already: FlatGroup.layouts)
@@ -205,7 +228,7 @@ class ChainPlan:
             if ops._PRECISION["f16"]:
                 alias._ali16 = twin.view(n_out, w.shape[2] * w.shape[3], cin_stride)
             return alias
-        val = self.cache.get((st.index, which, cin_stride), w, build)
+        val = self.cache.get((st.index, which, cin_stride) + ((hw,) if st.kind == "flat" else ()), w, build)
         if ops._PRECISION["f16"] and which in ("fwd", "dgrad"):
             with torch.no_grad():
                 ops.ensure_shadow16(val)         # fp16 twin of the packed weights, re-rounded whenever they are re-packed
@@ -241,7 +264,33 @@ def _out_shape(st: Stage, B, H, W, C):
     if st.unflat:
         Cc, hh, ww = st.unflat
         return B, hh, ww, Cc
-    return B, 1, 1, m.out_features
+    return B, 1, 1, m.out_features       # Linear, and Flatten + Linear: the whole map is the kernel
+
+
+def resolve_flat(st: Stage, in_shape, c_log: int):
+    """A "flat" stage meets its input map [B,h,w,Cp] with ``c_log`` real channels: fixes ``st.hw`` (it decides the
+    weight view and the packs) or raises when the Linear was built for another map."""
+    _, H, W, _ = in_shape
+    if st.mod.in_features != c_log * H * W:
+        raise ValueError(f"ali_hip.chain: Flatten + Linear(in_features={st.mod.in_features}) on a {c_log} x {H} x {W} "
+                         f"map ({c_log * H * W} features)")
+    if H * W > 28:
+        raise NotImplementedError(f"ali_hip.chain: Flatten of a {H} x {W} map (the conv kernels take at most 28 taps)")
+    st.hw = (H, W)
+
+
+def trace(plan: "ChainPlan", in_shape, c_log: int):
+    """[(input shape, output shape, Route)] of every stage for an NHWC input ``in_shape`` with ``c_log`` real channels
+    (no tensors, no device: what ``chain_forward_gen`` will decide)."""
+    out = []
+    cur = tuple(in_shape)
+    for st in plan.stages:
+        if st.kind == "flat":
+            resolve_flat(st, cur, c_log)
+        nxt = _out_shape(st, *cur)
+        out.append((cur, nxt, route(st, cur, c_log)))
+        cur, c_log = nxt, nxt[3]
+    return out
 
 
 def _geom(st: Stage, xin_shape, out_shape):
@@ -253,6 +302,8 @@ def _geom(st: Stage, xin_shape, out_shape):
         return ops.geom(B, H, W, C, P, Q, K, m.kernel_size[0], m.kernel_size[1], m.stride[0], m.padding[0])
     if st.kind == "convT":   # x := convT output, y := convT input
         return ops.geom(B, P, Q, K, H, W, C, m.kernel_size[0], m.kernel_size[1], m.stride[0], m.padding[0])
+    if st.kind == "flat":    # the (H, W) kernel covers the map once
+        return ops.geom(B, H, W, C, 1, 1, K, H, W, 1, 0)
     # linear: 1x1 conv on the [B,1,1,I] map with O output channels
     return ops.geom(B, 1, 1, C, 1, 1, P * Q * K, 1, 1, 1, 0)
 
@@ -263,7 +314,8 @@ class Route(namedtuple("Route", "fwd wgrad wgrad_fold dgrad planes fold_ok bn_le
     a FoldQueue, strided or non-contiguous operands, the workspace size) stays at the call, once per fact.
 
     fwd         "head" (GEMV) | "tconv1" (direct one-channel kernel) | "scatter" (scatter form, one launch) |
-                "scatter_gemm" (1x1 GEMM + col2im) | "convT" | "conv" (implicit GEMMs; a Linear is a 1x1 "conv").  Only
+                "scatter_gemm" (1x1 GEMM + col2im) | "convT" | "conv" (implicit GEMMs; a Linear is a 1x1 "conv", a
+                Flatten + Linear an (h, w) "conv" on all three passes).  Only
                 the GEMMs have an epilogue: a "head" / "scatter*" stage that has to fold the next stage's mask or leave
                 BatchNorm partials runs the GEMM of its kind instead.
     wgrad       (weight-gradient path, bias-gradient path): "head" | "first_direct" (ali_tconv1_wgrad over the <= 8
@@ -284,7 +336,8 @@ class Route(namedtuple("Route", "fwd wgrad wgrad_fold dgrad planes fold_ok bn_le
 def route(st: Stage, in_shape, c_log: int) -> Route:
     """The stage's Route for an input [B,H,W,Cp] = ``in_shape`` with ``c_log`` real channels (B does not matter)."""
     m, Cp = st.mod, in_shape[3]
-    taps = m.kernel_size[0] * m.kernel_size[1] if st.kind != "linear" else 1
+    taps = (1 if st.kind == "linear" else in_shape[1] * in_shape[2] if st.kind == "flat"
+            else m.kernel_size[0] * m.kernel_size[1])
     # ConvTranspose2d(C -> 1), stride 1, no output padding: served by the direct one-channel kernels
     tconv1 = (st.kind == "convT" and m.out_channels == 1 and m.stride[0] == 1 and m.output_padding[0] == 0
               and m.kernel_size[0] <= 5 and Cp in (32, 64, 128, 256))
@@ -604,6 +657,8 @@ def chain_forward_gen(plan: ChainPlan, x: torch.Tensor, training: bool, c_log_in
         nxt = plan.stages[si + 1] if si + 1 < len(plan.stages) else None
         sv = _Saved()
         sv.x_in, sv.bn, sv.pattern, sv.training, sv.c_log = cur, st.bn, st.pattern, training, c_log
+        if st.kind == "flat":
+            resolve_flat(st, (B, H, W, Cp), c_log)
         sv.in_shape, sv.out_shape = (B, H, W, Cp), _out_shape(st, B, H, W, Cp)
         sv.geom, sv.route = _geom(st, sv.in_shape, sv.out_shape), route(st, sv.in_shape, c_log)
         sv.mask = folded if folded is not None else early
@@ -659,6 +714,9 @@ def _param_grads(st: Stage, sv, g_pre, ld: int, grads, grad_dst, fold):
     elif db_path == "colsum":
         grads[id(m.bias)] = ops.colsum(B * P * Q, K, K, g_pre, out=grad_dst.get(id(m.bias)))
     dw = grads[id(m.weight)] = grad_dst[id(m.weight)] if id(m.weight) in grad_dst else torch.empty_like(m.weight)
+    if st.kind == "flat":                 # written in the view's layout [O][C][h][w] = the Linear's own [O][C*h*w]
+        ops.conv_bwd_weight(g, sv.t, g_pre, dw, c_in, K, dw.stride(0), H * W, 1, db=fused_db, dy_ld=ld, defer=fold)
+        return
     R, S = m.kernel_size if st.kind != "linear" else (1, 1)
     if path == "convT_scatter" and sv.t.is_contiguous() and g_pre.is_contiguous() and dw.stride(2) == S * dw.stride(3):
         # one-channel tail (stride 2): pixel-contraction kernel instead of a GEMM with one gathered channel

@@ -1123,6 +1123,29 @@ def bce_logits_pair(logit, B, target_a, target_b, gscale=1.0, want_grad=True):
     return out3, gl
 
 
+def softmax_xent(logit, target, gscale=1.0, want_grad=True, want_pred=False, hits_accum=None):
+    """Cross-entropy of [B, C] logits against probability rows, gradient, arg-max and hit count in one launch
+    (include/ali_hip.h: ali_softmax_xent).  Returns (out2 = [mean loss, hits] device tensor, glogit or None,
+    pred int32 [B] or None); ``hits_accum`` (one-element int64 device tensor) += hits on the device."""
+    lib = _lib.load()
+    if logit.dim() != 2 or target.shape != logit.shape:
+        raise ValueError(f"softmax_xent: need [B, C] logits and targets of one shape, got {tuple(logit.shape)} and "
+                         f"{tuple(target.shape)}")
+    B, C = logit.shape
+    if hits_accum is not None and not (hits_accum.is_cuda and hits_accum.dtype == torch.int64
+                                       and hits_accum.numel() == 1):
+        raise ValueError("softmax_xent: hits_accum must be a one-element int64 CUDA tensor")
+    out2 = torch.empty(2, dtype=torch.float32, device=logit.device)
+    gl = torch.empty_like(logit) if want_grad else None
+    pred = torch.empty(B, dtype=torch.int32, device=logit.device) if want_pred else None
+    ws = workspace(logit.device)
+    _lib.check(lib.ali_softmax_xent(_chk(logit, "logit"), _chk(target, "target"), B, C, float(gscale), _chk(out2),
+                                    _opt(gl), None if pred is None else c_void_p(pred.data_ptr()),
+                                    None if hits_accum is None else c_void_p(hits_accum.data_ptr()),
+                                    c_void_p(ws.data_ptr()), ws.numel(), _stream()), "ali_softmax_xent")
+    return out2, gl, pred
+
+
 def _attr_arrays(tensors):
     """ctypes views of a list of [B, n] one-hot tensors (fp32 or int32, contiguous CUDA)."""
     n = len(tensors)

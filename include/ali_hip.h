@@ -341,6 +341,21 @@ int ali_bn_bwd_from_partials(const float* part, int32_t slots, const float* x, c
 int ali_bce_logits(const float* logit, int32_t B, float target, float gscale, float* out2, float* glogit,
                    ali_stream_t stream);
 
+/* nn.CrossEntropyLoss() (mean) against probability targets, its gradient, the arg-max prediction and the hit count of
+ * the classifier loops (classifiers/mnist.py:48-56, audiomnist_generator_score.py:90-98) in one launch; csrc/xent.hip.
+ * logit, target: contiguous [B][C] fp32, 1 <= C <= 4096 (ALI_ERR_BAD_ARG before any launch otherwise).  Per row b, with
+ * lse_b the max-shifted logsumexp (no overflow for |logit| <= 1e4):
+ *   loss_b = -sum_j t_bj (z_bj - lse_b);   out2[0] = mean_b loss_b;
+ *   glogit[b][j] = gscale * (softmax_bj * sum_k t_bk - t_bj) / B     (soft targets need not sum to 1);   NULL: skipped
+ *   pred[b] = first maximum of the logit row (torch.argmax);   NULL: skipped
+ *   out2[1] = number of rows whose pred equals the first maximum of the target row, as a float;
+ *   *hits_accum += that number (device int64; NULL: skipped) -- a scoring loop needs no host read per batch.
+ * ws: >= ALI_WS_RESERVED + 16 * min(ceil(B / 4), 1024) bytes; the arrival counter is the last int of the reserved head
+ * and is left at zero.  No float atomics: bit-identical from run to run.  A NaN logit never becomes the prediction
+ * (torch.argmax would pick it) and makes its row's loss and gradient, hence out2[0], NaN. */
+int ali_softmax_xent(const float* logit, const float* target, int32_t B, int32_t C, float gscale, float* out2,
+                     float* glogit, int32_t* pred, int64_t* hits_accum, void* ws, size_t ws_bytes, ali_stream_t stream);
+
 /* torch.optim.Adam step (mnist.py:176-179,230,236,241), no amsgrad / decay.
  * One launch over a flat parameter segment.  The 1-based step count is `step`, or *dev_step when
  * dev_step != NULL (graph replays); the gradient is read as grad_scale * g (1/world for DP).
