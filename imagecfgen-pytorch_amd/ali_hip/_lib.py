@@ -100,6 +100,14 @@ SIGNATURES = {
     "ali_bce_logits": (c_int32, [c_void_p, c_int32, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     "ali_softmax_xent": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_float, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_size_t, c_void_p]),
+    "ali_vae_latent_fwd": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_uint64, c_void_p, c_uint64,
+                                    c_int32, c_int32, c_int32, c_float, POINTER(c_void_p), POINTER(c_int32),
+                                    POINTER(c_int32), POINTER(c_void_p), c_int32, c_void_p, c_int32, c_int32, c_int32,
+                                    c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "ali_vae_loglik": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_float, c_void_p, c_float, c_float,
+                                c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "ali_vae_latent_bwd": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
+                                    c_float, c_float, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     "ali_bce_logits_pair": (c_int32, [c_void_p, c_int32, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     "ali_attr_pack": (c_int32, [POINTER(c_void_p), POINTER(c_int32), POINTER(c_int32), c_int32, POINTER(c_void_p), c_int32,
                                 c_int32, c_void_p, c_void_p, c_void_p]),

@@ -1253,3 +1253,102 @@ def assemble_planes(X, idx, tables, cont, B, H, W, Cpad, out=None, mask=None):
                                        _chk(out), B, H, W, Cpad, None if mask is None else _ptr(mask),
                                        0 if mask is None else mask.stride(0), _stream()), "ali_assemble_planes")
     return out
+
+
+# ---- the DeepSCM conditional VAE between its conv stacks (csrc/vae.hip) ----------------------------------------------
+def _row_view(t, cols, name):
+    """a [rows, cols] fp32 CUDA view whose rows are ``stride(0)`` floats apart (a column range of a wider buffer)"""
+    if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == cols and t.stride(0) >= cols
+            and (cols == 1 or t.stride(1) == 1)):
+        raise ValueError(f"{name}: need a [rows, {cols}] fp32 CUDA view with unit column stride, got {t.dtype} "
+                         f"{tuple(t.shape)} strides {tuple(t.stride())}")
+    return c_void_p(t.data_ptr())
+
+
+def vae_latent_fwd(mean, log_var, S, out, k=0.5, eps=None, seed=0, dev_counter=None, offset=0, want_eps=False,
+                   onehots=None, tables=None, cont=None, want_kl=True):
+    """Decoder input rows of S latent draws (include/ali_hip.h: ali_vae_latent_fwd): out [S*B, ld] columns 0..L become
+    mean + eps * exp(k * log_var); ``onehots`` / ``tables`` / ``cont`` given (lists, may be empty): the columns behind
+    become [onehot_j @ table_j | cont | 0] in the same launch, else they are left alone.  ``mean`` / ``log_var``:
+    [B, L] views of one row stride.  ``eps`` [S, B, L], or None: drawn in the kernel from the stream of ``normal_fill``
+    keyed (seed, dev_counter) at ``offset`` (``want_eps``: returned).  Returns (kl_sum [1] or None, eps or None)."""
+    lib = _lib.load()
+    B, L = mean.shape
+    if log_var.shape != mean.shape or log_var.stride(0) != mean.stride(0):
+        raise ValueError("vae_latent_fwd: mean and log_var must be [B, L] views of one row stride")
+    if out.dim() != 2 or out.shape[0] != S * B or out.shape[1] < L:
+        raise ValueError(f"vae_latent_fwd: out must be [S*B, ld >= L], got {tuple(out.shape)}")
+    ld = out.shape[1]
+    eps_out = None
+    if eps is not None:
+        if eps.numel() != S * B * L:
+            raise ValueError(f"vae_latent_fwd: eps must hold S*B*L = {S * B * L} values, got {tuple(eps.shape)}")
+        _chk(eps, "eps")
+    elif want_eps:
+        eps_out = torch.empty(S, B, L, dtype=torch.float32, device=mean.device)
+    write_cond = onehots is not None
+    onehots, tables = list(onehots or []), list(tables or [])
+    if len(onehots) != len(tables):
+        raise ValueError("vae_latent_fwd: one table per one-hot attribute")
+    for t in onehots:
+        if t.shape[0] != B:
+            raise ValueError("vae_latent_fwd: the attributes are per sample ([B, n]); the S draws share them")
+    for t, oh in zip(tables, onehots):
+        _chk(t, "embedding table")
+        if t.shape != (oh.shape[1], 256):
+            raise ValueError(f"vae_latent_fwd: table {tuple(t.shape)} does not match its attribute's {oh.shape[1]} classes")
+    if cont is not None and cont.shape[0] != B:
+        raise ValueError("vae_latent_fwd: cont must be [B, n_cont]")
+    ptrs, ncls, isint = _attr_arrays(onehots)
+    tptr = (c_void_p * max(len(tables), 1))(*[t.data_ptr() for t in tables])
+    kl = torch.empty(1, dtype=torch.float32, device=mean.device) if want_kl else None
+    ctr = None
+    if dev_counter is not None:
+        assert dev_counter.is_cuda and dev_counter.dtype == torch.int64
+        ctr = c_void_p(dev_counter.data_ptr())
+    ws = workspace(mean.device)
+    _lib.check(lib.ali_vae_latent_fwd(
+        _row_view(mean, L, "mean"), _row_view(log_var, L, "log_var"), mean.stride(0),
+        None if eps is None else c_void_p(eps.data_ptr()), None if eps_out is None else c_void_p(eps_out.data_ptr()),
+        int(seed) & (2 ** 64 - 1), ctr, int(offset), S, B, L, float(k), ptrs, ncls, isint, tptr, len(tables),
+        _opt(cont, "cont"), 0 if cont is None else cont.shape[1], int(write_cond), ld, _chk(out, "out"), _opt(kl),
+        c_void_p(ws.data_ptr()), ws.numel(), _stream()), "ali_vae_latent_fwd")
+    return kl, (eps if eps is not None else eps_out)
+
+
+def vae_loglik(x, xhat, S, log_var=-5.0, kl_sum=None, kl_weight=1.0, gscale=1.0, want_grad=True):
+    """Gaussian log-likelihood of x [B, P] under xhat [S*B, P] (include/ali_hip.h: ali_vae_loglik).  Returns
+    (out3 = [logp, loss = -(logp - kl_weight * kl_sum / B), kl_sum / B] device tensor, gxhat [S*B, P] or None)."""
+    lib = _lib.load()
+    B, P = x.shape
+    if xhat.shape != (S * B, P):
+        raise ValueError(f"vae_loglik: xhat must be [S*B, P] = {(S * B, P)}, got {tuple(xhat.shape)}")
+    out3 = torch.empty(3, dtype=torch.float32, device=x.device)
+    g = torch.empty_like(xhat) if want_grad else None
+    ws = workspace(x.device)
+    _lib.check(lib.ali_vae_loglik(_chk(x, "x"), _chk(xhat, "xhat"), B, S, P, float(log_var), _opt(kl_sum, "kl_sum"),
+                                  float(kl_weight), float(gscale), _chk(out3), _opt(g), c_void_p(ws.data_ptr()),
+                                  ws.numel(), _stream()), "ali_vae_loglik")
+    return out3, g
+
+
+def vae_latent_bwd(gin, eps, mean, log_var, S, gmean, glog_var, k=0.5, kl_weight=1.0, kl_scale=None, ncond=0):
+    """Head gradient from the decoder input gradient gin [S*B, ld] (include/ali_hip.h: ali_vae_latent_bwd), written
+    into the [B, L] views ``gmean`` / ``glog_var`` (one row stride); ``ncond`` > 0: also returns gcond [B, ncond], the
+    sum over the S draws of gin's columns L .. L + ncond.  ``kl_scale``: one-element device tensor multiplying the KL
+    terms (autograd's incoming gradient)."""
+    lib = _lib.load()
+    B, L = mean.shape
+    if gin.dim() != 2 or gin.shape[0] != S * B or gin.shape[1] < L + ncond:
+        raise ValueError(f"vae_latent_bwd: gin must be [S*B, ld >= L + ncond], got {tuple(gin.shape)}")
+    if eps.numel() != S * B * L:
+        raise ValueError("vae_latent_bwd: eps must hold S*B*L values")
+    if log_var.stride(0) != mean.stride(0) or gmean.stride(0) != glog_var.stride(0):
+        raise ValueError("vae_latent_bwd: mean / log_var and gmean / glog_var must each share a row stride")
+    gcond = torch.empty(B, ncond, dtype=torch.float32, device=gin.device) if ncond else None
+    _lib.check(lib.ali_vae_latent_bwd(_chk(gin, "gin"), gin.shape[1], _chk(eps, "eps"), _row_view(mean, L, "mean"),
+                                      _row_view(log_var, L, "log_var"), mean.stride(0), S, B, L, float(k),
+                                      float(kl_weight), _opt(kl_scale, "kl_scale"), _row_view(gmean, L, "gmean"),
+                                      _row_view(glog_var, L, "glog_var"), gmean.stride(0), ncond, _opt(gcond),
+                                      _stream()), "ali_vae_latent_bwd")
+    return gcond

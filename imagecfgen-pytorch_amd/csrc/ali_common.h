@@ -81,6 +81,25 @@ __host__ __device__ __forceinline__ uint64_t mix64(uint64_t z) {
   return z ^ (z >> 31);
 }
 
+// The latent stream of ali_normal_fill (elementwise.hip; ali_hip/source.py: normal_reference): element g is one half of
+// the Box-Muller pair of hash g >> 1 under the key mix64(mix64(mix64(seed) ^ counter * kCounterMul) ^ kLatentStream).
+constexpr uint64_t kLatentStream = 0x4C4154454E545A31ull;
+__device__ __forceinline__ void normal_pair(uint64_t key, uint64_t pair, float& c, float& s) {
+  const uint64_t r = mix64(key ^ pair);
+  const float u1 = (float)((uint32_t)(r >> 40) + 1u) * (1.f / 16777216.f);
+  const float u2 = (float)((uint32_t)(r >> 16) & 0xFFFFFFu) * (1.f / 16777216.f);
+  const float rad = sqrtf(-2.f * logf(u1));
+  float sn, cs;
+  sincospif(2.f * u2, &sn, &cs);        // (the angle 2*pi*u2 without rounding 2*pi*u2 itself)
+  c = rad * cs;
+  s = rad * sn;
+}
+__device__ __forceinline__ float normal_at(uint64_t key, uint64_t g) {
+  float c, s;
+  normal_pair(key, g >> 1, c, s);
+  return (g & 1) ? s : c;
+}
+
 __device__ __forceinline__ float apply_act(float v, int act, float slope) {
   if (act == ALI_ACT_LEAKY) return v > 0.f ? v : v * slope;
   if (act == ALI_ACT_TANH) return tanhf(v);

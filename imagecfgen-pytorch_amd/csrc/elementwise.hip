@@ -1025,22 +1025,7 @@ __global__ void __launch_bounds__(256) copy_multi_kernel(const CopyJobs jobs) {
 // geometry, the split of a buffer over launches or the alignment of ``out``.  u1 in (0,1] and u2 in [0,1) are the
 // hash's bits 40..63 and 16..39.  kLatentStream separates the latents' keys from the masks' (one more mix64 round
 // over the masks' key).  ali_hip/source.py: normal_reference is the same recipe in fp64.
-constexpr uint64_t kLatentStream = 0x4C4154454E545A31ull;
-__device__ __forceinline__ void normal_pair(uint64_t key, uint64_t pair, float& c, float& s) {
-  const uint64_t r = mix64(key ^ pair);
-  const float u1 = (float)((uint32_t)(r >> 40) + 1u) * (1.f / 16777216.f);
-  const float u2 = (float)((uint32_t)(r >> 16) & 0xFFFFFFu) * (1.f / 16777216.f);
-  const float rad = sqrtf(-2.f * logf(u1));
-  float sn, cs;
-  sincospif(2.f * u2, &sn, &cs);        // (the angle 2*pi*u2 without rounding 2*pi*u2 itself)
-  c = rad * cs;
-  s = rad * sn;
-}
-__device__ __forceinline__ float normal_at(uint64_t key, uint64_t g) {
-  float c, s;
-  normal_pair(key, g >> 1, c, s);
-  return (g & 1) ? s : c;
-}
+// (kLatentStream, normal_pair, normal_at: ali_common.h -- csrc/vae.hip draws from the same stream)
 // ``head`` elements in front of the first 16-byte boundary of ``out`` and the < 4 behind the last whole vector are
 // stored one by one by block 0; everything between as float4.
 __global__ void __launch_bounds__(kEwBlock)

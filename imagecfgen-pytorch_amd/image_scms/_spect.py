@@ -123,7 +123,7 @@ class SpectEncoder(SpectBase):
 class SpectGenerator(SpectBase):
     def forward(self, z, a):
         z = z.reshape((-1, LATENT_DIM))
-        feats = [z] + [a[k].float().matmul(self.table(k).weight) for k in self.cat_keys]
+        feats = [z] + [a[k].to(self.table(k).weight.dtype).matmul(self.table(k).weight) for k in self.cat_keys]
         if self.cont_key is not None:
             feats.append(a[self.cont_key].reshape((-1, 1)))
         if not z.is_cuda:

@@ -356,6 +356,40 @@ int ali_bce_logits(const float* logit, int32_t B, float target, float gscale, fl
 int ali_softmax_xent(const float* logit, const float* target, int32_t B, int32_t C, float gscale, float* out2,
                      float* glogit, int32_t* pred, int64_t* hits_accum, void* ws, size_t ws_bytes, ali_stream_t stream);
 
+/* The DeepSCM conditional VAE between its conv stacks (deepscm_vae/mnist.py:121-133 and the audio / whale copies);
+ * csrc/vae.hip.  S draws of the latent for B samples are S*B rows (s-major: row = s*B + b) of ONE decoder pass.
+ *
+ * ali_vae_latent_fwd: out[row][0..L) = mean[b] + eps[row] * exp(k * log_var[b])  (k = 0.5: elbo; k = 1: encoder.sample,
+ *   which multiplies by exp(log_var), mnist.py:58-61).  mean / log_var: [B][L] views, rows head_ld floats apart (one
+ *   [B][2L] head output serves both).  eps [S*B][L] is read, or, when NULL, drawn from the latent stream of
+ *   ali_normal_fill -- element offset + row*L + l under (seed, *dev_counter) -- and stored to eps_out (optional).
+ *   write_cond: columns [L, ld) of every row become [onehot_j[b] @ tables[j] (256 each, j < n_emb <= 8) | cont[b] | 0],
+ *   the row of ali_g_input; otherwise they are left as they are.  kl_out (optional): kl_out[0] = sum_b dkl_b,
+ *   dkl_b = 0.5 sum_l (e^lv + mean^2 - 1 - lv); needs ws >= ALI_WS_RESERVED + 8*B bytes.
+ * ali_vae_loglik: x [B][P], xhat [S*B][P], the decoder's scalar log_var (reference: -5):
+ *   out3[0] = lp = mean_b (1/S) sum_s ( -0.5 sum_p (x - xhat)^2 e^-log_var - P log_var / 2 - P/2 log 2pi )
+ *   out3[2] = kl_sum[0] / B (0 when kl_sum is NULL);   out3[1] = -(lp - kl_weight * out3[2]), the training loss
+ *   gxhat (optional) = gscale * (xhat - x) * e^-log_var / (S*B), the loss gradient; 16-byte accesses when P % 4 == 0.
+ *   ws >= ALI_WS_RESERVED + 8 * min(S*B, 1024) bytes.
+ * ali_vae_latent_bwd: gin [S*B][ld] is the decoder input gradient.  For l < L, with gz = gin[s*B + b][l]:
+ *   gmean[b][l]    = sum_s gz + kl_weight * c * mean / B
+ *   glog_var[b][l] = sum_s gz * eps * k * e^(k lv) + kl_weight * c * 0.5 (e^lv - 1) / B
+ *   (rows gld floats apart; c = kl_scale[0], a device scalar, or 1 when NULL: autograd's incoming gradient).
+ *   gcond [B][ncond] (optional) = sum_s gin[s*B + b][L .. L + ncond), what ali_g_input_table_grad takes per table.
+ * Every reduction runs in a fixed order in fp64, without float atomics: bit-identical from run to run.  The arrival
+ * counter is the last int of the workspace's reserved head and is left at zero. */
+int ali_vae_latent_fwd(const float* mean, const float* log_var, int32_t head_ld, const float* eps, float* eps_out,
+                       uint64_t seed, const int64_t* dev_counter, uint64_t offset, int32_t S, int32_t B, int32_t L,
+                       float k, const void* const* onehot, const int32_t* n_classes, const int32_t* onehot_is_int,
+                       const float* const* tables, int32_t n_emb, const float* cont, int32_t n_cont, int32_t write_cond,
+                       int32_t ld, float* out, float* kl_out, void* ws, size_t ws_bytes, ali_stream_t stream);
+int ali_vae_loglik(const float* x, const float* xhat, int32_t B, int32_t S, int32_t P, float log_var,
+                   const float* kl_sum, float kl_weight, float gscale, float* out3, float* gxhat, void* ws,
+                   size_t ws_bytes, ali_stream_t stream);
+int ali_vae_latent_bwd(const float* gin, int32_t ld, const float* eps, const float* mean, const float* log_var,
+                       int32_t head_ld, int32_t S, int32_t B, int32_t L, float k, float kl_weight, const float* kl_scale,
+                       float* gmean, float* glog_var, int32_t gld, int32_t ncond, float* gcond, ali_stream_t stream);
+
 /* torch.optim.Adam step (mnist.py:176-179,230,236,241), no amsgrad / decay.
  * One launch over a flat parameter segment.  The 1-based step count is `step`, or *dev_step when
  * dev_step != NULL (graph replays); the gradient is read as grad_scale * g (1/world for DP).
