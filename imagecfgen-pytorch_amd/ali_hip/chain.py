@@ -875,6 +875,134 @@ def chain_backward_gen(plan: ChainPlan, saved, gy: torch.Tensor, c_log_in: int, 
     return gx, grads
 
 
+# ---------------------------------------------------------------------- gradient of a gradient norm (WGAN-GP)
+# A stack of convolutions and LeakyReLUs (no BatchNorm, no Dropout) is piecewise linear in its input.  With a_l the
+# activations, h_l = act'(a_l) * g_l the pre-activation gradients of a backward pass and g0 its input gradient, the
+# gradient of any f(g0) with respect to the weights is one more FORWARD pass of the tangent v = df/dg0 through the same
+# convolutions, u_l = act'(a_l) * conv(W_l, u_{l-1}) (no bias), and then dW_l = bwd_weight(x = u_{l-1}, dy = h_l):
+# g_{l-1} is linear in W_l and the masks act'(a_l) are piecewise constant.  Biases and the input get zero.
+def _plain_stack(plan: ChainPlan, what: str):
+    for st in plan.stages:
+        if st.pre or st.kind not in ("conv", "flat") or st.act not in (ACT_NONE, ACT_LEAKY):
+            raise NotImplementedError(f"ali_hip.chain.{what}: needs a stack of Conv2d / Flatten + Linear stages with "
+                                      f"LeakyReLU or no activation and nothing in front of them (stage {st.index}: "
+                                      f"{st.kind}, pre-ops {st.pattern}, activation {st.act})")
+
+
+def saved_rows(saved, lo: int, hi: int):
+    """The saved state of the samples [lo, hi) of a forward pass over a stack without BatchNorm (rows of a batch are
+    independent there: contiguous row ranges of every activation)."""
+    out = []
+    for sv in saved:
+        assert sv.bn is None and sv.bn_stats is None, "saved_rows: BatchNorm statistics couple the rows of a batch"
+        s2 = _Saved()
+        s2.x_in, s2.t, s2.y = sv.x_in[lo:hi], sv.t[lo:hi], sv.y[lo:hi]
+        s2.mask = None if sv.mask is None else sv.mask[lo:hi]
+        s2.bn, s2.bn_stats, s2.pattern, s2.training, s2.route, s2.c_log = None, None, sv.pattern, sv.training, sv.route, sv.c_log
+        s2.in_shape, s2.out_shape = (hi - lo,) + tuple(sv.in_shape[1:]), (hi - lo,) + tuple(sv.out_shape[1:])
+        g = sv.geom
+        s2.geom = ops.geom(hi - lo, g.H, g.W, g.C, g.P, g.Q, g.K, g.R, g.S, g.stride, g.pad)
+        out.append(s2)
+    return out
+
+
+def chain_backward_keep_gen(plan: ChainPlan, saved, gy: torch.Tensor, c_log_in: int, need_gx: bool = True,
+                            gx_planes=None, first_rows=None):
+    """The data-gradient half of ``chain_backward_gen`` over a plain stack, KEEPING every stage's pre-activation
+    gradient: returns (gx or None, [h_0 .. h_{n-1}]), h_l the gradient of stage l's convolution output (what its
+    weight gradient contracts with).  No parameter gradients.  ``first_rows`` = (lo, hi): the first stage's data
+    gradient -- the largest map -- only for those samples; ``gx_planes`` as in ``chain_backward_gen``."""
+    _plain_stack(plan, "chain_backward_keep")
+    n = len(plan.stages)
+    last = plan.stages[-1]
+    assert saved[0].c_log == c_log_in, "chain_backward_keep: c_log_in differs from the forward pass's"
+    gy = gy.contiguous()
+    g_pre = gy if last.act == ACT_NONE else ops.act_bwd(gy, saved[-1].y, last.act, last.slope)
+    hs = [None] * n
+    for i in range(n - 1, -1, -1):
+        hs[i] = g_pre
+        if i > 0:
+            g_pre = yield from _data_grad(plan, plan.stages[i], saved[i], g_pre, 0, plan.stages[i - 1].act,
+                                          plan.stages[i - 1].slope, True, False, {}, {})
+    if not need_gx:
+        return None, hs
+    st, sv = plan.stages[0], saved[0]
+    if first_rows is not None:
+        sv, g_pre = saved_rows(saved[:1], *first_rows)[0], g_pre[first_rows[0]:first_rows[1]]
+    gx = (yield from _plane_grads(plan, st, sv, g_pre, gx_planes)) if gx_planes is not None else None
+    if gx is None:
+        gx = yield from _data_grad(plan, st, sv, g_pre, 0, ACT_NONE, 0.0, True, False, {}, {})
+        if gx_planes is not None:
+            gx = torch.stack([gx[..., c] for c in gx_planes], dim=-1)
+    return gx, hs
+
+
+def chain_tangent_gen(plan: ChainPlan, saved, u0: torch.Tensor):
+    """The tangent pass over the saved activations of a plain stack: u_0 = ``u0`` (NHWC, the forward input's shape),
+    u_l = act'(a_l) * conv(W_l, u_{l-1}) without bias -- one forward GEMM per stage with the activation derivative as
+    its epilogue.  Returns [u_0 .. u_{n-1}], the inputs of the n stages (the last stage's own output is not needed for
+    the weight gradients).  Generator: yields after every GEMM request."""
+    _plain_stack(plan, "chain_tangent")
+    if tuple(u0.shape) != tuple(saved[0].in_shape):
+        raise ValueError(f"chain_tangent: u0 {tuple(u0.shape)} is not the forward input's shape {tuple(saved[0].in_shape)}")
+    us = [u0.contiguous()]
+    for st, sv in zip(plan.stages[:-1], saved[:-1]):
+        Cp = sv.in_shape[3]
+        u = torch.empty(sv.out_shape, dtype=torch.float32, device=u0.device)
+        ep = ops.epilogue(dact_y=sv.y if st.act != ACT_NONE else None, dact=st.act, dslope=st.slope)
+        if st.index == 0 and sv.c_log < Cp:
+            ep.in_ch_live = sv.c_log
+        ops.conv_fwd(sv.geom, us[-1], plan.packed(st, "fwd", Cp), u, ep, live=(sv.c_log, None))
+        yield
+        us.append(u)
+    return us
+
+
+def tangent_param_grads(plan: ChainPlan, saved, us, hs, grad_dst=None, head_ones: bool = False):
+    """{id(weight): dW_l = bwd_weight(x = u_{l-1}, dy = h_l)} of every stage (``chain_tangent_gen``'s ``us``,
+    ``chain_backward_keep_gen``'s ``hs``), written into ``grad_dst`` {id(param): view} where it names the weight.
+    Biases get nothing (their gradient is zero).  ``head_ones``: the backward pass started from gy = 1, so the
+    weight gradient of a Flatten + Linear(., 1) head on a 1x1 map is the column sum of its tangent input."""
+    grad_dst = grad_dst or {}
+    out = {}
+    for st, sv, u, h in zip(plan.stages, saved, us, hs):
+        w = st.mod.weight
+        B, H, W, Cp = sv.in_shape
+        if (head_ones and st.kind == "flat" and st.index == len(plan.stages) - 1 and H * W == 1 and w.shape[0] == 1
+                and Cp == sv.c_log and st.act == ACT_NONE):
+            dw = grad_dst[id(w)] if id(w) in grad_dst else torch.empty_like(w)
+            ops.colsum(B, Cp, Cp, u, out=dw.view(-1))
+            out[id(w)] = dw
+            continue
+        s2 = _Saved()
+        for name in _Saved.__slots__:
+            if hasattr(sv, name):
+                setattr(s2, name, getattr(sv, name))
+        s2.t = s2.x_in = u
+        tmp = {}
+        _param_grads(st, s2, h, 0, tmp, {id(w): grad_dst[id(w)]} if id(w) in grad_dst else {}, None)
+        out[id(w)] = tmp[id(w)]
+    return out
+
+
+def chain_param_grads(plan: ChainPlan, saved, hs, grad_dst=None):
+    """The parameter-gradient half that ``chain_backward_keep_gen`` leaves out: weight and bias gradients of every stage
+    from its saved input and its pre-activation gradient ``hs[l]`` (both may be row ranges: ``saved_rows``).  Returns
+    {id(param): grad}; ``grad_dst`` as in ``chain_backward_gen``."""
+    grads = {}
+    for st, sv, h in zip(plan.stages, saved, hs):
+        _param_grads(st, sv, h, 0, grads, grad_dst or {}, None)
+    return grads
+
+
+def chain_backward_keep(*args, **kwargs):
+    return drive(chain_backward_keep_gen(*args, **kwargs))
+
+
+def chain_tangent(*args, **kwargs):
+    return drive(chain_tangent_gen(*args, **kwargs))
+
+
 class ChainFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, plan: ChainPlan, training: bool, c_log_in: int, x, *params):

@@ -1123,6 +1123,70 @@ def bce_logits_pair(logit, B, target_a, target_b, gscale=1.0, want_grad=True):
     return out3, gl
 
 
+def _rows2d(t, name):
+    """(pointer, B, P) of a contiguous fp32 CUDA tensor read as [B][P] rows (B = its first dimension)"""
+    if t.dim() < 1 or t.numel() == 0:
+        raise ValueError(f"{name}: need a non-empty tensor with a batch dimension")
+    return _chk(t, name), t.shape[0], t.numel() // t.shape[0]
+
+
+def gp_mix(x_real, x_fake, eps=None, seed=0, dev_counter=None, offset=0, out=None):
+    """xhat = eps * x_real + (1 - eps) * x_fake with one eps per image (include/ali_hip.h: ali_gp_mix).  ``eps`` [B]
+    given, or None: drawn on the device, uniform in [0, 1), from the counter stream keyed (seed, *dev_counter) at
+    element ``offset + b`` (``ali_hip.source.uniform_reference``).  Returns (xhat, eps used [B])."""
+    if x_real.shape != x_fake.shape:
+        raise ValueError(f"gp_mix: x_real {tuple(x_real.shape)} and x_fake {tuple(x_fake.shape)} differ in shape")
+    pr, B, P = _rows2d(x_real, "x_real")
+    out = torch.empty_like(x_real) if out is None else out
+    if eps is not None and eps.numel() != B:
+        raise ValueError(f"gp_mix: eps holds {eps.numel()} values for {B} images")
+    eps_out = torch.empty(B, dtype=torch.float32, device=x_real.device)
+    _lib.check(_lib.load().ali_gp_mix(pr, _chk(x_fake, "x_fake"), _opt(eps, "eps"), int(seed) & (2 ** 64 - 1),
+                                      _counter_ptr(dev_counter), int(offset), B, P, _chk(out, "xhat"), _chk(eps_out),
+                                      _stream()), "ali_gp_mix")
+    return out, eps_out
+
+
+def gp_penalty(g0, weight=1.0, want_v=True, out=None):
+    """Per-image 2-norm n_b of ``g0`` [B, ...]: returns (out2 = [mean (n_b - 1)^2, mean n_b] device tensor,
+    v = weight * (2 / B) * (1 - 1 / n_b) * g0 or None); ``out`` may be ``g0`` itself (include/ali_hip.h:
+    ali_gp_penalty)."""
+    pg, B, P = _rows2d(g0, "g0")
+    out2 = torch.empty(2, dtype=torch.float32, device=g0.device)
+    v = (torch.empty_like(g0) if out is None else out) if want_v else None
+    if v is not None and v.shape != g0.shape:
+        raise ValueError("gp_penalty: out must have g0's shape")
+    ws = workspace(g0.device)
+    _lib.check(_lib.load().ali_gp_penalty(pg, B, P, float(weight), _chk(out2), _opt(v, "v"), c_void_p(ws.data_ptr()),
+                                          ws.numel(), _stream()), "ali_gp_penalty")
+    return out2, v
+
+
+def wgan_critic(d_fake, d_real, gscale=1.0, want_grad=True, g_fake=None, g_real=None):
+    """returns (out3 = [mean d_fake - mean d_real, mean d_fake, mean d_real] device tensor, g_fake, g_real): the
+    gradients gscale / B and -gscale / B (None for absent logits or ``want_grad=False``); ``g_fake`` / ``g_real``:
+    where to write them (include/ali_hip.h: ali_wgan_critic)."""
+    some = d_fake if d_fake is not None else d_real
+    if some is None:
+        raise ValueError("wgan_critic: needs d_fake or d_real")
+    B = some.numel()
+    if d_fake is not None and d_real is not None and d_real.numel() != B:
+        raise ValueError("wgan_critic: d_fake and d_real differ in length")
+    out3 = torch.empty(3, dtype=torch.float32, device=some.device)
+    if want_grad:
+        g_fake = g_fake if (g_fake is not None or d_fake is None) else torch.empty_like(d_fake)
+        g_real = g_real if (g_real is not None or d_real is None) else torch.empty_like(d_real)
+    else:
+        g_fake = g_real = None
+    for g, d in ((g_fake, d_fake), (g_real, d_real)):
+        if g is not None and (d is None or g.numel() != B):
+            raise ValueError("wgan_critic: a gradient buffer needs its logits and their length")
+    _lib.check(_lib.load().ali_wgan_critic(_opt(d_fake, "d_fake"), _opt(d_real, "d_real"), B, float(gscale), _chk(out3),
+                                           _opt(g_fake, "g_fake"), _opt(g_real, "g_real"), _stream()),
+               "ali_wgan_critic")
+    return out3, g_fake, g_real
+
+
 def softmax_xent(logit, target, gscale=1.0, want_grad=True, want_pred=False, hits_accum=None):
     """Cross-entropy of [B, C] logits against probability rows, gradient, arg-max and hit count in one launch
     (include/ali_hip.h: ali_softmax_xent).  Returns (out2 = [mean loss, hits] device tensor, glogit or None,

@@ -59,6 +59,20 @@ def normal_reference(seed, counter, n, offset=0):
     return torch.from_numpy(rad * np.where(odd, np.sin(ang), np.cos(ang)))
 
 
+_GP_STREAM = 0x47504D4958455053              # csrc/gan.hip: kGpStream
+
+
+def uniform_reference(seed, counter, n, offset=0):
+    """host evaluation of the per-image ``eps`` that ``ali_gp_mix(eps=NULL, seed, &counter, offset, B=n, ...)`` draws: a
+    float32 CPU tensor [n], exact (k / 2^24, k the top 24 bits of ``mix64(key ^ g)`` under the latent key mixed once
+    more with the stream's constant)."""
+    key = _mix64_int(_mix64_int(_mix64_int(int(seed)) ^ (int(counter) * _COUNTER_MUL & _M64)) ^ _LATENT_STREAM)
+    key = _mix64_int(key ^ _GP_STREAM)
+    g = np.arange(n, dtype=np.uint64) + np.uint64(int(offset) & _M64)
+    k = (_mix64(np.uint64(key) ^ g) >> np.uint64(40)).astype(np.int64)
+    return torch.from_numpy((k / 16777216.0).astype(np.float32))
+
+
 class DeviceDataset:
     """A MorphoMNIST-style data set resident in device memory, for ``AliStepper.step_indexed``.
 

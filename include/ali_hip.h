@@ -411,6 +411,32 @@ int ali_add_i64_multi(int32_t n, int64_t* const* counters, const int64_t* incs, 
 int ali_bce_logits_pair(const float* logit, int32_t B, float target_a, float target_b, float gscale, float* out3,
                         float* glogit, ali_stream_t stream);
 
+/* Between the conv stacks of a WGAN-GP critic step (gans/audio_mnist.py: wgan_loss_it, compute_gradient_penalty);
+ * csrc/gan.hip.  x_real, x_fake, xhat, g0, v: contiguous [B][P] fp32, 1 <= B <= 65535; 16-byte accesses when P % 4 == 0
+ * and the pointers are 16-byte aligned, one element at a time otherwise.
+ *
+ * ali_gp_mix: xhat[b][p] = eps[b] * x_real[b][p] + (1 - eps[b]) * x_fake[b][p], the products and the sum rounded one by
+ *   one (torch's fp32 statement bit for bit).  eps [B] is read, or, when NULL, drawn per image, uniform in [0, 1) (24
+ *   bits), from the counter RNG of ali_normal_fill under a key of its own: image b is element offset + b of the stream
+ *   keyed by (seed, *dev_counter; dev_counter may be NULL) -- a captured graph advances with the device counter.  The
+ *   eps used is stored to eps_out [B] (optional).
+ * ali_gp_penalty: g0 is the gradient of sum_b D(xhat_b) with respect to xhat.  n_b = ||g0_b||_2;
+ *   out2[0] = mean_b (n_b - 1)^2;  out2[1] = mean_b n_b;
+ *   v[b][p] = lambda * (2 / B) * (1 - 1 / n_b) * g0[b][p]  (NULL: skipped; v_b = 0 where n_b == 0, as torch's norm
+ *   backward) -- the gradient of lambda * out2[0] with respect to g0.  v may be g0 itself.  One launch, one block per
+ *   image; ws >= ALI_WS_RESERVED + 16 * B bytes; the arrival counter is the last int of the reserved head and is left
+ *   at zero.  fp64 sums in a fixed order, no float atomics: bit-identical from run to run.
+ * ali_wgan_critic: logits d_fake [B], d_real [B] (either may be NULL, its mean is then 0):
+ *   out3[0] = mean(d_fake) - mean(d_real);  out3[1] = mean(d_fake);  out3[2] = mean(d_real);
+ *   g_fake[b] = gscale / B;  g_real[b] = -gscale / B  (each optional; needs its logits).  The generator's loss
+ *   -mean D(G(z)) is the call with d_real = NULL, gscale = -1: out3[0] is then its negative. */
+int ali_gp_mix(const float* x_real, const float* x_fake, const float* eps, uint64_t seed, const int64_t* dev_counter,
+               uint64_t offset, int32_t B, int64_t P, float* xhat, float* eps_out, ali_stream_t stream);
+int ali_gp_penalty(const float* g0, int32_t B, int64_t P, float lambda, float* out2, float* v, void* ws,
+                   size_t ws_bytes, ali_stream_t stream);
+int ali_wgan_critic(const float* d_fake, const float* d_real, int32_t B, float gscale, float* out3, float* g_fake,
+                    float* g_real, ali_stream_t stream);
+
 /* Attribute plumbing of one batch (mnist.py:47-55, audio_mnist.py:203-210, whalecalls.py:455): idx[b*n_cat + j] =
  * argmax of categorical attribute j (one-hot rows of n_classes[j] floats, or int32 when cat_is_int[j]; first maximum
  * like torch.argmax); cont[b*n_cont + j] = cont_in[j][b]. */
