@@ -58,6 +58,11 @@ class PackCache:
         self.store = {}
         self.static = False
 
+    def make_static(self):
+        """from here on copies are rebuilt in place (the parameters were just re-pointed: what was built is dropped)"""
+        self.store.clear()
+        self.static = True
+
     @staticmethod
     def _tag(param):
         return (param.data_ptr(), param._version, tuple(param.shape))

@@ -18,17 +18,14 @@ import torch.nn.functional as F
 
 from . import ops
 from .chain import chain_backward, chain_forward, get_plan
-from .step import FlatGroup, GeneratorSampler, _Graphed
+from .graphs import GraphCache
+from .step import FlatGroup, GeneratorSampler
 
 
 def nhwc_input(x: torch.Tensor) -> torch.Tensor:
     """[B,C,H,W] image batch -> the chain's NHWC input, channels zero-padded to a multiple of 4"""
     x = x.float().permute(0, 2, 3, 1)
     return F.pad(x, (0, (-x.shape[-1]) % 4)).contiguous()
-
-
-def _sig(x, extra=()):
-    return (tuple(x.shape), x.dtype) + tuple(extra)
 
 
 class ClassifierStepper:
@@ -44,13 +41,12 @@ class ClassifierStepper:
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, capture=False):
         self.model = model
         self.capture = capture
-        self._graphs = {}
+        self._graphs = GraphCache()
         self.on_device = next(model.parameters()).is_cuda
         if self.on_device:
             self.plan = get_plan(model)
             self.opt = FlatGroup(list(model.parameters()), lr, betas, eps)
-            self.plan.cache.store.clear()
-            self.plan.cache.static = True
+            self.plan.cache.make_static()
         else:
             self.opt = torch.optim.Adam(model.parameters(), lr=lr, betas=betas, eps=eps)
 
@@ -63,24 +59,10 @@ class ClassifierStepper:
         y = y.float()
         if not self.capture:
             return self._step(x, y)
-        key = (_sig(x), _sig(y), self.model.training)
-        if key not in self._graphs:
-            snap = self._snapshot()
-            ent = _Graphed((x, y), self._step, lambda: self._restore(snap))
-            ent.out = ent.capture(self._step, *ent.inputs)
-            self._graphs[key] = ent
-        return self._graphs[key](x, y)
+        return self._graphs(self._step, (x, y), (self.model.training,), self.opt.state_tensors(), self._restored)
 
-    def _state_tensors(self):
-        return [self.opt.flat, self.opt.m, self.opt.v, self.opt.step_t]
-
-    def _snapshot(self):
-        return [t.clone() for t in self._state_tensors()]
-
-    def _restore(self, snap):
-        for t, v in zip(self._state_tensors(), snap):
-            t.copy_(v)
-        self.opt.steps = int(self.opt.step_t.item())
+    def _restored(self):
+        self.opt.resync()
         self.plan.cache.refresh()
 
     def _step(self, x, y):
@@ -104,10 +86,6 @@ class ClassifierStepper:
         return {"loss": loss.detach(), "hits": hits}
 
 
-def _versions(modules):
-    return tuple(p._version for m in modules for p in m.parameters())
-
-
 class ClassifierScorer:
     """Accuracy of several classifiers over a stream of batches:
 
@@ -116,21 +94,14 @@ class ClassifierScorer:
     ``add(images, labels)`` runs every classifier on the batch and adds its hits into that classifier's int64 counter
     ON THE DEVICE (``ali_softmax_xent(hits_accum=...)``), all of it one HIP graph per input shape; ``result()`` is the
     one host read, {name: hits / seen}; ``reset()`` clears the counters.  Graphs captured for older weights are dropped
-    when a parameter's version changes (``GeneratorSampler._sync``)."""
+    when a parameter's version changes (``GraphCache(modules=...)``)."""
 
     def __init__(self, models, capture=True):
         self.models = dict(models)
         self.capture = capture
         self.seen = 0
         self.counters = None
-        self._graphs = {}
-        self._versions = None
-
-    def _sync(self):
-        v = _versions(self.models.values())
-        if v != self._versions:
-            self._graphs.clear()
-            self._versions = v
+        self._graphs = GraphCache(modules=self.models.values())
 
     def _ensure_counters(self, device):
         if self.counters is None or self.counters.device != device:
@@ -154,15 +125,8 @@ class ClassifierScorer:
         self.seen += images.shape[0]
         if not (self.capture and images.is_cuda):
             return self._score(images, labels)
-        self._sync()
-        key = (_sig(images), tuple((k,) + _sig(v) for k, v in sorted(labels.items())),
-               tuple(m.training for m in self.models.values()))
-        if key not in self._graphs:
-            snap = self.counters.clone()        # (the warm-up pass is no batch of the stream)
-            ent = _Graphed((images, labels), self._score, lambda: self.counters.copy_(snap))
-            ent.capture(self._score, *ent.inputs)
-            self._graphs[key] = ent
-        self._graphs[key](images, labels)
+        # (state: the warm-up pass is no batch of the stream)
+        self._graphs(self._score, (images, labels), tuple(m.training for m in self.models.values()), [self.counters])
 
     def result(self):
         hits = self.counters.tolist() if self.counters is not None else [0] * len(self.models)
@@ -190,8 +154,7 @@ class GeneratorScore:
         self.capture = capture
         self.sampler = GeneratorSampler(G, capture=False)
         self.scorer = ClassifierScorer(models, capture=False)
-        self._graphs = {}
-        self._versions = None
+        self._graphs = GraphCache(modules=[G, *self.scorer.models.values()])
 
     def _run(self, zs, attrs):
         gen = self.sampler._forward(zs, attrs)
@@ -211,18 +174,8 @@ class GeneratorScore:
         sc.seen += B
         if not (self.capture and zs.is_cuda):
             return self._run(zs, attrs)
-        v = _versions([self.G] + list(sc.models.values()))
-        if v != self._versions:
-            self._graphs.clear()
-            self._versions = v
-        key = (_sig(zs), tuple((k,) + _sig(t) for k, t in sorted(attrs.items())), self.G.training,
-               tuple(m.training for m in sc.models.values()))
-        if key not in self._graphs:
-            snap = sc.counters.clone()
-            ent = _Graphed((zs, attrs), self._run, lambda: sc.counters.copy_(snap))
-            ent.out = ent.capture(self._run, *ent.inputs)
-            self._graphs[key] = ent
-        return self._graphs[key](zs, attrs)
+        return self._graphs(self._run, (zs, attrs), (self.G.training, tuple(m.training for m in sc.models.values())),
+                            [sc.counters])
 
     def result(self):
         return self.scorer.result()

@@ -24,7 +24,8 @@ from . import ops
 from . import source as _source
 from .chain import (chain_backward, chain_backward_keep, chain_forward, chain_param_grads, chain_tangent, get_plan,
                     saved_rows, tangent_param_grads)
-from .step import FlatGroup, _Graphed
+from .graphs import GraphCache
+from .step import FlatGroup
 
 LATENT_DIM = 100
 LATENT_LD = 128          # channel stride of the Generator's input rows: % 32 == 0 -> the GEMM's uniform-tap loop
@@ -95,39 +96,6 @@ def gradient_penalty(disc, interpolates):
     return GradientPenaltyFn.apply(plan, x, *plan.params())
 
 
-def _sig(x):
-    return None if x is None else (tuple(x.shape), x.dtype)
-
-
-def adam_state_dict(group: FlatGroup):
-    """the ``torch.optim.Adam.state_dict()`` of a FlatGroup (per-parameter moments in the parameters' own layout, CPU
-    clones): ``torch.optim.Adam(params, ...).load_state_dict(...)`` takes it"""
-    step = int(group.step_t.item())
-    proto = torch.optim.Adam([torch.zeros(1)], lr=group.lr, betas=tuple(group.betas), eps=group.eps).state_dict()
-    pg = dict(proto["param_groups"][0], params=list(range(len(group.params))))
-    state = {i: {"step": torch.tensor(float(step)), "exp_avg": m.detach().cpu().clone().contiguous(),
-                 "exp_avg_sq": v.detach().cpu().clone().contiguous()}
-             for i, (m, v) in enumerate(zip(group.m_views, group.v_views))}
-    return {"state": state, "param_groups": [pg]}
-
-
-def load_adam_state_dict(group: FlatGroup, sd):
-    """inverse of ``adam_state_dict`` (also takes the state dict of a ``torch.optim.Adam`` over the same parameters;
-    parameters without state get zero moments); in place, so captured graphs stay valid"""
-    with torch.no_grad():
-        steps = 0
-        for i, (m, v) in enumerate(zip(group.m_views, group.v_views)):
-            st = sd["state"].get(i)
-            if st is None:
-                m.zero_(), v.zero_()
-                continue
-            m.copy_(st["exp_avg"].to(m.device))
-            v.copy_(st["exp_avg_sq"].to(v.device))
-            steps = int(st["step"])
-        group.steps = steps
-        group.step_t.fill_(steps)
-
-
 class GanStepper:
     """One iteration of gans/audio_mnist.py:287-337, hand scheduled (no autograd engine):
 
@@ -181,11 +149,10 @@ class GanStepper:
             off += p.numel()
         self.gp_weight_views = {id(st.mod.weight): self.gp_views[id(st.mod.weight)] for st in self.pD.stages}
         for plan in (self.pG, self.pD):
-            plan.cache.store.clear()
-            plan.cache.static = True
+            plan.cache.make_static()
         self.iter_t = torch.zeros(1, dtype=torch.int64, device=dev)     # iterations done: keys the draws
         self.ctr = 0                                                    # host mirror: decides the G step
-        self._graphs = {}
+        self._graphs = GraphCache()
 
     # ------------------------------------------------------------------ draws
     def _z(self, given, B, slot, dev):
@@ -266,15 +233,9 @@ class GanStepper:
         return res
 
     # ------------------------------------------------------------------ capture, state
-    def _state_tensors(self):
-        return [t for g in (self.opt_g, self.opt_d) for t in (g.flat, g.m, g.v, g.step_t)] + [self.iter_t]
-
-    def _restore(self, snap):
-        for t, v in zip(self._state_tensors(), snap):
-            t.copy_(v)
-        for g in (self.opt_g, self.opt_d):
-            g.steps = int(g.step_t.item())
-        for plan in (self.pG, self.pD):
+    def _restored(self):
+        for g, plan in ((self.opt_g, self.pG), (self.opt_d, self.pD)):
+            g.resync()
             plan.cache.refresh()
 
     @torch.no_grad()
@@ -283,32 +244,18 @@ class GanStepper:
             raise ValueError("GanStepper.step: the batch must live on the model's CUDA device")
         do_g = self.ctr % self.k == 0
         self.ctr += 1
-        opt = (z_g, z_d, z_s, eps)
         if not self.capture:
-            return self._iteration(do_g, images, *opt)
-        given = [i for i, t in enumerate(opt) if t is not None]
-        key = (_sig(images), tuple(_sig(t) for t in opt), do_g, self.G.training, self.D.training)
-        args = [images] + [opt[i] for i in given]
-
-        def run(*a):
-            full = [None] * 4
-            for i, t in zip(given, a[1:]):
-                full[i] = t
-            return self._iteration(do_g, a[0], *full)
-
-        if key not in self._graphs:
-            snap = [t.clone() for t in self._state_tensors()]
-            ent = _Graphed(args, run, lambda: self._restore(snap))
-            ent.out = ent.capture(run, *ent.inputs)
-            self._graphs[key] = ent
-        return self._graphs[key](*args)
+            return self._iteration(do_g, images, z_g, z_d, z_s, eps)
+        return self._graphs(lambda *a: self._iteration(do_g, *a), (images, z_g, z_d, z_s, eps),
+                            (do_g, self.G.training, self.D.training),
+                            self.opt_g.state_tensors() + self.opt_d.state_tensors() + [self.iter_t], self._restored)
 
     def state_dict(self):
         """Resumable checkpoint: the two module state dicts, both Adam states in ``torch.optim.Adam.state_dict()``
         format, the iteration counter and the seed that key the draws.  Tensors are cloned to the CPU."""
         sd = {f"{n}_state_dict": {k: v.detach().cpu().clone() for k, v in m.state_dict().items()}
               for n, m in (("G", self.G), ("D", self.D))}
-        sd.update(optimizer_G=adam_state_dict(self.opt_g), optimizer_D=adam_state_dict(self.opt_d),
+        sd.update(optimizer_G=self.opt_g.torch_state_dict(), optimizer_D=self.opt_d.torch_state_dict(),
                   iteration=int(self.iter_t.item()), z_seed=self.seed)
         return sd
 
@@ -320,8 +267,8 @@ class GanStepper:
                 src = sd[f"{n}_state_dict"]
                 for k, v in m.state_dict().items():
                     v.copy_(src[k])
-            load_adam_state_dict(self.opt_g, sd["optimizer_G"])
-            load_adam_state_dict(self.opt_d, sd["optimizer_D"])
+            self.opt_g.load_torch_state_dict(sd["optimizer_G"])
+            self.opt_d.load_torch_state_dict(sd["optimizer_D"])
             self.ctr = int(sd.get("iteration", 0))
             self.iter_t.fill_(self.ctr)
             if int(sd.get("z_seed", self.seed)) != self.seed:

@@ -33,6 +33,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .graphs import GraphCache
 from .source import _COUNTER_MUL, _M64, _mix64, _mix64_int
 
 _PHASE_STREAM = 0x474C504841534531            # csrc/griffinlim.hip: kPhaseStream
@@ -167,10 +168,10 @@ class GriffinLim:
     ``gl(specgram[..., F, T], angles0=None) -> [..., length]`` and ``gl.from_image(img, mean, std, stds_kept)`` straight
     from the generator's standardised output (``img_to_spect``, ``.exp()`` and the root fused into the first launch);
     ``gl.from_log(log_spec)`` takes a log-spectrogram.  Buffers are allocated once per input shape; with ``capture``
-    the whole call is recorded once per shape through ``step._Graphed`` and replayed.  Random initial phases are keyed
-    by (``seed``, ``gl.counter``): the device counter advances by one per call -- inside the final launch, so replays
-    draw fresh phases -- and ``uniform_reference(seed, counter, B*F*T)`` reproduces a call's draws on the host.
-    CPU tensors run ``griffinlim_torch``."""
+    the whole call is recorded once per shape and entry point (``graphs.GraphCache``) and replayed.  Random initial
+    phases are keyed by (``seed``, ``gl.counter``): the device counter advances by one per call -- inside the final
+    launch, so replays draw fresh phases -- and ``uniform_reference(seed, counter, B*F*T)`` reproduces a call's draws on
+    the host.  CPU tensors run ``griffinlim_torch``."""
 
     def __init__(self, n_fft, n_iter=32, win_length=None, hop_length=None, power=2.0, momentum=0.99, length=None,
                  rand_init=True, device="cuda", seed=0, capture=True):
@@ -192,6 +193,7 @@ class GriffinLim:
         self._w = None                     # (forward [2F,1,win], inverse [win,1,2F]) on the device
         self.counter = None                # int64 [1] on the device: calls that drew random phases so far
         self._states = {}
+        self._graphs = GraphCache()
         self.launches = 0                  # C-ABI launches of the last eager / recorded pass
 
     # ---- per-shape state
@@ -222,7 +224,7 @@ class GriffinLim:
             new = lambda *s: torch.empty(*s, dtype=torch.float32, device=self.device)  # noqa: E731
             st = dict(L=L, renv=self.renv(T, L).to(self.device), mag=new(B * T, self.F), X=new(B * T, 2 * self.F),
                       fr=new(B, T, self.win), frames=new(B, T, self.win), Y=(new(B * T, 2 * self.F), new(B * T, 2 * self.F)),
-                      out=new(B, L), graphs={})
+                      out=new(B, L))
             self._states[(B, T)] = st
         return st
 
@@ -273,21 +275,13 @@ class GriffinLim:
         if not self.capture:
             out = self._run(st, mode, src, a0, stats)
         else:
-            from .step import _Graphed
-            key = (mode, a0 is not None, None if stats is None else stats[2])
-            ent = st["graphs"].get(key)
-            inputs = (src,) + (a0 or ()) + (stats[:2] if stats is not None else ())
+            kept = None if stats is None else stats[2]
 
-            def run(s, *rest):
-                a = tuple(rest[:2]) if a0 is not None else None
-                ms = (tuple(rest[-2:]) + (stats[2],)) if stats is not None else None
-                return self._run(st, mode, s, a, ms)
-            if ent is None:
-                c0 = self.counter.clone()
-                ent = _Graphed(inputs, run, lambda: self.counter.copy_(c0))     # (the warm-up is no call: same key again)
-                ent.out = ent.capture(run, *ent.inputs)
-                st["graphs"][key] = ent
-            out = ent(*inputs)
+            def run(s, re, im, mean, std):
+                return self._run(st, mode, s, None if re is None else (re, im), None if mean is None else (mean, std, kept))
+            # (state: the warm-up is no call -- the same counter value again)
+            out = self._graphs(run, (src,) + (a0 or (None, None)) + (stats[:2] if stats is not None else (None, None)),
+                               (mode, kept), [self.counter])
         return out.clone().reshape(shape[:-2] + (st["L"],))
 
     def __call__(self, specgram, angles0=None):

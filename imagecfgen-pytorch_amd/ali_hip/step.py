@@ -32,6 +32,7 @@ from . import ssim
 from . import chain as _chain
 from .chain import (chain_backward, chain_backward_gen, chain_forward, chain_forward_gen, drive, get_plan,
                     run_parallel, slice_saved)
+from .graphs import GraphCache, _Graphed
 
 
 class FlatGroup:
@@ -89,6 +90,15 @@ class FlatGroup:
         if self.flat16 is not None:
             self.flat16.copy_(self.flat)
 
+    def state_tensors(self):
+        """what a pass that must not count (a graph's warm-up) clones and puts back; then ``resync``"""
+        return [self.flat, self.m, self.v, self.step_t]
+
+    def resync(self):
+        """the state tensors were rewritten on the device: the host's step count and the fp16 twin follow"""
+        self.steps = int(self.step_t.item())
+        self.sync16()
+
     @staticmethod
     def logical(views):
         """the buffer behind ``views`` as one flat tensor in the parameters' own (row-major) element order"""
@@ -122,6 +132,33 @@ class FlatGroup:
         self.steps = int(self.step_t.item())
         return {"step": self.steps, "exp_avg": self.logical(self.m_views), "exp_avg_sq": self.logical(self.v_views),
                 "lr": self.lr, "betas": self.betas, "eps": self.eps}
+
+    def torch_state_dict(self):
+        """this group as a ``torch.optim.Adam.state_dict()`` (per-parameter moments in the parameters' own layout, CPU
+        clones): ``torch.optim.Adam(params, ...).load_state_dict(...)`` takes it"""
+        step = int(self.step_t.item())
+        proto = torch.optim.Adam([torch.zeros(1)], lr=self.lr, betas=tuple(self.betas), eps=self.eps).state_dict()
+        pg = dict(proto["param_groups"][0], params=list(range(len(self.params))))
+        state = {i: {"step": torch.tensor(float(step)), "exp_avg": m.detach().cpu().clone().contiguous(),
+                     "exp_avg_sq": v.detach().cpu().clone().contiguous()}
+                 for i, (m, v) in enumerate(zip(self.m_views, self.v_views))}
+        return {"state": state, "param_groups": [pg]}
+
+    def load_torch_state_dict(self, sd):
+        """inverse of ``torch_state_dict`` (also takes the state dict of a ``torch.optim.Adam`` over the same parameters;
+        parameters without state get zero moments); in place, so captured graphs stay valid"""
+        with torch.no_grad():
+            steps = 0
+            for i, (m, v) in enumerate(zip(self.m_views, self.v_views)):
+                st = sd["state"].get(i)
+                if st is None:
+                    m.zero_(), v.zero_()
+                    continue
+                m.copy_(st["exp_avg"].to(m.device))
+                v.copy_(st["exp_avg_sq"].to(v.device))
+                steps = int(st["step"])
+            self.steps = steps
+            self.step_t.fill_(steps)
 
 
 class MnistFamily:
@@ -243,40 +280,6 @@ class _Batch(namedtuple("_Batch", "images c z ahead source index", defaults=(Non
         return (self.images.data_ptr(), tuple(self.images.shape), self.z.data_ptr(), tuple(self.z.shape))
 
 
-class _Graphed:
-    """HIP graphs of one input signature: static copies of the inputs (tensors, dicts of tensors); ``warm`` run on them
-    once on a side stream outside capture (packs, workspace, plans), then ``restore`` (a warm-up is no training step);
-    one graph per ``capture``, on the current stream, all in one pool.  A call copies inputs in and replays in order."""
-
-    def __init__(self, inputs, warm, restore=None):
-        self.inputs = [{k: x.clone() for k, x in v.items()} if isinstance(v, dict) else v.clone() for v in inputs]
-        self.graphs, self.out, self._pool = [], None, torch.cuda.graph_pool_handle()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            warm(*self.inputs)
-        torch.cuda.current_stream().wait_stream(side)
-        if restore is not None:
-            restore()
-
-    def capture(self, fn, *args):
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, pool=self._pool, capture_error_mode="thread_local"):
-            out = fn(*args)
-        self.graphs.append(g)
-        return out
-
-    def load(self, inputs):
-        ops.copy_multi([p for st, v in zip(self.inputs, inputs)
-                        for p in ([(st[k], x) for k, x in v.items()] if isinstance(v, dict) else [(st, v)])])
-
-    def __call__(self, *inputs):
-        self.load(inputs)
-        for g in self.graphs:
-            g.replay()
-        return self.out
-
-
 def _allreduce_now(flat, pg):
     """the collective of the capture pass: synchronous (the ranks' sequences stay aligned), nothing left to wait for"""
     dp.allreduce_sum_(flat, pg)
@@ -318,8 +321,7 @@ class AliStepper:
         self.opt_eg = FlatGroup(list(E.parameters()) + list(G.parameters()), lr, betas, eps, layouts=lay, twin16=t16)
         self.opt_d = FlatGroup(list(D.parameters()), lr, betas, eps, layouts=lay, twin16=t16)
         for pl in self.plans:
-            pl.cache.store.clear()
-            pl.cache.static = True
+            pl.cache.make_static()
         self.pg = process_group
         self.world = torch.distributed.get_world_size(process_group) if process_group is not None else 1
         self.rank = torch.distributed.get_rank(process_group) if process_group is not None else 0
@@ -790,7 +792,7 @@ class AliStepper:
     def _state_tensors(self):
         ts = [self.iter_t]
         for g in (self.opt_eg, self.opt_d):
-            ts += [g.flat, g.m, g.v, g.step_t]
+            ts += g.state_tensors()
         ts += [b for _, b in self.D.named_buffers()]
         return ts
 
@@ -1023,10 +1025,9 @@ class FinetuneStepper:
             raise ValueError(f"metric='ssim' needs images of at least 11x11 (the window), got {self.family.hw}")
         self.pE, self.pG = get_plan(E.layers), get_plan(G.layers)
         self.opt_e = FlatGroup(list(E.parameters()), lr, betas, eps)
-        self.pE.cache.store.clear()
-        self.pE.cache.static = True
+        self.pE.cache.make_static()
         self.capture = capture
-        self._graphs = {}
+        self._graphs = GraphCache()
 
     @torch.no_grad()
     def step(self, x, a):
@@ -1035,25 +1036,11 @@ class FinetuneStepper:
         a = self.family.used(a)
         if not (self.capture and x.is_cuda):
             return self._step(x, a)
-        key = (tuple(x.shape), tuple((k, tuple(v.shape), v.dtype) for k, v in sorted(a.items())), self.E.training,
-               self.G.training)
-        if key not in self._graphs:
-            snap = self._snapshot()
-            ent = _Graphed((x, a), self._step, lambda: self._restore(snap))
-            ent.out = ent.capture(self._step, *ent.inputs)
-            self._graphs[key] = ent
-        return self._graphs[key](x, a)
+        return self._graphs(self._step, (x, a), (self.E.training, self.G.training), self.opt_e.state_tensors(),
+                            self._restored)
 
-    def _state_tensors(self):
-        return [self.opt_e.flat, self.opt_e.m, self.opt_e.v, self.opt_e.step_t]
-
-    def _snapshot(self):
-        return [t.clone() for t in self._state_tensors()]
-
-    def _restore(self, snap):
-        for t, v in zip(self._state_tensors(), snap):
-            t.copy_(v)
-        self.opt_e.steps = int(self.opt_e.step_t.item())
+    def _restored(self):
+        self.opt_e.resync()
         self.pE.cache.refresh()
 
     def _step(self, x, a):
@@ -1104,6 +1091,14 @@ class FinetuneStepper:
         return {"rec": rec, "latent": latent}
 
 
+def mean_of_rounds(out):
+    """``out`` [R, ...] -> the mean over R as the reference loops form it: added in the loop's order, then divided"""
+    acc = out[0]
+    for r in range(1, out.shape[0]):
+        acc = acc + out[r]
+    return acc / out.shape[0] if out.shape[0] > 1 else acc
+
+
 class GeneratorSampler:
     """Generator inference for the ``*_generator_score.py`` loops:
 
@@ -1117,26 +1112,13 @@ class GeneratorSampler:
     def __init__(self, G, capture=True):
         self.G = G
         self.capture = capture
-        self._graphs = {}
-        self._versions = None
-
-    def _sync(self):
-        """Graph replays run no host code, and a re-pack after a weight update lands in new buffers: drop the graphs
-        captured for older parameter versions (inference callers update weights rarely, if ever)."""
-        v = tuple(p._version for p in self.G.parameters())
-        if v != self._versions:
-            self._graphs.clear()
-            self._versions = v
+        self._graphs = GraphCache(modules=[G])
 
     def _forward(self, zs, a):
         R, B = zs.shape[0], zs.shape[1]
         a_rep = {k: v.repeat((R,) + (1,) * (v.dim() - 1)) for k, v in a.items()}
         out = self.G(zs.reshape((R * B,) + tuple(zs.shape[2:])), a_rep)
-        out = out.reshape((R, B) + tuple(out.shape[1:]))
-        gen = out[0]
-        for r in range(1, R):
-            gen = gen + out[r]
-        return gen / R if R > 1 else gen
+        return mean_of_rounds(out.reshape((R, B) + tuple(out.shape[1:])))
 
     @torch.no_grad()
     def __call__(self, zs, a):
@@ -1145,13 +1127,7 @@ class GeneratorSampler:
             zs = zs.unsqueeze(0)
         if not (self.capture and zs.is_cuda):
             return self._forward(zs, a)
-        self._sync()
-        key = (tuple(zs.shape), tuple((k, tuple(v.shape), v.dtype) for k, v in sorted(a.items())), self.G.training)
-        if key not in self._graphs:
-            ent = _Graphed((zs, a), self._forward)
-            ent.out = ent.capture(self._forward, *ent.inputs)
-            self._graphs[key] = ent
-        return self._graphs[key](zs, a)
+        return self._graphs(self._forward, (zs, a), (self.G.training,))
 
 
 def _mnist_family_eg(E, G):

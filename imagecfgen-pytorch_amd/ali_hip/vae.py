@@ -23,7 +23,8 @@ import torch.nn as nn
 from . import ops
 from . import source as _source
 from .chain import chain_backward, chain_forward, get_plan
-from .step import FlatGroup, MnistFamily, SpectFamily, _Graphed, _plane_count
+from .graphs import GraphCache
+from .step import FlatGroup, MnistFamily, SpectFamily, _plane_count, mean_of_rounds
 
 DECODER_LOG_VAR = -5.0          # log-variance of p(x | z) (mnist.py:95, audio_mnist.py:282, whalecalls.py:332)
 
@@ -217,14 +218,6 @@ def elbo(vae, x, c, num_samples=4, kl_weight=1.0, eps=None):
     return ElboFn.apply(core, x, c, int(num_samples), float(kl_weight), eps, params, *params)
 
 
-def _sig(x, extra=()):
-    return (tuple(x.shape), x.dtype) + tuple(extra)
-
-
-def _attr_key(c):
-    return tuple((k,) + _sig(v) for k, v in sorted(c.items()))
-
-
 def elbo_torch(vae, x, c, eps, kl_weight):
     """the stock torch statement with given draws ``eps`` [S, B, L]: (elbo, logp, mean dkl)"""
     from deepscm_vae._vae import gaussian_log_prob
@@ -258,14 +251,13 @@ class VaeStepper:
         self.kl_weight, self.num_samples = float(kl_weight), int(num_samples)
         self.capture = capture
         self.seed = _source.DEFAULT_Z_SEED if seed is None else int(seed)
-        self._graphs = {}
+        self._graphs = GraphCache()
         self.on_device = next(vae.parameters()).is_cuda
         if self.on_device:
             self.core = core_of(vae)
             self.opt = FlatGroup(list(vae.parameters()), lr, betas, eps)
             for plan in self.core.plans():
-                plan.cache.store.clear()
-                plan.cache.static = True
+                plan.cache.make_static()
             self.draws = torch.zeros(1, dtype=torch.int64, device=self.opt.flat.device)   # steps that drew in the kernel
         else:
             self.opt = torch.optim.Adam(vae.parameters(), lr=lr, betas=betas, eps=eps)
@@ -280,25 +272,11 @@ class VaeStepper:
         c = self.core.fam.used(c)
         if not self.capture:
             return self._step(x, c, eps)
-        key = (_sig(x), _attr_key(c), None if eps is None else _sig(eps), self.vae.training)
-        args = (x, c) if eps is None else (x, c, eps)
-        if key not in self._graphs:
-            snap = self._snapshot()
-            ent = _Graphed(args, self._step, lambda: self._restore(snap))
-            ent.out = ent.capture(self._step, *ent.inputs)
-            self._graphs[key] = ent
-        return self._graphs[key](*args)
+        return self._graphs(self._step, (x, c, eps), (self.vae.training,), self.opt.state_tensors() + [self.draws],
+                            self._restored)
 
-    def _state_tensors(self):
-        return [self.opt.flat, self.opt.m, self.opt.v, self.opt.step_t, self.draws]
-
-    def _snapshot(self):
-        return [t.clone() for t in self._state_tensors()]
-
-    def _restore(self, snap):
-        for t, v in zip(self._state_tensors(), snap):
-            t.copy_(v)
-        self.opt.steps = int(self.opt.step_t.item())
+    def _restored(self):
+        self.opt.resync()
         for plan in self.core.plans():
             plan.cache.refresh()
 
@@ -338,7 +316,7 @@ class VaeReconstructor:
     the round), the rounds' latents in one ``ali_vae_latent_fwd`` launch (k = 1: ``sample`` multiplies by
     ``exp(log_var)``), ONE decoder pass over rounds*B rows, the rounds added in the loop's order.  ``eps``
     [rounds, B, L]: the draws; None: drawn in the kernel from the counter stream keyed (seed, call number).  One HIP
-    graph per input shape; graphs of older parameter versions are dropped (``GeneratorSampler._sync``)."""
+    graph per input shape; graphs of older parameter versions are dropped (``GraphCache(modules=...)``)."""
 
     def __init__(self, vae, rounds=32, capture=True, seed=None):
         self.vae = vae
@@ -346,8 +324,7 @@ class VaeReconstructor:
         self.capture = capture
         self.seed = _source.DEFAULT_Z_SEED + 1 if seed is None else int(seed)
         self.calls = None
-        self._graphs = {}
-        self._versions = None
+        self._graphs = GraphCache(modules=[vae])
 
     def _run(self, x, c, c_cf=None, eps=None):
         core = core_of(self.vae)
@@ -361,11 +338,7 @@ class VaeReconstructor:
         xhat, _, _, _, _ = core.decode_rows(mean, lv, R, cond_cf, 1.0, eps, (self.seed, self.calls), False, False)
         if eps is None:
             ops.add_i64_multi([self.calls], [1])
-        out = xhat.reshape((R, B, 1) + tuple(fam.hw))
-        rec = out[0]
-        for r in range(1, R):
-            rec = rec + out[r]
-        return rec / R if R > 1 else rec
+        return mean_of_rounds(xhat.reshape((R, B, 1) + tuple(fam.hw)))
 
     def _run_torch(self, x, c, c_cf, eps):
         enc, dec = self.vae.encoder, self.vae.decoder
@@ -387,25 +360,5 @@ class VaeReconstructor:
             self.calls = torch.zeros(1, dtype=torch.int64, device=x.device)
         if not self.capture:
             return self._run(x, c, c_cf, eps)
-        v = tuple(p._version for p in self.vae.parameters())
-        if v != self._versions:
-            self._graphs.clear()
-            self._versions = v
-        key = (_sig(x), _attr_key(c), None if c_cf is None else _attr_key(c_cf), None if eps is None else _sig(eps),
-               self.vae.training)
-        args = [x, c] + ([c_cf] if c_cf is not None else []) + ([eps] if eps is not None else [])
-        has_cf, has_eps = c_cf is not None, eps is not None
-
-        def run(*a):
-            a = list(a)
-            xx, cc = a[0], a[1]
-            cf = a[2] if has_cf else None
-            ee = a[-1] if has_eps else None
-            return self._run(xx, cc, cf, ee)
-
-        if key not in self._graphs:
-            snap = self.calls.clone()
-            ent = _Graphed(args, run, lambda: self.calls.copy_(snap))
-            ent.out = ent.capture(run, *ent.inputs)
-            self._graphs[key] = ent
-        return self._graphs[key](*args)
+        # (state: the warm-up pass is no call of the counter stream)
+        return self._graphs(self._run, (x, c, c_cf, eps), (self.vae.training,), [self.calls])
