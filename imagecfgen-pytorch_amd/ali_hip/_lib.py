@@ -5,7 +5,7 @@ The library is the product: if it cannot be loaded every GPU entry point raises
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int32, c_int64, c_size_t, c_uint64, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int32, c_int64, c_size_t, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libali_hip.so")
@@ -40,6 +40,11 @@ class AliWgradFold(Structure):
 
 class AliWgradJob(Structure):
     _fields_ = [("opaque", c_uint64 * 40)]
+
+
+class AliCfSegment(Structure):
+    _fields_ = [("kind", c_int32), ("width", c_int32), ("src_off", c_int32), ("dst_off", c_int32), ("table", c_int32),
+                ("attr_off", c_int32)]
 
 
 class AliGemmJob(Structure):
@@ -108,6 +113,19 @@ SIGNATURES = {
                                 c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "ali_vae_latent_bwd": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
                                     c_float, c_float, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    "ali_row_dist": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_size_t,
+                              c_void_p]),
+    "ali_cf_hinge": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int32, c_int32, c_void_p, c_void_p,
+                              c_void_p]),
+    "ali_cf_join": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p, c_void_p]),
+    "ali_cf_input_fwd": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, POINTER(AliCfSegment), c_int32,
+                                  POINTER(c_void_p), c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32,
+                                  c_void_p]),
+    "ali_cf_input_step": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, POINTER(AliCfSegment), c_int32,
+                                   POINTER(c_void_p), c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
+                                   c_void_p, c_double, c_double, c_double, c_double, c_void_p, c_void_p]),
+    "ali_cf_select": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                               c_void_p]),
     "ali_bce_logits_pair": (c_int32, [c_void_p, c_int32, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     "ali_gp_mix": (c_int32, [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_int32, c_int64, c_void_p,
                             c_void_p, c_void_p]),

@@ -1416,3 +1416,151 @@ def vae_latent_bwd(gin, eps, mean, log_var, S, gmean, glog_var, k=0.5, kl_weight
                                       _row_view(glog_var, L, "glog_var"), gmean.stride(0), ncond, _opt(gcond),
                                       _stream()), "ali_vae_latent_bwd")
     return gcond
+
+
+# ---------------------------------------------------------------------- the counterfactual explainers (csrc/explain.hip)
+DIST_L1, DIST_L2 = 0, 1
+CF_COPY, CF_TANH, CF_SOFTMAX = 0, 1, 2
+CF_EMB = 256
+
+
+def _i32(t, name, n=None):
+    if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and (n is None or t.numel() == n)):
+        raise ValueError(f"{name}: need a contiguous int32 CUDA tensor" + ("" if n is None else f" of {n} elements"))
+    return c_void_p(t.data_ptr())
+
+
+def row_dist(x, y, mode=DIST_L1, out=None):
+    """out[s] = mean_n |y[s, n] - x[s or 0, n]| (``DIST_L1``) or the mean of the squares (``DIST_L2``); x: [1 or S, ...],
+    y: [S, ...], rows flattened (include/ali_hip.h: ali_row_dist)."""
+    lib = _lib.load()
+    S = y.shape[0]
+    N = y.numel() // max(S, 1)
+    if x.shape[0] not in (1, S) or x.numel() != x.shape[0] * N:
+        raise ValueError(f"row_dist: x {tuple(x.shape)} is neither one row nor one row per row of y {tuple(y.shape)}")
+    if out is None:
+        out = torch.empty(S, dtype=torch.float32, device=y.device)
+    ws = workspace(y.device)
+    _lib.check(lib.ali_row_dist(_chk(x, "x"), x.shape[0], _chk(y, "y"), S, N, int(mode), _chk(out, "out"),
+                                c_void_p(ws.data_ptr()), ws.numel(), _stream()), "ali_row_dist")
+    return out
+
+
+def cf_hinge(logit, target, m, c, orig_pred=None, want_grad=True, out=None, glogit=None):
+    """Per-row loss of the hinge explainer (include/ali_hip.h: ali_cf_hinge): logit [B, C], target [B] int32 (< 0: the
+    row compares with ``orig_pred`` [B, C] instead), m [B].  Returns (out [B, 3] = (c*h + m, h, m), glogit or None)."""
+    lib = _lib.load()
+    if logit.dim() != 2:
+        raise ValueError(f"cf_hinge: need [B, C] logits, got {tuple(logit.shape)}")
+    B, C = logit.shape
+    if orig_pred is not None and orig_pred.shape != logit.shape:
+        raise ValueError("cf_hinge: orig_pred must have the logits' shape")
+    if m.numel() != B:
+        raise ValueError("cf_hinge: one m per row")
+    if out is None:
+        out = torch.empty(B, 3, dtype=torch.float32, device=logit.device)
+    if glogit is None and want_grad:
+        glogit = torch.empty_like(logit)
+    _lib.check(lib.ali_cf_hinge(_chk(logit, "logit"), _i32(target, "target", B), _opt(orig_pred, "orig_pred"),
+                                _chk(m, "m"), float(c), B, C, _chk(out, "out"), _opt(glogit, "glogit"), _stream()),
+               "ali_cf_hinge")
+    return out, glogit
+
+
+def cf_join(gx_clf, x_cf, x, out=None):
+    """gy [B, N] = gx_clf[..., 0] + sign(x_cf - x) / N: the classifier's NHWC input gradient [B, H, W, Cpad] joined with
+    the gradient of mean |x - x_cf| (include/ali_hip.h: ali_cf_join); x: [B or 1, N]."""
+    lib = _lib.load()
+    B = x_cf.shape[0]
+    N = x_cf.numel() // B
+    if gx_clf.numel() % (B * N) or x.numel() not in (N, B * N):
+        raise ValueError(f"cf_join: gx_clf {tuple(gx_clf.shape)}, x_cf {tuple(x_cf.shape)} and x {tuple(x.shape)} "
+                         "do not belong together")
+    if out is None:
+        out = torch.empty(B, N, dtype=torch.float32, device=x_cf.device)
+    _lib.check(lib.ali_cf_join(_chk(gx_clf, "gx_clf"), gx_clf.numel() // (B * N), _chk(x_cf, "x_cf"), _chk(x, "x"),
+                               x.numel() // N, B, N, _chk(out, "out"), _stream()), "ali_cf_join")
+    return out
+
+
+class CfLayout:
+    """The segment table of ``cf_input_fwd`` / ``cf_input_step`` (include/ali_hip.h: AliCfSegment): ``segments`` is a
+    list of (kind, width, src_off, dst_off, table index or -1, attr_off or -1); ``tables`` the embedding tables
+    ([width, 256] fp32 CUDA) the indices name; ``n_log`` / ``ld`` the logical and padded width of the generator's
+    input row.  The widths of the raw, given and attribute rows follow from the segments."""
+
+    def __init__(self, segments, tables, n_log, ld):
+        self.segments = [tuple(int(v) for v in s) for s in segments]
+        self.tables = list(tables)
+        self.n_log, self.ld = int(n_log), int(ld)
+        self.raw_ld = max([s[2] + s[1] for s in self.segments if s[0] != CF_COPY], default=0)
+        self.given_ld = max([s[2] + s[1] for s in self.segments if s[0] == CF_COPY], default=0)
+        self.attrs_ld = max([s[5] + s[1] for s in self.segments if s[5] >= 0], default=0)
+        self._segs = (_lib.AliCfSegment * max(len(self.segments), 1))(*[_lib.AliCfSegment(*s) for s in self.segments])
+        for t in self.tables:
+            _chk(t, "embedding table")
+        for s in self.segments:
+            if s[4] >= 0 and (s[4] >= len(self.tables) or tuple(self.tables[s[4]].shape) != (s[1], CF_EMB)):
+                raise ValueError(f"CfLayout: segment {s} needs table {s[4]} of shape ({s[1]}, {CF_EMB})")
+        self._tabs = (c_void_p * max(len(self.tables), 1))(*[t.data_ptr() for t in self.tables])
+
+
+def _rows(t, ld, name, B=None):
+    if t is None:
+        if ld:
+            raise ValueError(f"{name}: the layout needs {ld} columns")
+        return None
+    if t.dim() != 2 or t.shape[1] != ld or (B is not None and t.shape[0] != B):
+        raise ValueError(f"{name}: need [B, {ld}] rows, got {tuple(t.shape)}")
+    return _chk(t, name)
+
+
+def cf_input_fwd(lay: CfLayout, raw, given, rows=None, attrs=None):
+    """Raw variables [B, raw_ld] (and the given columns [B, given_ld]) -> (generator input rows [B, ld], transformed
+    attribute rows [B, attrs_ld]) in one launch (include/ali_hip.h: ali_cf_input_fwd)."""
+    lib = _lib.load()
+    some = raw if raw is not None else given
+    B = some.shape[0]
+    if rows is None:
+        rows = torch.empty(B, lay.ld, dtype=torch.float32, device=some.device)
+    if attrs is None:
+        attrs = torch.empty(B, lay.attrs_ld, dtype=torch.float32, device=some.device)
+    _lib.check(lib.ali_cf_input_fwd(_rows(raw, lay.raw_ld, "raw", B), lay.raw_ld, _rows(given, lay.given_ld, "given", B),
+                                    lay.given_ld, lay._segs, len(lay.segments), lay._tabs, len(lay.tables), B, lay.n_log,
+                                    lay.ld, _rows(rows, lay.ld, "rows", B), _rows(attrs, lay.attrs_ld, "attrs", B),
+                                    lay.attrs_ld, _stream()), "ali_cf_input_fwd")
+    return rows, attrs
+
+
+def cf_input_step(lay: CfLayout, g_rows, rows, attrs, raw, m, v, step, lr, betas=(0.9, 0.999), eps=1e-8, graw=None):
+    """Backward of ``cf_input_fwd`` from the input rows' gradient and torch.optim.Adam's update of ``raw`` (moments
+    ``m`` / ``v``, per-row int32 counters ``step`` of completed steps) in one launch (include/ali_hip.h:
+    ali_cf_input_step).  ``graw`` (optional [B, raw_ld]) receives the gradient of the trained columns."""
+    lib = _lib.load()
+    B = raw.shape[0]
+    _lib.check(lib.ali_cf_input_step(_rows(g_rows, lay.ld, "g_rows", B), lay.ld, _rows(rows, lay.ld, "rows", B),
+                                     _rows(attrs, lay.attrs_ld, "attrs", B), lay.attrs_ld, lay._segs, len(lay.segments),
+                                     lay._tabs, len(lay.tables), B, _rows(raw, lay.raw_ld, "raw", B),
+                                     _rows(m, lay.raw_ld, "m", B), _rows(v, lay.raw_ld, "v", B), lay.raw_ld, lay.given_ld,
+                                     _i32(step, "step", B), float(lr), float(betas[0]), float(betas[1]), float(eps),
+                                     None if graw is None else _rows(graw, lay.raw_ld, "graw", B), _stream()),
+               "ali_cf_input_step")
+
+
+def cf_select(logit, metric, target, pred=None, order=None, n_hit=None):
+    """Tail of the mixture sweep (include/ali_hip.h: ali_cf_select): logit [S, C], metric [S], target a one-element
+    int32 device tensor.  Returns (pred [S], order [S], n_hit [1]) int32 device tensors: the first-maximum class per
+    row, the rows with pred == target by ascending metric (stable) followed by the other rows, and their number."""
+    lib = _lib.load()
+    if logit.dim() != 2 or metric.numel() != logit.shape[0]:
+        raise ValueError(f"cf_select: need [S, C] logits and S metric values, got {tuple(logit.shape)} and "
+                         f"{tuple(metric.shape)}")
+    S, C = logit.shape
+    dev = logit.device
+    pred = torch.empty(S, dtype=torch.int32, device=dev) if pred is None else pred
+    order = torch.empty(S, dtype=torch.int32, device=dev) if order is None else order
+    n_hit = torch.empty(1, dtype=torch.int32, device=dev) if n_hit is None else n_hit
+    _lib.check(lib.ali_cf_select(_chk(logit, "logit"), _chk(metric, "metric"), _i32(target, "target", 1), S, C,
+                                 _i32(pred, "pred", S), _i32(order, "order", S), _i32(n_hit, "n_hit", 1), _stream()),
+               "ali_cf_select")
+    return pred, order, n_hit

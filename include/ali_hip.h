@@ -390,6 +390,76 @@ int ali_vae_latent_bwd(const float* gin, int32_t ld, const float* eps, const flo
                        int32_t head_ld, int32_t S, int32_t B, int32_t L, float k, float kl_weight, const float* kl_scale,
                        float* gmean, float* glog_var, int32_t gld, int32_t ncond, float* gcond, ali_stream_t stream);
 
+/* The counterfactual explainers (explain/cf_example.py); csrc/explain.hip.  Row arithmetic in fp64, fixed reduction
+ * order, no float atomics (bit-identical from run to run), no host reads and no allocation: every launch can be recorded
+ * into a HIP graph.  Arguments are checked before the launch (ALI_ERR_BAD_ARG, message in ali_last_error).
+ *
+ * ali_row_dist: out[s] = mean_n |y[s][n] - x[s or 0][n]| (ALI_DIST_L1) or the mean of the squares (ALI_DIST_L2);
+ *   x: [xB][N] with xB in {1, S} (1: the one row is compared with every row of y), y: [S][N], 1 <= S <= 65535.  A row is
+ *   split over min(ceil(N / 4096), 64) blocks; ws >= ALI_WS_RESERVED + 8 * S * that many bytes; the arrival counter is
+ *   the last int of the reserved head and is left at zero.  The `mse` metric of the sweep and the
+ *   `(x - x_).abs().mean()` term of the hinge loop (cf_example.py:14,121).
+ * ali_cf_hinge: the per-row loss of HingeLossCFExplainer (cf_example.py:111-122); logit [B][C], 2 <= C <= 4096,
+ *   target [B] int32, m [B], out3 [B][3] = (c * h + m, h, m), glogit [B][C] (optional) = d (c * h) / d logit.
+ *   target[b] >= 0: h = max_{i != t} logit[i] - logit[t]; the maximum is the FIRST one (the strict `>` of
+ *   max_excluding); glogit = +c there, -c at t, 0 elsewhere.  target[b] < 0: h = mean_i (logit[i] - orig_pred[b][i])^2,
+ *   glogit = 2 c (logit - orig_pred) / C (orig_pred: the softmax row the reference compares the logits with).  Rows are
+ *   independent explanations: nothing is averaged over B.  A target >= C, or target < 0 with orig_pred NULL, gives
+ *   h = NaN and a zero gradient row.
+ * ali_cf_join: gy[b][n] = gx_clf[b][n][0] + sign(x_cf[b][n] - x[b or 0][n]) / N -- plane 0 of the classifier's
+ *   NHWC input gradient ([B][N][cpad]) plus the gradient of mean |x - x_cf| (sign(0) = 0, 1 / N as an fp32 division:
+ *   exactly torch's fp32 statement); 1 <= N < 2^24, xB in {1, B}.
+ * ali_cf_input_fwd: raw optimisation variables -> the generator's input rows (the layout of ali_g_input) and the
+ *   transformed attribute rows, one launch, one block per row.  A segment table describes the row: segment q takes
+ *   `width` values at column src_off of raw (ALI_CF_TANH, ALI_CF_SOFTMAX: trained) or of given (ALI_CF_COPY: an ignored
+ *   feature, or the encoder's codes), transforms them (tanh / softmax over the segment / nothing), stores them at
+ *   column attr_off of attrs_out (attr_off < 0: not stored) and writes them to columns dst_off.. of the row (table < 0)
+ *   or their product with tables[table] ([width][256], summed over the classes in ascending order) to the 256 columns
+ *   at dst_off.  Columns [n_log, ld) become 0.  At most ALI_CF_MAX_SEGMENTS segments; softmax / table segments are at
+ *   most 1024 wide and need attr_off >= 0 when they go through a table.
+ * ali_cf_input_step: the backward of that map and torch.optim.Adam's update of the trained variables (bias corrected,
+ *   eps outside the square root, no decay) in one launch, one block per row.  g_rows [B][ld]: the gradient of the input
+ *   rows; rows / attrs: what ali_cf_input_fwd left.  Gradient of the transformed values: g_rows[dst_off + i], or
+ *   <g_rows[dst_off .. dst_off + 256), tables[table][k]>; then g * (1 - t^2) (tanh) or the softmax Jacobian
+ *   p_k (g_k - sum_j p_j g_j).  raw, m, v: [B][raw_ld]; step [B] int32 counts COMPLETED steps per row: the row's block
+ *   reads it, runs step + 1 and stores that back.  graw (optional, [B][raw_ld]): the gradient of the trained columns.
+ *   lr, beta1, beta2, eps are doubles, as torch.optim.Adam holds them.
+ * ali_cf_select: the tail of DeepCounterfactualExplainer's sweep (cf_example.py:53,64-69): pred[s] = first maximum of
+ *   logit[s] ([S][C], S <= 1024, C <= 4096), hit = pred[s] == *target (device int32), order = the hit rows by ascending
+ *   metric (ties: ascending row; NaN behind every number, torch.argsort's stable order) followed by the other rows in
+ *   row order, *n_hit = the number of hit rows.  One block, rank by counting.  A NaN logit never becomes the prediction
+ *   (torch.argmax would pick it). */
+#define ALI_DIST_L1 0
+#define ALI_DIST_L2 1
+#define ALI_CF_COPY 0
+#define ALI_CF_TANH 1
+#define ALI_CF_SOFTMAX 2
+#define ALI_CF_MAX_SEGMENTS 16
+#define ALI_CF_EMB 256
+typedef struct {
+  int32_t kind;      /* ALI_CF_COPY / ALI_CF_TANH / ALI_CF_SOFTMAX */
+  int32_t width;
+  int32_t src_off;   /* column of raw (trained) or of given (ALI_CF_COPY) */
+  int32_t dst_off;   /* column of the generator's input row */
+  int32_t table;     /* >= 0: through tables[table] into ALI_CF_EMB columns; < 0: width columns, directly */
+  int32_t attr_off;  /* column of the attribute rows; < 0: not kept (z) */
+} AliCfSegment;
+int ali_row_dist(const float* x, int32_t xB, const float* y, int32_t S, int64_t N, int32_t mode, float* out, void* ws,
+                 size_t ws_bytes, ali_stream_t stream);
+int ali_cf_hinge(const float* logit, const int32_t* target, const float* orig_pred, const float* m, float c, int32_t B,
+                 int32_t C, float* out3, float* glogit, ali_stream_t stream);
+int ali_cf_join(const float* gx_clf, int32_t cpad, const float* x_cf, const float* x, int32_t xB, int32_t B, int64_t N,
+                float* gy, ali_stream_t stream);
+int ali_cf_input_fwd(const float* raw, int32_t raw_ld, const float* given, int32_t given_ld, const AliCfSegment* segs,
+                     int32_t n_seg, const float* const* tables, int32_t n_tables, int32_t B, int32_t n_log, int32_t ld,
+                     float* rows, float* attrs_out, int32_t attrs_ld, ali_stream_t stream);
+int ali_cf_input_step(const float* g_rows, int32_t ld, const float* rows, const float* attrs, int32_t attrs_ld,
+                      const AliCfSegment* segs, int32_t n_seg, const float* const* tables, int32_t n_tables, int32_t B,
+                      float* raw, float* m, float* v, int32_t raw_ld, int32_t given_ld, int32_t* step, double lr,
+                      double beta1, double beta2, double eps, float* graw, ali_stream_t stream);
+int ali_cf_select(const float* logit, const float* metric, const int32_t* target, int32_t S, int32_t C, int32_t* pred,
+                  int32_t* order, int32_t* n_hit, ali_stream_t stream);
+
 /* torch.optim.Adam step (mnist.py:176-179,230,236,241), no amsgrad / decay.
  * One launch over a flat parameter segment.  The 1-based step count is `step`, or *dev_step when
  * dev_step != NULL (graph replays); the gradient is read as grad_scale * g (1/world for DP).
