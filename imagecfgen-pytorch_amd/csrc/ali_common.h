@@ -71,6 +71,10 @@ constexpr size_t kWsReserved = ALI_WS_RESERVED;
 inline void* ws_payload(void* ws) { return ws ? static_cast<char*>(ws) + kWsReserved : nullptr; }
 inline size_t ws_payload_bytes(size_t bytes) { return bytes > kWsReserved ? bytes - kWsReserved : 0; }
 
+// entry points: the ABI's stream handle as HIP's, and whether a base pointer allows 16-byte accesses
+#define ST(s) ((hipStream_t)(s))
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 // splitmix64's finaliser: the hash of the counter RNG (Dropout2d masks, latents: elementwise.hip; Griffin-Lim phases:
 // griffinlim.hip).  A stream's key is mix64(mix64(seed) ^ counter * kCounterMul), one more round per stream constant.
 constexpr uint64_t kCounterMul = 0xD1B54A32D192ED03ull;

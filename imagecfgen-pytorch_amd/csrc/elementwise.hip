@@ -595,7 +595,6 @@ bn_bwd_apply_vec_kernel(const float* __restrict__ x, const float* __restrict__ g
   }
 }
 
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 static bool vec_ok(long long rows, int C) {
   return (C % 4) == 0 && C >= 4 && C <= 4 * kEwBlock && rows * C < (1LL << 31);
 }
@@ -1126,7 +1125,6 @@ batch_gather_kernel(const void* __restrict__ images, int images_u8, int vec, con
 }  // namespace ali
 
 using namespace ali;
-#define ST(s) ((hipStream_t)(s))
 
 extern "C" int ali_pack_weights(const float* src, float* dst, int32_t N, int32_t T, int32_t C, int32_t Cpad,
                                 int64_t s_n, int64_t s_tap, int64_t s_c, ali_stream_t stream) {

@@ -3,9 +3,9 @@
 // classifier's conv chains in one step of HingeLossCFExplainer.explain and at the tail of
 // DeepCounterfactualExplainer.explain's sweep.  Every one of them is launch bound at the callers' sizes (batch 1 .. 64,
 // 10-class logits, 28x28 .. 128x128 images), so the row arithmetic is fp64 -- every fp32 result is the rounding of an
-// fp64 evaluation -- and every reduction runs in a fixed order: lanes -> xor butterfly (a + b == b + a bit for bit, all
-// lanes agree) -> waves 0..3 in order -> blocks in block order.  No float atomics, no host reads, no allocation: the
-// same inputs give the same bits, and every launch can be recorded into a HIP graph.
+// fp64 evaluation -- and every reduction runs in a fixed order (ali_reduce.h): lanes -> waves 0..3 in order -> blocks in
+// block order.  No float atomics, no host reads, no allocation: the same inputs give the same bits, and every launch can
+// be recorded into a HIP graph.
 //
 // NaN (what falls out, untested unless said otherwise):
 //   ali_row_dist    a NaN element makes its row's distance NaN.
@@ -15,7 +15,7 @@
 //   ali_cf_join     a NaN difference gives a NaN gradient entry (torch.sign(NaN) is NaN).
 //   ali_cf_select   a NaN logit never becomes the prediction (torch.argmax would pick it); NaN metrics sort behind every
 //                   number among the hits, in row order among themselves -- torch.argsort's order (tested).
-#include "ali_common.h"
+#include "ali_reduce.h"
 
 #include <limits.h>
 #include <string.h>
@@ -26,52 +26,8 @@ constexpr int kCfBlock = 256;
 constexpr int kCfWaves = kCfBlock / 64;
 constexpr int kDistChunk = 4096;                                     // elements of a row one block adds up
 constexpr int kDistMaxSplit = 64;
-constexpr int kDistCtr = (int)(kWsReserved / sizeof(int)) - 1;       // the arrival counter softmax_xent_kernel uses
 constexpr int kCfMaxCat = 1024;                                      // widest segment that goes through LDS
 constexpr int kSelMax = 1024;
-
-__device__ __forceinline__ double cf_wave_sum(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
-__device__ __forceinline__ float cf_wave_max(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
-  return v;
-}
-
-__device__ __forceinline__ void cf_wave_argmax(float& v, int& i) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    const float ov = __shfl_xor(v, m, 64);
-    const int oi = __shfl_xor(i, m, 64);
-    if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
-  }
-}
-
-// sum over the block (kCfBlock threads): waves in order; every thread gets the same value.  `s` holds kCfWaves doubles
-// and is free again when the call returns.
-__device__ __forceinline__ double cf_block_sum(double v, double* s) {
-  v = cf_wave_sum(v);
-  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = 0.0;
-  for (int w = 0; w < kCfWaves; ++w) t += s[w];
-  __syncthreads();
-  return t;
-}
-
-__device__ __forceinline__ float cf_block_max(float v, double* s) {
-  v = cf_wave_max(v);
-  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = (double)v;
-  __syncthreads();
-  float t = -INFINITY;
-  for (int w = 0; w < kCfWaves; ++w) t = fmaxf(t, (float)s[w]);
-  __syncthreads();
-  return t;
-}
 
 // ---------------------------------------------------------------------------------------------------- ali_row_dist
 // grid (split, S): block (k, s) adds elements [k * chunk, (k + 1) * chunk) of row s; the block that arrives last at the
@@ -92,25 +48,12 @@ row_dist_kernel(const float* __restrict__ x, int xB, const float* __restrict__ y
     const double d = (double)yr[n] - (double)xr[n];
     acc += mode == ALI_DIST_L1 ? fabs(d) : d * d;
   }
-  acc = cf_block_sum(acc, s_red);
-  if (threadIdx.x == 0) {
-    // write-through (device-scope) store, drained before the arrival: the reducer's device-scope loads see it on
-    // whichever XCD it runs (the protocol of softmax_xent_kernel)
-    __hip_atomic_store(&part[(long long)s * split + k], (unsigned long long)__double_as_longlong(acc), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const int total = (int)(gridDim.x * gridDim.y);
-    const int arrived = __hip_atomic_fetch_add(ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s_last = arrived == total - 1;
-    if (s_last) __hip_atomic_store(ctr, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // all blocks have arrived
-  }
-  __syncthreads();
-  if (!s_last) return;
+  acc = block_sum<kCfWaves>(acc, s_red);
+  if (threadIdx.x == 0) partial_store(&part[(long long)s * split + k], acc);
+  if (!arrive_last(ctr, (int)(gridDim.x * gridDim.y), &s_last)) return;
   for (int r = threadIdx.x; r < S; r += kCfBlock) {
     double total = 0.0;
-    for (int i = 0; i < split; ++i)                    // block order, whichever block this is
-      total += __longlong_as_double((long long)__hip_atomic_load(&part[(long long)r * split + i], __ATOMIC_RELAXED,
-                                                                 __HIP_MEMORY_SCOPE_AGENT));
+    for (int i = 0; i < split; ++i) total += partial_load(&part[(long long)r * split + i]);   // block order
     out[r] = (float)(total / (double)N);
   }
 }
@@ -136,7 +79,7 @@ cf_hinge_kernel(const float* __restrict__ logit, const int* __restrict__ target,
       const float zv = z[j];
       if (j != t && zv > best) { best = zv; bi = j; }
     }
-    cf_wave_argmax(best, bi);
+    wave_argmax(best, bi);
     const bool ok = t < C;                            // (a target past the row: h = NaN, no gradient)
     h = ok ? (double)best - (double)z[t] : (double)NAN;
     if (g)
@@ -150,7 +93,7 @@ cf_hinge_kernel(const float* __restrict__ logit, const int* __restrict__ target,
       acc += d * d;
       if (g) g[j] = (float)(gs * d);
     }
-    h = cf_wave_sum(acc) / (double)C;
+    h = wave_sum(acc) / (double)C;
   } else {                                            // (no target and nothing to compare with)
     h = (double)NAN;
     if (g)
@@ -189,6 +132,7 @@ cf_input_fwd_kernel(const float* __restrict__ raw, int raw_ld, const float* __re
                     int n_log, int ld, float* __restrict__ rows, float* __restrict__ attrs, int attrs_ld) {
   __shared__ double s_p[kCfMaxCat];
   __shared__ double s_red[kCfWaves];
+  __shared__ float s_max[kCfWaves];
   const int b = blockIdx.x, tid = threadIdx.x;
   float* row = rows + (long long)b * ld;
   float* arow = attrs ? attrs + (long long)b * attrs_ld : nullptr;
@@ -208,14 +152,14 @@ cf_input_fwd_kernel(const float* __restrict__ raw, int raw_ld, const float* __re
     if (s.kind == ALI_CF_SOFTMAX) {
       float mx = -INFINITY;
       for (int i = tid; i < s.width; i += kCfBlock) mx = fmaxf(mx, src[i]);
-      mx = cf_block_max(mx, s_red);
+      mx = block_max<kCfWaves>(mx, s_max);
       double e = 0.0;
       for (int i = tid; i < s.width; i += kCfBlock) {
         const double ev = exp((double)src[i] - (double)mx);
         s_p[i] = ev;
         e += ev;
       }
-      e = cf_block_sum(e, s_red);
+      e = block_sum<kCfWaves>(e, s_red);
       for (int i = tid; i < s.width; i += kCfBlock) s_p[i] = s_p[i] / e;     // (the thread's own entries)
     } else {
       for (int i = tid; i < s.width; i += kCfBlock)
@@ -286,7 +230,7 @@ cf_input_step_kernel(const float* __restrict__ g_rows, int ld, const float* __re
         double acc = 0.0;
         for (int j = lane; j < ALI_CF_EMB; j += 64)
           acc += (double)grow[s.dst_off + j] * (double)tab[(long long)k * ALI_CF_EMB + j];
-        acc = cf_wave_sum(acc);
+        acc = wave_sum(acc);
         if (lane == 0) s_g[k] = acc;
       }
     } else {
@@ -423,14 +367,12 @@ extern "C" int ali_row_dist(const float* x, int32_t xB, const float* y, int32_t 
   long long split = (N + kDistChunk - 1) / kDistChunk;
   if (split > kDistMaxSplit) split = kDistMaxSplit;
   const long long chunk = (N + split - 1) / split;
-  const size_t need = (size_t)S * (size_t)split * sizeof(unsigned long long);
-  if (!ws || ws_payload_bytes(ws_bytes) < need) {
-    set_error("ali_row_dist: workspace too small (%zu bytes behind the reserved head needed)", need);
-    return ALI_ERR_WORKSPACE;
-  }
-  hipLaunchKernelGGL(row_dist_kernel, dim3((unsigned)split, (unsigned)S), dim3(kCfBlock), 0, (hipStream_t)stream, x,
-                     (int)xB, y, (int)S, (long long)N, chunk, (int)mode, out,
-                     reinterpret_cast<unsigned long long*>(ws_payload(ws)), reinterpret_cast<int*>(ws) + kDistCtr);
+  unsigned long long* part;
+  int* ctr;
+  const int rc = fold_workspace("ali_row_dist", ws, ws_bytes, (size_t)S * (size_t)split, &part, &ctr);
+  if (rc != ALI_OK) return rc;
+  hipLaunchKernelGGL(row_dist_kernel, dim3((unsigned)split, (unsigned)S), dim3(kCfBlock), 0, ST(stream), x, (int)xB, y,
+                     (int)S, (long long)N, chunk, (int)mode, out, part, ctr);
   return check_launch("row_dist_kernel");
 }
 

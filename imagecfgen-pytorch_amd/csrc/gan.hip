@@ -9,27 +9,19 @@
 // At the sizes the callers have (B = 64 images of 128 x 128 floats: 4 MB per operand) all three are bound by launch and
 // memory latency, not by bandwidth: one block per image (penalty) or a few per image (mix), 16-byte accesses where the
 // row length and the pointers allow them, everything else one element at a time.
-// Reductions are fp64 in a fixed order -- elements thread-strided, lanes by xor butterfly (a + b == b + a bit for bit),
-// waves in order, images in order by the block that arrives last -- without float atomics: the same inputs give the
-// same bits on every run.  The arrival counter is the last int of the workspace's reserved head (zero between launches)
-// and is left at zero.  The scalars are written by one thread with ordinary vector stores.
-#include "ali_common.h"
+// Reductions are fp64 in a fixed order (ali_reduce.h, the hand-off between blocks included): elements thread-strided,
+// lanes, waves in order, images in order by thread 0 of the block that arrives last.  wgan_critic_kernel is one block
+// with an LDS tree of its own.  The scalars are written by one thread with ordinary vector stores.
+#include "ali_reduce.h"
 
 namespace ali {
 
 constexpr int kGpThreads = 1024;
 constexpr int kGpWaves = kGpThreads / 64;
 constexpr int kMixThreads = 256;
-constexpr int kGanCtr = (int)(kWsReserved / sizeof(int)) - 1;
 constexpr uint64_t kGpStream = 0x47504D4958455053ull;     // one more mix64 round over the latent key: eps is a stream of its own
 
 struct GpPart { unsigned long long pen_bits; unsigned long long norm_bits; };
-
-__device__ __forceinline__ double gan_wave_sum(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
 
 // uniform in [0, 1): the top 24 bits of the hash of image g under the stream's key
 __device__ __forceinline__ float gp_uniform(uint64_t key, uint64_t g) {
@@ -83,9 +75,8 @@ __global__ void __launch_bounds__(kGpThreads)
 gp_penalty_kernel(const float* g0, int B, long long P, float lambda, float* __restrict__ out2, float* v, GpPart* part,
                   int* ctr, int vec) {
   __shared__ double s_w[kGpWaves];
-  __shared__ double s_norm;
   __shared__ int s_last;
-  const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int b = blockIdx.x, t = threadIdx.x;
   const float* g = g0 + (long long)b * P;
   float* o = v ? v + (long long)b * P : nullptr;
   double ss = 0.0;
@@ -101,16 +92,7 @@ gp_penalty_kernel(const float* g0, int B, long long P, float lambda, float* __re
   } else {
     for (long long i = t; i < P; i += kGpThreads) { const float a = g[i]; ss += (double)a * a; }
   }
-  ss = gan_wave_sum(ss);
-  if (lane == 0) s_w[wave] = ss;
-  __syncthreads();
-  if (t == 0) {
-    double tot = 0.0;
-    for (int w = 0; w < kGpWaves; ++w) tot += s_w[w];
-    s_norm = sqrt(tot);
-  }
-  __syncthreads();
-  const double n = s_norm;
+  const double n = sqrt(block_sum<kGpWaves>(ss, s_w));       // (its barriers: the norm pass is complete)
   if (o) {
     // d/dg (n - 1)^2 / B = (2 / B) (n - 1) g / n; at n == 0 the subgradient 0, as torch's norm backward
     const float sc = n > 0.0 ? (float)((double)lambda * (2.0 / (double)B) * (1.0 - 1.0 / n)) : 0.f;
@@ -126,26 +108,14 @@ gp_penalty_kernel(const float* g0, int B, long long P, float lambda, float* __re
     }
   }
   if (t == 0) {
-    const double pen = (n - 1.0) * (n - 1.0);
-    // write-through (device-scope) stores, drained before the arrival: the reducer's device-scope loads see them on
-    // whichever XCD it runs
-    __hip_atomic_store(&part[b].pen_bits, (unsigned long long)__double_as_longlong(pen), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(&part[b].norm_bits, (unsigned long long)__double_as_longlong(n), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const int arrived = __hip_atomic_fetch_add(ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s_last = arrived == (int)gridDim.x - 1;
-    if (s_last) __hip_atomic_store(ctr, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // all blocks have arrived
+    partial_store(&part[b].pen_bits, (n - 1.0) * (n - 1.0));
+    partial_store(&part[b].norm_bits, n);
   }
-  __syncthreads();
-  if (!s_last || t != 0) return;
+  if (!arrive_last(ctr, (int)gridDim.x, &s_last) || t != 0) return;
   double pen = 0.0, nrm = 0.0;
   for (int i = 0; i < B; ++i) {                    // image order, whichever block this is
-    pen += __longlong_as_double((long long)__hip_atomic_load(&part[i].pen_bits, __ATOMIC_RELAXED,
-                                                             __HIP_MEMORY_SCOPE_AGENT));
-    nrm += __longlong_as_double((long long)__hip_atomic_load(&part[i].norm_bits, __ATOMIC_RELAXED,
-                                                             __HIP_MEMORY_SCOPE_AGENT));
+    pen += partial_load(&part[i].pen_bits);
+    nrm += partial_load(&part[i].norm_bits);
   }
   out2[0] = (float)(pen / (double)B);
   out2[1] = (float)(nrm / (double)B);
@@ -180,8 +150,6 @@ wgan_critic_kernel(const float* __restrict__ d_fake, const float* __restrict__ d
   }
 }
 
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace ali
 
 using namespace ali;
@@ -211,14 +179,13 @@ extern "C" int ali_gp_penalty(const float* g0, int32_t B, int64_t P, float lambd
     set_error("ali_gp_penalty: B = %d outside [1, 65535] or P = %lld outside [1, 2^40 / B)", (int)B, (long long)P);
     return ALI_ERR_BAD_ARG;
   }
-  if (!ws || ws_payload_bytes(ws_bytes) < (size_t)B * sizeof(GpPart)) {
-    set_error("ali_gp_penalty: workspace too small (%zu bytes behind the reserved head needed)", (size_t)B * sizeof(GpPart));
-    return ALI_ERR_WORKSPACE;
-  }
+  GpPart* part;
+  int* ctr;
+  const int rc = fold_workspace("ali_gp_penalty", ws, ws_bytes, (size_t)B, &part, &ctr);
+  if (rc != ALI_OK) return rc;
   const int vec = (P % 4) == 0 && aligned16(g0) && (!v || aligned16(v));
-  hipLaunchKernelGGL(gp_penalty_kernel, dim3((unsigned)B), dim3(kGpThreads), 0, (hipStream_t)stream, g0, (int)B,
-                     (long long)P, lambda, out2, v, reinterpret_cast<GpPart*>(ws_payload(ws)),
-                     reinterpret_cast<int*>(ws) + kGanCtr, vec);
+  hipLaunchKernelGGL(gp_penalty_kernel, dim3((unsigned)B), dim3(kGpThreads), 0, ST(stream), g0, (int)B, (long long)P,
+                     lambda, out2, v, part, ctr, vec);
   return check_launch("gp_penalty_kernel");
 }
 

@@ -15,7 +15,6 @@
 
 namespace ali {
 
-#define ST(s) ((hipStream_t)(s))
 
 constexpr uint64_t kPhaseStream = 0x474C504841534531ull;   // "GLPHASE1": separates the phases' keys from masks / latents
 constexpr int kGlBlock = 256;

@@ -231,7 +231,6 @@ static bool ssim_shape_ok(const char* what, int64_t planes, int H, int W, int wi
 }  // namespace ali
 
 using namespace ali;
-#define ST(s) ((hipStream_t)(s))
 
 extern "C" int ali_ssim_fwd(const float* X, const float* Y, int64_t planes, int32_t H, int32_t W, const float* win,
                             int32_t win_size, float C1, float C2, float* ssim_pc, float* mA, float* mB, float* mC,

@@ -12,18 +12,15 @@
 //
 // One 256-thread block per row, threads strided over the columns; the S decoder passes are S*B rows of one pass.  Row
 // arithmetic is fp64 (exp included): the kernels are launch- or HBM-bound at every size the callers have, and each fp32
-// result is then the rounding of an fp64 evaluation.  Reductions: lanes by xor butterflies (a + b == b + a bit for
-// bit), waves 0..3 in order, blocks through 8-byte write-through partials in the workspace that the block arriving last
-// adds in block order -- xent.hip's fold, with its counter (the last int of the reserved head; zero between launches).
-// No float atomics: the same inputs give the same bits on every run.
-#include "ali_common.h"
+// result is then the rounding of an fp64 evaluation.  Reductions and the hand-off between blocks: ali_reduce.h.  Here:
+// the block that arrives last folds the partials with all its threads (vae_fold).
+#include "ali_reduce.h"
 
 namespace ali {
 
 constexpr int kVaeBlock = 256;
 constexpr int kVaeWaves = kVaeBlock / 64;
 constexpr int kVaeMaxBlocks = 1024;
-constexpr int kVaeCtr = (int)(kWsReserved / sizeof(int)) - 1;
 constexpr int kVaeMaxEmb = 8;
 
 struct VaeCond {
@@ -35,45 +32,11 @@ struct VaeCond {
   int n_emb, n_cont;
 };
 
-__device__ __forceinline__ double vae_wave_sum(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
-// sum over the block, valid in every thread; `red` holds kVaeWaves doubles
-__device__ __forceinline__ double vae_block_sum(double v, double* red) {
-  v = vae_wave_sum(v);
-  __syncthreads();                                   // (red may still be read from an earlier call)
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = 0.0;
-#pragma unroll
-  for (int w = 0; w < kVaeWaves; ++w) t += red[w];
-  return t;
-}
-
-// thread 0 publishes the block's partial and arrives; returns (to every thread) whether this block arrived last
-__device__ __forceinline__ bool vae_arrive(double partial, double* slot, int* ctr, int expected, int* s_last) {
-  if (threadIdx.x == 0) {
-    __hip_atomic_store(reinterpret_cast<unsigned long long*>(slot), (unsigned long long)__double_as_longlong(partial),
-                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const int arrived = __hip_atomic_fetch_add(ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    *s_last = arrived == expected - 1;
-    if (*s_last) __hip_atomic_store(ctr, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // all have arrived
-  }
-  __syncthreads();
-  return *s_last != 0;
-}
-
 // partials 0..n-1 added in a fixed order: thread t takes t, t + 256, ... ascending, then the block sum
-__device__ __forceinline__ double vae_fold(const double* part, int n, double* red) {
+__device__ __forceinline__ double vae_fold(const unsigned long long* part, int n, double* red) {
   double v = 0.0;
-  for (int i = threadIdx.x; i < n; i += kVaeBlock)
-    v += __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<const unsigned long long*>(part + i),
-                                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-  return vae_block_sum(v, red);
+  for (int i = threadIdx.x; i < n; i += kVaeBlock) v += partial_load(part + i);
+  return block_sum<kVaeWaves>(v, red);
 }
 
 __device__ __forceinline__ float vae_attr(const void* p, int is_int, long long i) {
@@ -85,7 +48,7 @@ vae_latent_fwd_kernel(const float* __restrict__ mean, const float* __restrict__ 
                       const float* __restrict__ eps_in, float* __restrict__ eps_out, uint64_t seed,
                       const long long* __restrict__ dev_counter, uint64_t offset, int S, int B, int L, float k,
                       VaeCond c, int write_cond, int ld, float* __restrict__ out, float* __restrict__ kl_out,
-                      double* part, int* ctr) {
+                      unsigned long long* part, int* ctr) {
   __shared__ double red[kVaeWaves];
   __shared__ int s_last;
   const long long row = blockIdx.x;
@@ -122,8 +85,9 @@ vae_latent_fwd_kernel(const float* __restrict__ mean, const float* __restrict__ 
     }
   }
   if (!kl_row) return;                                          // (block-uniform)
-  const double dkl = 0.5 * vae_block_sum(acc, red);
-  if (!vae_arrive(dkl, part + b, ctr, B, &s_last)) return;
+  const double dkl = 0.5 * block_sum<kVaeWaves>(acc, red);
+  if (threadIdx.x == 0) partial_store(part + b, dkl);
+  if (!arrive_last(ctr, B, &s_last)) return;
   const double total = vae_fold(part, B, red);
   if (threadIdx.x == 0) kl_out[0] = (float)total;
 }
@@ -132,7 +96,7 @@ template <bool kVec>
 __global__ void __launch_bounds__(kVaeBlock)
 vae_loglik_kernel(const float* __restrict__ x, const float* __restrict__ xhat, int B, int S, int P, float log_var,
                   const float* __restrict__ kl_sum, float kl_weight, float gscale, float* __restrict__ out3,
-                  float* __restrict__ gxhat, double* part, int* ctr) {
+                  float* __restrict__ gxhat, unsigned long long* part, int* ctr) {
   __shared__ double red[kVaeWaves];
   __shared__ int s_last;
   const long long R = (long long)S * B;
@@ -161,8 +125,9 @@ vae_loglik_kernel(const float* __restrict__ x, const float* __restrict__ xhat, i
       }
     }
   }
-  const double sq = vae_block_sum(acc, red);
-  if (!vae_arrive(sq, part + blockIdx.x, ctr, (int)gridDim.x, &s_last)) return;
+  const double sq = block_sum<kVaeWaves>(acc, red);
+  if (threadIdx.x == 0) partial_store(part + blockIdx.x, sq);
+  if (!arrive_last(ctr, (int)gridDim.x, &s_last)) return;
   const double total = vae_fold(part, (int)gridDim.x, red);
   if (threadIdx.x != 0) return;
   const double lp = -0.5 * inv * total / (double)R - 0.5 * (double)P * (double)log_var
@@ -200,8 +165,6 @@ vae_latent_bwd_kernel(const float* __restrict__ gin, int ld, const float* __rest
   glv[(long long)b * gld + col] = (float)(gl * (double)k * exp((double)k * vv) + kw * 0.5 * (exp(vv) - 1.0));
 }
 
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace ali
 
 using namespace ali;
@@ -232,15 +195,15 @@ extern "C" int ali_vae_latent_fwd(const float* mean, const float* log_var, int32
     }
     c.cont = cont; c.n_emb = n_emb; c.n_cont = n_cont;
   }
-  if (kl_out && (!ws || ws_payload_bytes(ws_bytes) < (size_t)B * sizeof(double))) {
-    set_error("ali_vae_latent_fwd: workspace too small (%zu bytes behind the reserved head needed)",
-              (size_t)B * sizeof(double));
-    return ALI_ERR_WORKSPACE;
+  unsigned long long* part = nullptr;                             // (without kl_out nothing is folded)
+  int* ctr = nullptr;
+  if (kl_out) {
+    const int rc = fold_workspace("ali_vae_latent_fwd", ws, ws_bytes, (size_t)B, &part, &ctr);
+    if (rc != ALI_OK) return rc;
   }
-  hipLaunchKernelGGL(vae_latent_fwd_kernel, dim3((unsigned)((long long)S * B)), dim3(kVaeBlock), 0, (hipStream_t)stream,
-                     mean, log_var, (int)head_ld, eps, eps_out, seed, reinterpret_cast<const long long*>(dev_counter),
-                     offset, (int)S, (int)B, (int)L, k, c, (int)(write_cond != 0), (int)ld, out, kl_out,
-                     reinterpret_cast<double*>(ws_payload(ws)), ws ? reinterpret_cast<int*>(ws) + kVaeCtr : nullptr);
+  hipLaunchKernelGGL(vae_latent_fwd_kernel, dim3((unsigned)((long long)S * B)), dim3(kVaeBlock), 0, ST(stream), mean,
+                     log_var, (int)head_ld, eps, eps_out, seed, reinterpret_cast<const long long*>(dev_counter), offset,
+                     (int)S, (int)B, (int)L, k, c, (int)(write_cond != 0), (int)ld, out, kl_out, part, ctr);
   return check_launch("vae_latent_fwd_kernel");
 }
 
@@ -253,20 +216,17 @@ extern "C" int ali_vae_loglik(const float* x, const float* xhat, int32_t B, int3
   }
   const long long R = (long long)S * B;
   const int blocks = (int)(R < kVaeMaxBlocks ? R : kVaeMaxBlocks);
-  if (!ws || ws_payload_bytes(ws_bytes) < (size_t)blocks * sizeof(double)) {
-    set_error("ali_vae_loglik: workspace too small (%zu bytes behind the reserved head needed)",
-              (size_t)blocks * sizeof(double));
-    return ALI_ERR_WORKSPACE;
-  }
+  unsigned long long* part;
+  int* ctr;
+  const int rc = fold_workspace("ali_vae_loglik", ws, ws_bytes, (size_t)blocks, &part, &ctr);
+  if (rc != ALI_OK) return rc;
   const bool vec = P % 4 == 0 && aligned16(x) && aligned16(xhat) && (!gxhat || aligned16(gxhat));
-  double* part = reinterpret_cast<double*>(ws_payload(ws));
-  int* ctr = reinterpret_cast<int*>(ws) + kVaeCtr;
   if (vec)
-    hipLaunchKernelGGL(vae_loglik_kernel<true>, dim3(blocks), dim3(kVaeBlock), 0, (hipStream_t)stream, x, xhat, (int)B,
-                       (int)S, (int)P, log_var, kl_sum, kl_weight, gscale, out3, gxhat, part, ctr);
+    hipLaunchKernelGGL(vae_loglik_kernel<true>, dim3(blocks), dim3(kVaeBlock), 0, ST(stream), x, xhat, (int)B, (int)S,
+                       (int)P, log_var, kl_sum, kl_weight, gscale, out3, gxhat, part, ctr);
   else
-    hipLaunchKernelGGL(vae_loglik_kernel<false>, dim3(blocks), dim3(kVaeBlock), 0, (hipStream_t)stream, x, xhat, (int)B,
-                       (int)S, (int)P, log_var, kl_sum, kl_weight, gscale, out3, gxhat, part, ctr);
+    hipLaunchKernelGGL(vae_loglik_kernel<false>, dim3(blocks), dim3(kVaeBlock), 0, ST(stream), x, xhat, (int)B, (int)S,
+                       (int)P, log_var, kl_sum, kl_weight, gscale, out3, gxhat, part, ctr);
   return check_launch("vae_loglik_kernel");
 }
 

@@ -10,16 +10,12 @@
 //   3. loss_b = sum t * (lse - z),  glogit = gscale * (exp(z - lse) * sum t - t) / B
 // The row arithmetic is fp64 (exp and log included): the kernel is launch bound at every size the callers have, and
 // every fp32 result is then the rounding of an fp64 evaluation, whatever |logit| <= 1e4 does to z - max.
-// Cross-lane reductions are xor butterflies (a + b == b + a bit for bit, so all lanes agree); the arg-max butterfly
-// carries the index and prefers the lower one on equal values, which is torch.argmax's first maximum.
-// Rows -> wave partials (fixed row order) -> block partial (waves 0..3 in order) -> 8-byte write-through stores into
-// the workspace; the block that arrives last at the counter adds the block partials in block order.  No float atomics:
-// the same inputs give the same bits on every run.  The counter is the last int of the workspace's reserved head
-// (zero between launches, like the split-K counters in front of it) and is left at zero.
+// Reductions and the hand-off between blocks: ali_reduce.h.  Here: rows -> wave partials (fixed row order) -> block
+// partial (waves 0..3 in order) -> the block that arrives last adds the block partials, thread 0, blocks ascending.
 //
 // NaN logits (what falls out, untested): comparisons with NaN are false, so a NaN never becomes the maximum or the
 // prediction -- torch.argmax would pick it --; exp(NaN - max) makes the row's loss and gradient NaN, and with them out2[0].
-#include "ali_common.h"
+#include "ali_reduce.h"
 
 #include <limits.h>
 
@@ -27,24 +23,8 @@ namespace ali {
 
 constexpr int kXentWaves = 4;
 constexpr int kXentMaxBlocks = 1024;
-constexpr int kXentCtr = (int)(kWsReserved / sizeof(int)) - 1;
 
 struct XentPart { unsigned long long loss_bits; unsigned long long hits; };
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
-__device__ __forceinline__ void wave_argmax(float& v, int& i) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    const float ov = __shfl_xor(v, m, 64);
-    const int oi = __shfl_xor(i, m, 64);
-    if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
-  }
-}
 
 __global__ void __launch_bounds__(kXentWaves * 64)
 softmax_xent_kernel(const float* __restrict__ logit, const float* __restrict__ target, int B, int C, float gscale,
@@ -87,30 +67,18 @@ softmax_xent_kernel(const float* __restrict__ logit, const float* __restrict__ t
     hits_w += (zi == ti) ? 1 : 0;
     if (pred && lane == 0) pred[b] = zi;
   }
-  if (lane == 0) { s_loss[wave] = loss_w; s_hits[wave] = hits_w; }
-  __syncthreads();
+  const double l = waves_sum<kXentWaves>(loss_w, s_loss);
+  const int h = waves_sum<kXentWaves>(hits_w, s_hits);
   if (threadIdx.x == 0) {
-    double l = 0.0;
-    long long h = 0;
-    for (int w = 0; w < kXentWaves; ++w) { l += s_loss[w]; h += s_hits[w]; }
-    // write-through (device-scope) stores, drained before the arrival: the reducer's device-scope loads see them on
-    // whichever XCD it runs
-    __hip_atomic_store(&part[blockIdx.x].loss_bits, (unsigned long long)__double_as_longlong(l), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(&part[blockIdx.x].hits, (unsigned long long)h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const int arrived = __hip_atomic_fetch_add(ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s_last = arrived == (int)gridDim.x - 1;
-    if (s_last) __hip_atomic_store(ctr, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // all blocks have arrived
+    partial_store(&part[blockIdx.x].loss_bits, l);
+    partial_store_int(&part[blockIdx.x].hits, (unsigned long long)h);
   }
-  __syncthreads();
-  if (!s_last || threadIdx.x != 0) return;
+  if (!arrive_last(ctr, (int)gridDim.x, &s_last) || threadIdx.x != 0) return;
   double total = 0.0;
   long long hits = 0;
   for (int i = 0; i < (int)gridDim.x; ++i) {       // block order, whichever block this is
-    total += __longlong_as_double((long long)__hip_atomic_load(&part[i].loss_bits, __ATOMIC_RELAXED,
-                                                               __HIP_MEMORY_SCOPE_AGENT));
-    hits += (long long)__hip_atomic_load(&part[i].hits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    total += partial_load(&part[i].loss_bits);
+    hits += (long long)partial_load_int(&part[i].hits);
   }
   out2[0] = (float)(total / (double)B);
   out2[1] = (float)hits;
@@ -138,14 +106,12 @@ extern "C" int ali_softmax_xent(const float* logit, const float* target, int32_t
   }
   int blocks = (B + kXentWaves - 1) / kXentWaves;
   if (blocks > kXentMaxBlocks) blocks = kXentMaxBlocks;
-  if (!ws || ws_payload_bytes(ws_bytes) < (size_t)blocks * sizeof(XentPart)) {
-    set_error("ali_softmax_xent: workspace too small (%zu bytes behind the reserved head needed)",
-              (size_t)blocks * sizeof(XentPart));
-    return ALI_ERR_WORKSPACE;
-  }
-  hipLaunchKernelGGL(softmax_xent_kernel, dim3(blocks), dim3(kXentWaves * 64), 0, (hipStream_t)stream, logit, target,
-                     (int)B, (int)C, gscale, out2, glogit, reinterpret_cast<int*>(pred),
-                     reinterpret_cast<long long*>(hits_accum), reinterpret_cast<XentPart*>(ws_payload(ws)),
-                     reinterpret_cast<int*>(ws) + kXentCtr);
+  XentPart* part;
+  int* ctr;
+  const int rc = fold_workspace("ali_softmax_xent", ws, ws_bytes, (size_t)blocks, &part, &ctr);
+  if (rc != ALI_OK) return rc;
+  hipLaunchKernelGGL(softmax_xent_kernel, dim3(blocks), dim3(kXentWaves * 64), 0, ST(stream), logit, target, (int)B,
+                     (int)C, gscale, out2, glogit, reinterpret_cast<int*>(pred),
+                     reinterpret_cast<long long*>(hits_accum), part, ctr);
   return check_launch("softmax_xent_kernel");
 }
