@@ -80,6 +80,7 @@ struct GDesc {
   int tail_u0, tail_split;  // whole tiles first, then the left-over tiles cut tail_split ways along K
   const int* order;         // AliEpilogue.tile_order (M-tile ids, longest k-loop first) or null
   int ldi;                  // pixel pitch of the gathered operand (floats): Cin, or AliEpilogue.in_ld
+  int no_clean;        // ALI_NO_CLEAN=1: every tile takes the general fp32 k-loop (A/B, tests)
   int f16;             // AliEpilogue.mfma_f16: fp16 operands on v_mfma_f32_32x32x16_f16 where the fast path applies
   const _Float16* in16;   // AliEpilogue.in16 / w16 / out16 (fp16 twins of in / w / out), or null
   const _Float16* w16;
@@ -135,6 +136,7 @@ __device__ __forceinline__ void gconv_body(const GDesc& d, const int bx_, const 
   __shared__ int s_tap[kMaxTaps];                                  // dh | dw<<8 | wt<<16 (generic path)
   __shared__ __attribute__((aligned(16))) int s_live[kMaxTaps + 8][4]; // per (live) tap {doff, woff, tap bit, 0} (bytes)
   __shared__ unsigned s_tapmask;
+  __shared__ int s_clean, s_dmin;   // fp32 MODE 2: no row of the tile misses a live tap; smallest live tap offset (bytes)
 
   const int t = threadIdx.x;
   const int lane = t & 63, wave = t >> 6;
@@ -209,7 +211,7 @@ __device__ __forceinline__ void gconv_body(const GDesc& d, const int bx_, const 
     }
     s_tap[t] = v;
   }
-  if (t == 0) s_tapmask = 0u;
+  if (t == 0) { s_tapmask = 0u; s_clean = 1; s_dmin = 0x7fffffff; }
 
   const float rW = 1.0f / (float)P.Wq, rH = 1.0f / (float)P.Hq, rB = 1.0f / (float)d.B;
   auto decode = [&](int m, int& img, int& qh, int& qw) {
@@ -262,6 +264,12 @@ __device__ __forceinline__ void gconv_body(const GDesc& d, const int bx_, const 
   if (c4 == 0 && blockmask) atomicOr(&s_tapmask, blockmask);
   __syncthreads();
   const unsigned tapmask = s_tapmask;
+  if (MODE == 2 && F16 == 0) {   // clean-tile test, row part: read behind the next barrier
+    bool mine = true;
+#pragma unroll
+    for (int i = 0; i < AP; ++i) mine = mine && (amask[i] & tapmask) == tapmask;
+    if (!mine) s_clean = 0;
+  }
 
   // the epilogue's bias values, requested now: by the end of the k-loop they have long arrived (a dependent load in
   // the epilogue costs a full memory latency, which is a tenth of a small launch)
@@ -311,6 +319,7 @@ __device__ __forceinline__ void gconv_body(const GDesc& d, const int bx_, const 
       const int tv = s_tap[t];
       const int dh = (signed char)(tv & 0xff), dw = (signed char)((tv >> 8) & 0xff), wt = (tv >> 16) & 0xff;
       s_live[pos][0] = ((dh * Win + dw) * d.ldi) * 4;
+      if (F16 == 0) atomicMin(&s_dmin, ((dh * Win + dw) * d.ldi) * 4);
       s_live[pos][1] = (wt * Cin) * 4;
       s_live[pos][2] = (int)(1u << t);
       s_live[pos][3] = 0;
@@ -629,16 +638,61 @@ __device__ __forceinline__ void gconv_body(const GDesc& d, const int bx_, const 
       store_tile(0);
       if (++ch == cpt) { ch = 0; ++li; }
       Ctx cxn = tile_ctx(li, ch, q + 2 < qe);
+      // Clean tile: every row is a real row (an absent row has an empty tap mask, so it clears s_clean
+      // like a row that misses a live tap), every live tap hits the input for every row and every weight row exists -- no gather of the k-loop can be dead, so the selects above decide nothing.  The clean loop
+      // keeps a constant per-thread voffset; the block-uniform tap / chunk offset travels as the scalar soffset.  The
+      // hardware adds soffset unsigned, so the A voffset is biased by the smallest live tap offset (still the address of
+      // a real pixel of the row: in range).  Tiles past qe are fetched through a descriptor of 0 records: zeros, no
+      // memory traffic, exactly what the general loop stages.  Same slots, same LDS image, same k order: same bits.
+      const bool clean = F16 == 0 && MODE == 2 && d.no_clean == 0 && n0 + BN <= d.Cout &&
+                         __builtin_amdgcn_readfirstlane(s_clean) != 0;
+      struct CCtx { int sa, sb; unsigned na, nb; };
+      unsigned aoffC[AP];
+      int dmin = 0, tap_sa = 0, tap_sb = 0;
+      auto clean_tap = [&](int l) {    // the tap's constants: one LDS broadcast read per TAP, made uniform once
+        const int4 ti = *reinterpret_cast<const int4*>(&s_live[l < nlive ? l : nlive - 1][0]);
+        tap_sa = __builtin_amdgcn_readfirstlane(ti.x - dmin);
+        tap_sb = __builtin_amdgcn_readfirstlane(ti.y);
+      };
+      auto clean_ctx = [&](int c, bool live) -> CCtx {
+        CCtx cc;
+        cc.sa = tap_sa + c * (BK * 4);
+        cc.sb = tap_sb + c * (BK * 4);
+        cc.na = live ? d.in_bytes : 0u;
+        cc.nb = live ? d.w_bytes : 0u;
+        return cc;
+      };
+      CCtx ccn = {0, 0, 0u, 0u};
+      if (clean) {
+        dmin = __builtin_amdgcn_readfirstlane(s_dmin);
+#pragma unroll
+        for (int i = 0; i < AP; ++i) aoffC[i] = aoffB[i] + (unsigned)dmin;
+        clean_tap(li);
+        ccn = clean_ctx(ch, q + 2 < qe);
+      }
+      auto load_ac = [&](const CCtx& cc, int i, auto SET) {
+        const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void*)d.in, 0, cc.na, 0x00020000);
+        const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)aoffC[i], cc.sa, 0));
+        if (decltype(SET)::value) ra1[i] = v; else ra[i] = v;
+      };
+      auto load_bc = [&](const CCtx& cc, int j, auto SET) {
+        const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void*)d.w, 0, cc.nb, 0x00020000);
+        const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)woffB[j], cc.sb, 0));
+        if (decltype(SET)::value) rb1[j] = v; else rb[j] = v;
+      };
       __syncthreads();
-      int buf = 0;
-      // one iteration; FETCH = staging set that receives tile q+2 (the other one holds tile q+1)
-      auto iteration = [&](auto FETCH) {
+      // one iteration; FETCH = staging set that receives tile q+2 (the other one holds tile q+1).  The LDS buffer that
+      // is multiplied is tied to the set (q - qb even: set 0, buffer 0), so every LDS address is base + immediate.
+      auto iteration = [&](auto FETCH, auto CLEAN) {
         constexpr int fetch = decltype(FETCH)::value;
+        constexpr bool cl = decltype(CLEAN)::value;
+        constexpr int buf = fetch;
         const float* Ac = Ab + buf * (BM * LDK);
         const float* Bc = Bb + buf * (BN * LDK);
         float* Aw = &As[buf ^ 1][r0 * LDK + c4 * 4];
         float* Bw = &Bs[buf ^ 1][r0 * LDK + c4 * 4];
         Ctx cxn2 = cxn;
+        CCtx ccn2 = ccn;
 #pragma unroll
         for (int i = 0; i < TM; ++i) fa[0][i] = *reinterpret_cast<const f32x4*>(Ac + i * 32 * LDK);
 #pragma unroll
@@ -658,7 +712,11 @@ __device__ __forceinline__ void gconv_body(const GDesc& d, const int bx_, const 
 #pragma unroll
               for (int x = 0; x < NL; ++x) {
                 if ((x * Q) / NL != s) continue;
-                if (x < AP) load_a(cxn, x, FETCH); else load_b(cxn, x - AP, FETCH);
+                if (cl) {
+                  if (x < AP) load_ac(ccn, x, FETCH); else load_bc(ccn, x - AP, FETCH);
+                } else {
+                  if (x < AP) load_a(cxn, x, FETCH); else load_b(cxn, x - AP, FETCH);
+                }
               }
             }
           }
@@ -671,9 +729,14 @@ __device__ __forceinline__ void gconv_body(const GDesc& d, const int bx_, const 
                 fb[(kg + 1) & 1][sg - TM] = *reinterpret_cast<const f32x4*>(Bc + (sg - TM) * 32 * LDK + (kg + 1) * 8);
             }
           }
-          if (s == NMF / 2) {  // constants of the tile fetched by the next iteration (LDS broadcast read)
-            if (++ch == cpt) { ch = 0; ++li; }
-            cxn2 = tile_ctx(li, ch, q + 3 < qe);
+          if (s == NMF / 2) {  // constants of the tile fetched by the next iteration
+            if (cl) {          // scalar adds; the LDS read only when the tap changes
+              if (++ch == cpt) { ch = 0; ++li; clean_tap(li); }
+              ccn2 = clean_ctx(ch, q + 3 < qe);
+            } else {           // (LDS broadcast read)
+              if (++ch == cpt) { ch = 0; ++li; }
+              cxn2 = tile_ctx(li, ch, q + 3 < qe);
+            }
           }
           {  // LDS writes over the last quarter
             constexpr int Q = NMF / 4;
@@ -690,14 +753,28 @@ __device__ __forceinline__ void gconv_body(const GDesc& d, const int bx_, const 
           __builtin_amdgcn_sched_barrier(0);
         }
         cxn = cxn2;
+        ccn = ccn2;
         __syncthreads();
-        buf ^= 1;
         ++q;
       };
-      while (q < qe) {
-        iteration(Set0{});        // tile q+2 -> set 0 (q - qb even), tile q+1 sits in set 1
-        if (q >= qe) break;
-        iteration(Set1{});
+      // Whole pairs, then the odd tile: the loop has ONE back edge, behind the set-1 iteration.  (An early exit between
+      // the two halves made the compiler carry the set-0 gathers, just issued, into the loop header as pending writes
+      // of registers the header's fragment reads reuse: a vmcnt(0) per pair that drained the gathers the pipeline means
+      // to keep in flight -- DESIGN.md 3.1.)
+      auto run = [&](auto CLEAN) {
+        const int npair = (qe - qb) >> 1;
+#pragma unroll 1
+        for (int pr = 0; pr < npair; ++pr) {
+          iteration(Set0{}, CLEAN);   // tile q+2 -> set 0 (q - qb even), tile q+1 sits in set 1
+          iteration(Set1{}, CLEAN);
+        }
+        if ((qe - qb) & 1) iteration(Set0{}, CLEAN);
+      };
+      if constexpr (MODE == 2 && F16 == 0) {
+        if (clean) run(std::true_type{});
+        else run(std::false_type{});
+      } else {
+        run(std::false_type{});
       }
     }
   } else {
@@ -1282,6 +1359,7 @@ static int finalize_and_launch(GDesc& d, void* ws, size_t ws_bytes, hipStream_t 
     d.xcd_chunk = (int)((blocks + 7) / 8);
     d.lin1d = 1;
   }
+  d.no_clean = tuning().no_clean;
   d.ctr = reinterpret_cast<int*>(ws);
   d.ws = reinterpret_cast<float*>(ws_payload(ws));
   dim3 grid(tiles, ntile_n, S), block(256);

@@ -14,6 +14,7 @@
 #include "ali_common.h"
 #include <string.h>
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 namespace ali {
@@ -38,6 +39,7 @@ struct WDesc {
   const _Float16* x16;   // fp16 twins of x / dy (same shapes), or null: the F16 == 2 kernels read these
   const _Float16* dy16;
   int ldd;            // floats between consecutive pixels of dy (Cd, or more when dy is a column range of wider rows)
+  int no_clean;       // ALI_NO_CLEAN=1: every block takes the general fp32 k-loop (A/B, tests)
 };
 
 template <int BM, int BN, int WAVES_M, int WAVES_N, bool VECA, bool VECB>
@@ -241,6 +243,7 @@ __device__ __forceinline__ void wgrad_fast_body(const WDesc& d, const unsigned x
   __shared__ __attribute__((aligned(16))) float As[2][WBK2 * LDA];
   __shared__ __attribute__((aligned(16))) float Bs[2][WBK2 * LDB];
   __shared__ long long s_rowdst[BM];
+  __shared__ int s_wclean;   // fp32 TAB loop: every tap of the tile hits the map at every output pixel
 
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int wm = wave / WAVES_N, wn = wave % WAVES_N;
@@ -249,6 +252,10 @@ __device__ __forceinline__ void wgrad_fast_body(const WDesc& d, const unsigned x
   const int pix_end = min(d.npix, pix_begin + d.pix_per_split);
   const int PQ = d.P * d.Q;
   const float rPQ = 1.0f / (float)PQ, rQ = 1.0f / (float)d.Q;
+  // what the gathers of the k-loop test against, pinned in scalar registers (left to itself the compiler re-reads
+  // these descriptor fields with s_load_dword + s_waitcnt in front of every gather of the general loop)
+  const int dH = __builtin_amdgcn_readfirstlane(d.H), dW = __builtin_amdgcn_readfirstlane(d.W);
+  const int ldd = __builtin_amdgcn_readfirstlane(d.ldd);
 
   for (int r = t; r < BM; r += 256) {
     const int m = m0 + r;
@@ -272,7 +279,12 @@ __device__ __forceinline__ void wgrad_fast_body(const WDesc& d, const unsigned x
   const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)d.x, 0, x_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc((void*)d.dy, 0, dy_bytes, 0x00020000);
   constexpr unsigned OOB = 0xFFFFFF00u;
+  if (t == 0) s_wclean = 1;
   __syncthreads();
+  if (TAB && F16 == 0) {   // clean-block test, tap part (read behind the barrier that ends the prologue)
+    const bool mine = a_ok && dhA >= 0 && dhA + (d.P - 1) * d.stride < d.H && dwA >= 0 && dwA + (d.Q - 1) * d.stride < d.W;
+    if (!mine) s_wclean = 0;
+  }
 
   f32x4 ra[AP], rb[BP];
   const bool do_db = d.db != nullptr && bx_ == 0;
@@ -293,7 +305,7 @@ __device__ __forceinline__ void wgrad_fast_body(const WDesc& d, const unsigned x
     if (TAB) {
       // entry: x = byte offset of x[b, p*stride, q*stride, 0]; y = (p*stride + 0x4000) | (q*stride + 0x4000) << 16
       const int ih = (te[i].y & 0xffff) - 0x4000 + dhA, iw = (int)((unsigned)te[i].y >> 16) - 0x4000 + dwA;
-      if (a_ok && (unsigned)ih < (unsigned)d.H && (unsigned)iw < (unsigned)d.W) off = (unsigned)(te[i].x + tapoffA);
+      if (a_ok && (unsigned)ih < (unsigned)dH && (unsigned)iw < (unsigned)dW) off = (unsigned)(te[i].x + tapoffA);
     } else {
       const int pix = pix0 + arow0 + i * AROWS;
       if (a_ok && pix < pix_end) {
@@ -301,15 +313,15 @@ __device__ __forceinline__ void wgrad_fast_body(const WDesc& d, const unsigned x
         w_divmod(pix, PQ, rPQ, b, rem);
         w_divmod(rem, d.Q, rQ, p, q);
         const int ih = p * d.stride + dhA, iw = q * d.stride + dwA;
-        if ((unsigned)ih < (unsigned)d.H && (unsigned)iw < (unsigned)d.W)
-          off = (unsigned)(((b * d.H + ih) * d.W + iw) * d.Cg + gcA) * 4u;
+        if ((unsigned)ih < (unsigned)dH && (unsigned)iw < (unsigned)dW)
+          off = (unsigned)(((b * dH + ih) * dW + iw) * d.Cg + gcA) * 4u;
       }
     }
     ra[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, (int)off, 0, 0));
   };
   auto load_b = [&](int pix0, int j) {
     const int pix = pix0 + brow0 + j * BROWS;
-    const unsigned off = (b_ok && pix < pix_end) ? (unsigned)(pix * d.ldd + nB) * 4u : OOB;
+    const unsigned off = (b_ok && pix < pix_end) ? (unsigned)(pix * ldd + nB) * 4u : OOB;
     rb[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ry, (int)off, 0, 0));
   };
   auto store_tile = [&](int buf) {
@@ -554,11 +566,34 @@ __device__ __forceinline__ void wgrad_fast_body(const WDesc& d, const unsigned x
     }
     store_tile(0);
     __syncthreads();
-    int buf = 0;
+    // Clean block: every row of the tile is a real (tap, channel), every dense column exists, and every
+    // tap of the tile hits the map at EVERY output pixel (any unpadded conv; the interior taps of a padded one) -- so
+    // for a k-tile that lies wholly below pix_end no gather can be dead: the A offset is table entry + tap constant,
+    // the B offset a per-thread constant plus a scalar that advances by a constant per k-tile.  The k-tiles at the end
+    // of the slab (the partial one, the ones fetched past it) keep the tests: they run the general iteration.
+    bool clean = false;
+    if constexpr (TAB && F16 == 0)
+      clean = d.no_clean == 0 && n0 + BN <= d.Cd && __builtin_amdgcn_readfirstlane(s_wclean) != 0;
+    unsigned boffC[BP];
+#pragma unroll
+    for (int j = 0; j < BP; ++j) boffC[j] = (unsigned)((brow0 + j * BROWS) * ldd + nB) * 4u;
+    auto load_ac = [&](int i) {
+      ra[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, te[i].x + tapoffA, 0, 0));
+    };
+    auto load_bc = [&](int soff, int j) {
+      rb[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ry, (int)boffC[j], soff, 0));
+    };
     const int lcol = lane & 31, lh = lane >> 5;
     float fa[2][TM], fb[2][TN];
-    for (int pix0 = pix_begin; pix0 < pix_end; pix0 += WBK2) {
+    // One k-tile.  BUF: the LDS buffer that is multiplied -- a compile-time constant in the clean loop (unrolled by
+    // two: every LDS address is base + immediate), a run-time value in the general one.  CLEAN: the gathers of the next
+    // tile without tests.  DB: (clean loop) whether this block accumulates the bias gradient, decided once per block.
+    auto iteration = [&](int pix0, auto BUF, auto CLEAN, auto DB) {
+      constexpr bool cl = decltype(CLEAN)::value;
+      const int buf = BUF;
+      const bool dbv = cl ? (bool)decltype(DB)::value : do_db;
       const int nxt = pix0 + WBK2;   // rows >= pix_end load zeros (range-checked offsets)
+      const int soffB = cl ? __builtin_amdgcn_readfirstlane((int)((unsigned)nxt * (unsigned)ldd * 4u)) : 0;   // (bytes, < 2^32)
       const float* Ac = &As[buf][lh * LDA + wm * WM + lcol];
       const float* Bc = &Bs[buf][lh * LDB + wn * WN + lcol];
 #pragma unroll
@@ -576,7 +611,11 @@ __device__ __forceinline__ void wgrad_fast_body(const WDesc& d, const unsigned x
 #pragma unroll
             for (int x = 0; x < NL; ++x) {
               if ((x * Q) / NL != s) continue;
-              if (x < AP) load_a(nxt, x); else load_b(nxt, x - AP);
+              if (cl) {
+                if (x < AP) load_ac(x); else load_bc(soffB, x - AP);
+              } else {
+                if (x < AP) load_a(nxt, x); else load_b(nxt, x - AP);
+              }
             }
           }
           if (TAB && s >= Q && s < 2 * Q) {   // second quarter: table entries of the tile after next
@@ -609,7 +648,7 @@ __device__ __forceinline__ void wgrad_fast_body(const WDesc& d, const unsigned x
               if (x < AP) *reinterpret_cast<f32x4*>(&As[buf ^ 1][(arow0 + x * AROWS) * LDA + a4 * 4]) = ra[x];
               else {
                 *reinterpret_cast<f32x4*>(&Bs[buf ^ 1][(brow0 + (x - AP) * BROWS) * LDB + b4 * 4]) = rb[x - AP];
-                if (do_db) dbacc += rb[x - AP];
+                if (dbv) dbacc += rb[x - AP];
               }
             }
           }
@@ -617,6 +656,31 @@ __device__ __forceinline__ void wgrad_fast_body(const WDesc& d, const unsigned x
         __builtin_amdgcn_sched_barrier(0);
       }
       __syncthreads();
+    };
+    using B0 = std::integral_constant<int, 0>;
+    using B1 = std::integral_constant<int, 1>;
+    int pix0 = pix_begin;
+    if constexpr (TAB && F16 == 0) {
+      if (clean) {   // pairs of iterations whose fetched tiles (pix0 + 32, pix0 + 64) lie wholly below pix_end
+        if (do_db) {
+#pragma unroll 1
+          for (; pix0 + 3 * WBK2 <= pix_end; pix0 += 2 * WBK2) {
+            iteration(pix0, B0{}, std::true_type{}, std::true_type{});
+            iteration(pix0 + WBK2, B1{}, std::true_type{}, std::true_type{});
+          }
+        } else {
+#pragma unroll 1
+          for (; pix0 + 3 * WBK2 <= pix_end; pix0 += 2 * WBK2) {
+            iteration(pix0, B0{}, std::true_type{}, std::false_type{});
+            iteration(pix0 + WBK2, B1{}, std::true_type{}, std::false_type{});
+          }
+        }
+      }
+    }
+    int buf = 0;     // (the clean loop runs whole pairs)
+#pragma unroll 1
+    for (; pix0 < pix_end; pix0 += WBK2) {
+      iteration(pix0, buf, std::false_type{}, std::false_type{});
       buf ^= 1;
     }
   }
@@ -1123,6 +1187,7 @@ extern "C" int ali_conv_bwd_weight(const AliConvGeom* g, const float* x, const f
     if (S < 1) S = 1;
   }
   d.splitk = S;
+  d.no_clean = tuning().no_clean;
   int per = (nkt + S - 1) / S;
   d.pix_per_split = per * wbk;
   d.db = fast ? db : nullptr;
