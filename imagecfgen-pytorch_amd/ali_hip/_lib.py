@@ -131,6 +131,13 @@ SIGNATURES = {
                             c_void_p, c_void_p]),
     "ali_gp_penalty": (c_int32, [c_void_p, c_int32, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "ali_wgan_critic": (c_int32, [c_void_p, c_void_p, c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ali_flow_stats": (c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_float, c_void_p, c_size_t, c_void_p]),
+    "ali_flow_nll": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
+                              c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "ali_flow_map": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32,
+                              c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ali_gumbel_posterior": (c_int32, [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_int32, c_int32,
+                                      c_void_p, c_void_p, c_void_p]),
     "ali_attr_pack": (c_int32, [POINTER(c_void_p), POINTER(c_int32), POINTER(c_int32), c_int32, POINTER(c_void_p), c_int32,
                                 c_int32, c_void_p, c_void_p, c_void_p]),
     "ali_g_input": (c_int32, [c_void_p, c_int32, POINTER(c_void_p), POINTER(c_int32), POINTER(c_int32), POINTER(c_void_p),

@@ -1187,6 +1187,113 @@ def wgan_critic(d_fake, d_real, gscale=1.0, want_grad=True, g_fake=None, g_real=
     return out3, g_fake, g_real
 
 
+FLOW_THETA = 75
+FLOW_SKIP, FLOW_FORWARD, FLOW_INVERSE = 0, 1, 2
+
+
+def _col(t, name):
+    """(pointer, rows, row stride in floats) of an fp32 CUDA column, [N] or [N, 1]; it may be a strided view (one
+    column of an attribute table)"""
+    if not (t.is_cuda and t.dtype == torch.float32 and (t.dim() == 1 or (t.dim() == 2 and t.shape[1] == 1))
+            and t.shape[0] >= 1):
+        raise ValueError(f"{name}: need a non-empty fp32 CUDA column [N] or [N, 1], got {t.dtype} {t.device} "
+                         f"{tuple(t.shape)}")
+    N = t.shape[0]
+    stride = t.stride(0) if N > 1 else 1
+    if stride < 1:
+        raise ValueError(f"{name}: rows must lie at a positive stride, got {stride}")
+    return c_void_p(t.data_ptr()), N, stride
+
+
+def _flow_vec(t, n, name):
+    if t.numel() != n:
+        raise ValueError(f"{name}: need {n} floats, got {t.numel()}")
+    return _chk(t, name)
+
+
+def flow_stats(t, moving=None, momentum=0.1, out=None):
+    """out2 = [mean, unbiased variance] of log ``t`` (a column, see ``_col``); ``moving`` (2 floats: mean, variance) is
+    moved by ``momentum`` towards them in the same launch and then needs N >= 2 (include/ali_hip.h: ali_flow_stats)."""
+    pt, N, st = _col(t, "t")
+    out = torch.empty(2, dtype=torch.float32, device=t.device) if out is None else out
+    ws = workspace(t.device)
+    _lib.check(_lib.load().ali_flow_stats(pt, st, N, _flow_vec(out, 2, "out2"),
+                                          None if moving is None else _flow_vec(moving, 2, "moving"), float(momentum),
+                                          c_void_p(ws.data_ptr()), ws.numel(), _stream()), "ali_flow_stats")
+    return out
+
+
+def flow_nll(t, i, s, theta, cst, stats, wgt=None, gscale=1.0, want_lp=True, want_out4=True, want_grad=False,
+             gtheta=None):
+    """The three log-densities of the MorphoMNIST attribute SCM for rows (t, i, s) -- columns, see ``_col`` -- under
+    ``theta`` [75], ``cst`` [4] and ``stats`` [2] (include/ali_hip.h: ali_flow_nll).  Returns (lp [N, 3] or None,
+    out4 = [-mean(sum lp), mean lp_t, mean lp_i, mean lp_s] or None, gtheta [75] or None): gtheta = sum wgt * d lp /
+    d theta with ``wgt`` [N, 3], or the constant ``gscale`` / N when ``wgt`` is None; ``gtheta``: where to write it."""
+    pt, N, st = _col(t, "t")
+    pi, Ni, si = _col(i, "i")
+    ps, Ns, ss = _col(s, "s")
+    if not N == Ni == Ns:
+        raise ValueError(f"flow_nll: the columns hold {N}, {Ni} and {Ns} rows")
+    dev = t.device
+    lp = torch.empty(N, 3, dtype=torch.float32, device=dev) if want_lp else None
+    out4 = torch.empty(4, dtype=torch.float32, device=dev) if want_out4 else None
+    if gtheta is None and want_grad:
+        gtheta = torch.empty(FLOW_THETA, dtype=torch.float32, device=dev)
+    if wgt is not None and tuple(wgt.shape) != (N, 3):
+        raise ValueError(f"flow_nll: wgt must be [{N}, 3], got {tuple(wgt.shape)}")
+    ws = workspace(dev)
+    _lib.check(_lib.load().ali_flow_nll(pt, st, pi, si, ps, ss, N, _flow_vec(theta, FLOW_THETA, "theta"),
+                                        _flow_vec(cst, 4, "cst"), _flow_vec(stats, 2, "stats"), _opt(wgt, "wgt"),
+                                        float(gscale), _opt(lp), _opt(out4),
+                                        None if gtheta is None else _flow_vec(gtheta, FLOW_THETA, "gtheta"),
+                                        c_void_p(ws.data_ptr()), ws.numel(), _stream()), "ali_flow_nll")
+    return lp, out4, gtheta
+
+
+def flow_map(rows, theta, cst, stats_inv, stats_fwd, modes=(FLOW_SKIP, FLOW_SKIP, FLOW_SKIP), cf_mask=None, val=None,
+             want_noise=False, out=None):
+    """The mechanisms elementwise on ``rows`` [N, 3] (thickness, intensity, slant): per column skip / forward (noise ->
+    value) / inverse (value -> noise), or -- ``cf_mask`` not None -- the counterfactual of observed rows with the
+    columns of the bit mask replaced by ``val`` [N, 3] (include/ali_hip.h: ali_flow_map).  Returns (out [N, 3], the
+    abducted noise [N, 3] or None); ``out`` may be ``rows``."""
+    if rows.dim() != 2 or rows.shape[1] != 3 or rows.shape[0] < 1:
+        raise ValueError(f"flow_map: need [N, 3] rows, got {tuple(rows.shape)}")
+    N = rows.shape[0]
+    out = torch.empty_like(rows) if out is None else out
+    cf = cf_mask is not None
+    if val is not None and val.shape != rows.shape:
+        raise ValueError("flow_map: val must have the rows' shape")
+    if out.shape != rows.shape:
+        raise ValueError("flow_map: out must have the rows' shape")
+    noise = torch.empty_like(rows) if (cf and want_noise) else None
+    _lib.check(_lib.load().ali_flow_map(_chk(rows, "rows"), _opt(val, "val"), _chk(out, "out"), _opt(noise), N,
+                                        int(modes[0]), int(modes[1]), int(modes[2]), int(cf), int(cf_mask or 0),
+                                        _flow_vec(theta, FLOW_THETA, "theta"), _flow_vec(cst, 4, "cst"),
+                                        _flow_vec(stats_inv, 2, "stats_inv"), _flow_vec(stats_fwd, 2, "stats_fwd"),
+                                        _stream()), "ali_flow_map")
+    return out, noise
+
+
+def gumbel_posterior(logits, y, g=None, seed=0, dev_counter=None, offset=0, want_g=False):
+    """Gumbel-max posterior noise [N, C] of observed classes ``y`` [N] (int64) under ``logits`` [N, C], so that
+    ``argmax(logits + noise) == y`` (include/ali_hip.h: ali_gumbel_posterior).  ``g`` [N, C] given, or None: drawn on
+    the device from the counter stream keyed (seed, *dev_counter) at elements ``offset + n * C + c``
+    (``ali_hip.source.gumbel_reference``).  Returns (noise, the g used or None)."""
+    if logits.dim() != 2:
+        raise ValueError(f"gumbel_posterior: need [N, C] logits, got {tuple(logits.shape)}")
+    N, C = logits.shape
+    if not (y.is_cuda and y.dtype == torch.int64 and y.is_contiguous() and y.numel() == N):
+        raise ValueError(f"gumbel_posterior: y must be {N} contiguous int64 CUDA values")
+    if g is not None and g.shape != logits.shape:
+        raise ValueError("gumbel_posterior: g must have the logits' shape")
+    noise = torch.empty_like(logits)
+    g_out = torch.empty_like(logits) if want_g else None
+    _lib.check(_lib.load().ali_gumbel_posterior(_chk(logits, "logits"), c_void_p(y.data_ptr()), _opt(g, "g"),
+                                                int(seed) & (2 ** 64 - 1), _counter_ptr(dev_counter), int(offset), N, C,
+                                                _chk(noise), _opt(g_out), _stream()), "ali_gumbel_posterior")
+    return noise, g_out
+
+
 def softmax_xent(logit, target, gscale=1.0, want_grad=True, want_pred=False, hits_accum=None):
     """Cross-entropy of [B, C] logits against probability rows, gradient, arg-max and hit count in one launch
     (include/ali_hip.h: ali_softmax_xent).  Returns (out2 = [mean loss, hits] device tensor, glogit or None,

@@ -73,6 +73,22 @@ def uniform_reference(seed, counter, n, offset=0):
     return torch.from_numpy((k / 16777216.0).astype(np.float32))
 
 
+_GUMBEL_STREAM = 0x47554D42454C3031           # csrc/flow.hip: kGumbelStream
+
+
+def gumbel_reference(seed, counter, n, offset=0):
+    """fp64 host evaluation of the Gumbel(0, 1) draws of ``ali_gumbel_posterior(g=NULL, seed, &counter, offset, ...)``:
+    a float64 CPU tensor [n], element e = offset + row * C + class.  g = -log(-log u) with u = (k + 0.5) / 2^24
+    strictly inside (0, 1), k the top 24 bits of ``mix64(key ^ e)`` under the latent key mixed once more with the
+    stream's constant.  k is exact on both sides; the device evaluates the logarithms in fp64 too and rounds g to fp32
+    once, so ``gumbel_reference(...).float()`` is what it stores, up to the last bit of the device's log."""
+    key = _mix64_int(_mix64_int(_mix64_int(int(seed)) ^ (int(counter) * _COUNTER_MUL & _M64)) ^ _LATENT_STREAM)
+    key = _mix64_int(key ^ _GUMBEL_STREAM)
+    e = np.arange(n, dtype=np.uint64) + np.uint64(int(offset) & _M64)
+    k = (_mix64(np.uint64(key) ^ e) >> np.uint64(40)).astype(np.float64)
+    return torch.from_numpy(-np.log(-np.log((k + 0.5) / 16777216.0)))
+
+
 class DeviceDataset:
     """A MorphoMNIST-style data set resident in device memory, for ``AliStepper.step_indexed``.
 

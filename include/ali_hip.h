@@ -507,6 +507,68 @@ int ali_gp_penalty(const float* g0, int32_t B, int64_t P, float lambda, float* o
 int ali_wgan_critic(const float* d_fake, const float* d_real, int32_t B, float gscale, float* out3, float* g_fake,
                     float* g_real, ali_stream_t stream);
 
+/* The MorphoMNIST attribute SCM (attribute_scms/mnist.py, attribute_scms/_flows.py: the statement) and the Gumbel-max
+ * posterior of the conditional categoricals (attribute_scms/causal_module.py); csrc/flow.hip.
+ *
+ * theta: the trainable state, ALI_FLOW_THETA = 75 floats
+ *   gamma, beta | W1[10] b1[10] W2[2][10] b2[2] | uw[8] uh[8] ud[7] ul[8]
+ *   (BatchNorm of log thickness | Linear(1,10) -> ReLU -> Linear(10,2) = (mean, log_scale) of the intensity's affine
+ *   flow given the raw thickness | raw widths, heights, knot derivatives, lambdas of the slant's rational-linear spline,
+ *   8 bins on [-3, 3]^2).  cst: 4 floats {i_min, i_max - i_min, s_min, s_max - s_min}.  stats: 2 device floats {mean,
+ *   variance} of log thickness, a batch's (ali_flow_stats) or the moving buffers.  eps = 1e-5; g = relu(gamma) + 1e-6.
+ *   Rows are evaluated in fp64 and rounded once; all sums are fp64 in a fixed order (threads strided over rows, lanes,
+ *   waves, blocks ascending in the block that arrives last), no float atomics: the same inputs give the same bits.
+ *   ws >= ALI_WS_RESERVED + 8 * 103 * 64 bytes serves every entry; the arrival counter (last int of the reserved head)
+ *   is left at zero.
+ *
+ * ali_flow_stats: out2 = {mean, unbiased variance} of log t[n * stride], n < N.  moving (optional, 2 floats {mean,
+ *   variance}): moving <- (1 - momentum) * moving + momentum * out2 in the same launch; N < 2 is then ALI_ERR_BAD_ARG
+ *   before any launch (torch yields NaN statistics there and poisons the buffers).  Without moving, N == 1 gives a NaN
+ *   variance as torch does.
+ *
+ * ali_flow_nll: the three log-densities of rows (t, i, s) -- columns with row strides st, si, ss (in floats):
+ *   thickness  x1 = log t; u = (x1 - m) rsqrt(v + eps) g + beta;  lp = N(u) - x1 + log g - log(v + eps) / 2
+ *   intensity  p = clamp((i - i_min) / i_rng, FLT_MIN, 1 - FLT_EPSILON); w = log p - log1p(-p);
+ *              h = relu(W1 t + b1); (mean, a) = W2 h + b2; ls = clamp(a, -5, 3); u = (w - mean) exp(-ls);
+ *              lp = N(u) - ls + softplus(-w) + softplus(w) - log i_rng
+ *   slant      q = (s - s_min) / s_rng; u = spline^-1(q);  lp = N(u) + log(du/dq) - log s_rng
+ *   with N(u) = -u^2 / 2 - log(2 pi) / 2.  lp [N][3] (optional); out4 (optional) = {-mean_n(lp_t + lp_i + lp_s),
+ *   mean lp_t, mean lp_i, mean lp_s}; gtheta [75] (optional) = sum_n sum_j wgt[n][j] * d lp[n][j] / d theta, wgt a
+ *   [N][3] device array or, when NULL, the constant gscale / N.  The statistics depend on data alone and carry no
+ *   gradient; gamma and the hidden units are gated by their ReLU; the clamp of a passes the gradient straight through.
+ *
+ * ali_flow_map: the mechanisms elementwise on rows in [N][3] -> out [N][3] (thickness, intensity, slant).  Per column
+ *   ALI_FLOW_SKIP (copied through), ALI_FLOW_FORWARD (noise -> value) or ALI_FLOW_INVERSE (value -> noise); the
+ *   intensity's context is the thickness VALUE of the row: the column's output when it runs forward, its input
+ *   otherwise.  Inverse BatchNorm reads stats_inv, forward BatchNorm stats_fwd (the moving buffers).  The spline is
+ *   the identity outside [-3, 3]; sigmoid's output is clamped like p above.
+ *   cf != 0 (the modes are ignored): in = observed rows; columns named in cf_mask (bit 0 thickness, 1 intensity, 2
+ *   slant) take val [N][3], every other column is forward(inverse(observed | observed parents) | counterfactual
+ *   parents), thickness before intensity; the abducted noise goes to noise_out [N][3] (optional).  val may be NULL
+ *   when cf_mask == 0.  out may be in.
+ *
+ * ali_gumbel_posterior: logits [N][C], y [N] (int64, in [0, C)), 1 <= C <= 4096, one wave per row:
+ *   noise[n][y] = g_y + lse(logits_n) - logit_y  (lse max-shifted, fp64)
+ *   noise[n][l] = -log(exp(-g_l - logit_l) + exp(-g_y - logit_y)) - logit_l
+ *   so that argmax_l(logits + noise) = y.  g [N][C] ~ Gumbel(0, 1) is read, or, when NULL, drawn from the counter RNG
+ *   of ali_normal_fill under a key of its own: g = -log(-log u), u = (k + 0.5) / 2^24 strictly inside (0, 1), k the
+ *   top 24 bits of the hash of element offset + n * C + l of the stream keyed by (seed, *dev_counter; may be NULL).
+ *   The g used is stored to g_out (optional).  ali_hip.source.gumbel_reference is the recipe in fp64.  A y outside
+ *   [0, C) is not checked (it is device data): such a row gets NaN and no out-of-bounds access is made. */
+#define ALI_FLOW_THETA 75
+typedef enum { ALI_FLOW_SKIP = 0, ALI_FLOW_FORWARD = 1, ALI_FLOW_INVERSE = 2 } AliFlowMode;
+int ali_flow_stats(const float* t, int64_t stride, int64_t N, float* out2, float* moving, float momentum, void* ws,
+                   size_t ws_bytes, ali_stream_t stream);
+int ali_flow_nll(const float* t, int64_t st, const float* i, int64_t si, const float* s, int64_t ss, int64_t N,
+                 const float* theta, const float* cst, const float* stats, const float* wgt, float gscale, float* lp,
+                 float* out4, float* gtheta, void* ws, size_t ws_bytes, ali_stream_t stream);
+int ali_flow_map(const float* in, const float* val, float* out, float* noise_out, int64_t N, int32_t mode_t,
+                 int32_t mode_i, int32_t mode_s, int32_t cf, int32_t cf_mask, const float* theta, const float* cst,
+                 const float* stats_inv, const float* stats_fwd, ali_stream_t stream);
+int ali_gumbel_posterior(const float* logits, const int64_t* y, const float* g, uint64_t seed,
+                         const int64_t* dev_counter, uint64_t offset, int32_t N, int32_t C, float* noise, float* g_out,
+                         ali_stream_t stream);
+
 /* Attribute plumbing of one batch (mnist.py:47-55, audio_mnist.py:203-210, whalecalls.py:455): idx[b*n_cat + j] =
  * argmax of categorical attribute j (one-hot rows of n_classes[j] floats, or int32 when cat_is_int[j]; first maximum
  * like torch.argmax); cont[b*n_cont + j] = cont_in[j][b]. */
