@@ -138,6 +138,12 @@ SIGNATURES = {
                               c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ali_gumbel_posterior": (c_int32, [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_int32, c_int32,
                                       c_void_p, c_void_p, c_void_p]),
+    "ali_mse": (c_int32, [c_void_p, c_void_p, c_int64, c_float, c_int32, c_void_p, c_void_p, c_void_p, c_size_t,
+                          c_void_p]),
+    "ali_cf_recon": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_int32,
+                               c_void_p, c_void_p]),
+    "ali_oracle_scores": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                    c_void_p]),
     "ali_attr_pack": (c_int32, [POINTER(c_void_p), POINTER(c_int32), POINTER(c_int32), c_int32, POINTER(c_void_p), c_int32,
                                 c_int32, c_void_p, c_void_p, c_void_p]),
     "ali_g_input": (c_int32, [c_void_p, c_int32, POINTER(c_void_p), POINTER(c_int32), POINTER(c_int32), POINTER(c_void_p),

@@ -4,7 +4,7 @@ A stack (``Encoder.layers``, ``Generator.layers``, ``Discriminator.dx/dz/dxz``;
 reference image_scms/mnist.py:30-40,63-74,98-136) is parsed once into *stages*
 
     [Dropout2d] [BatchNorm2d] [Dropout2d]  ->  Conv2d | ConvTranspose2d | Linear(+Unflatten) | Flatten+Linear
-                                           ->  LeakyReLU | Tanh
+                                           ->  LeakyReLU | ReLU | Tanh
 
 and executed as ONE autograd node: forward runs the NHWC kernels stage by stage,
 backward is hand scheduled -- the activation derivative of stage i-1 (and the
@@ -123,6 +123,10 @@ class ChainPlan:
                 if i + 1 < len(mods) and isinstance(mods[i + 1], nn.LeakyReLU):
                     st.act, st.slope = ACT_LEAKY, float(mods[i + 1].negative_slope)
                     i += 1
+                elif i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU):
+                    # LeakyReLU with slope 0: max(v, 0) forward, y > 0 ? 1 : 0 backward (0 at exactly 0, as torch's)
+                    st.act, st.slope = ACT_LEAKY, 0.0
+                    i += 1
                 elif i + 1 < len(mods) and isinstance(mods[i + 1], nn.Tanh):
                     st.act = ACT_TANH
                     i += 1
@@ -186,6 +190,10 @@ class ChainPlan:
             if st.kind == "flat":             # the Linear's [O][C*h*w] storage read as a Conv2d weight [O][C][h][w]
                 O, T = w.shape[0], hw[0] * hw[1]
                 C = w.shape[1] // T
+                if T > FLAT_TAPS:             # a 1x1 GEMM over T*C channels: [O][1][T*C] and its transpose [T*C][1][O]
+                    if which == "fwd":        # (the same permutation as below; cin_stride == T*C: nothing is padded)
+                        return ops.pack_weights(w.detach(), buf(O, 1, T * C), O, T, C, C, C * T, 1, T)
+                    return ops.pack_weights(w.detach(), buf(T * C, 1, O), T, C, O, O, 1, T, C * T)
                 if which == "fwd":            # [O][T][Cpad]
                     return ops.pack_weights(w.detach(), buf(O, T, cin_stride), O, T, C, cin_stride, C * T, 1, T)
                 out = buf(cin_stride, T, O, zero=True)             # [Cpad][T][O]; rows >= C stay zero
@@ -272,6 +280,16 @@ def _out_shape(st: Stage, B, H, W, C):
     return B, 1, 1, m.out_features       # Linear, and Flatten + Linear: the whole map is the kernel
 
 
+FLAT_TAPS = 28      # the conv kernels take at most 28 taps (csrc/ali_common.h: kMaxTaps)
+
+
+def flat_gemm(st: Stage) -> bool:
+    """A Flatten + Linear on a map of more than ``FLAT_TAPS`` positions: the NHWC map [B,h,w,C] (unpadded) already is
+    the row [B,1,1,h*w*C], so the stage runs as a 1x1 GEMM over h*w*C input channels on weights permuted to that
+    order (train_morphomnist_ae.py:23-24, a 7 x 7 map)."""
+    return st.kind == "flat" and st.hw is not None and st.hw[0] * st.hw[1] > FLAT_TAPS
+
+
 def resolve_flat(st: Stage, in_shape, c_log: int):
     """A "flat" stage meets its input map [B,h,w,Cp] with ``c_log`` real channels: fixes ``st.hw`` (it decides the
     weight view and the packs) or raises when the Linear was built for another map."""
@@ -279,8 +297,11 @@ def resolve_flat(st: Stage, in_shape, c_log: int):
     if st.mod.in_features != c_log * H * W:
         raise ValueError(f"ali_hip.chain: Flatten + Linear(in_features={st.mod.in_features}) on a {c_log} x {H} x {W} "
                          f"map ({c_log * H * W} features)")
-    if H * W > 28:
-        raise NotImplementedError(f"ali_hip.chain: Flatten of a {H} x {W} map (the conv kernels take at most 28 taps)")
+    if H * W > FLAT_TAPS and (in_shape[3] != c_log or st.pre):
+        # (read as one row, the map has no channel axis left for padding, a Dropout2d mask or BatchNorm statistics)
+        raise NotImplementedError(f"ali_hip.chain: Flatten of a {H} x {W} map with padded channels ({c_log} of "
+                                  f"{in_shape[3]}) or pre-ops {st.pattern}: a map of more than {FLAT_TAPS} positions "
+                                  f"is read as one row")
     st.hw = (H, W)
 
 
@@ -307,6 +328,8 @@ def _geom(st: Stage, xin_shape, out_shape):
         return ops.geom(B, H, W, C, P, Q, K, m.kernel_size[0], m.kernel_size[1], m.stride[0], m.padding[0])
     if st.kind == "convT":   # x := convT output, y := convT input
         return ops.geom(B, P, Q, K, H, W, C, m.kernel_size[0], m.kernel_size[1], m.stride[0], m.padding[0])
+    if flat_gemm(st):        # the whole map is one row of H*W*C channels
+        return ops.geom(B, 1, 1, H * W * C, 1, 1, K, 1, 1, 1, 0)
     if st.kind == "flat":    # the (H, W) kernel covers the map once
         return ops.geom(B, H, W, C, 1, 1, K, H, W, 1, 0)
     # linear: 1x1 conv on the [B,1,1,I] map with O output channels
@@ -320,12 +343,14 @@ class Route(namedtuple("Route", "fwd wgrad wgrad_fold dgrad planes fold_ok bn_le
 
     fwd         "head" (GEMV) | "tconv1" (direct one-channel kernel) | "scatter" (scatter form, one launch) |
                 "scatter_gemm" (1x1 GEMM + col2im) | "convT" | "conv" (implicit GEMMs; a Linear is a 1x1 "conv", a
-                Flatten + Linear an (h, w) "conv" on all three passes).  Only
+                Flatten + Linear an (h, w) "conv" on all three passes) | "flat_gemm" (Flatten + Linear on a map of more
+                than 28 positions: a 1x1 "conv" over h*w*C channels, ``flat_gemm``; also its ``dgrad``).  Only
                 the GEMMs have an epilogue: a "head" / "scatter*" stage that has to fold the next stage's mask or leave
                 BatchNorm partials runs the GEMM of its kind instead.
     wgrad       (weight-gradient path, bias-gradient path): "head" | "first_direct" (ali_tconv1_wgrad over the <= 8
                 input planes) | "conv" | "tconv1" | "convT_scatter" (pixel contraction; the GEMM when the operands or
-                the workspace do not allow it) | "convT" | "linear" | "linear_repack"; the bias gradient is "fused"
+                the workspace do not allow it) | "convT" | "linear" | "linear_repack" | "flat_repack" (computed in the
+                "flat_gemm" pack's order, re-packed into the Linear's own layout right away); the bias gradient is "fused"
                 into that launch, a "colsum" of its own, the "unflat" column sum in Unflatten order, or None (no bias).
     wgrad_fold  the same when the launches are deferred to a FoldQueue: a "first_direct" stage with 4-aligned channels
                 then rides the pass's combined weight-gradient launch as one more GEMM job (its 200 x 32 GEMM fills gaps
@@ -343,6 +368,10 @@ def route(st: Stage, in_shape, c_log: int) -> Route:
     m, Cp = st.mod, in_shape[3]
     taps = (1 if st.kind == "linear" else in_shape[1] * in_shape[2] if st.kind == "flat"
             else m.kernel_size[0] * m.kernel_size[1])
+    if st.kind == "flat" and taps > FLAT_TAPS:
+        return Route("flat_gemm", ("flat_repack", None if m.bias is None else "colsum"),
+                     ("flat_repack", None if m.bias is None else "colsum"), dgrad="flat_gemm", planes=None,
+                     fold_ok=st.act in (ACT_NONE, ACT_LEAKY), bn_leave=False, bn_reduce=False)
     # ConvTranspose2d(C -> 1), stride 1, no output padding: served by the direct one-channel kernels
     tconv1 = (st.kind == "convT" and m.out_channels == 1 and m.stride[0] == 1 and m.output_padding[0] == 0
               and m.kernel_size[0] <= 5 and Cp in (32, 64, 128, 256))
@@ -628,6 +657,8 @@ def _launch_fwd(plan: ChainPlan, st: Stage, sv, folded, bn_fwd, out_ld: int, jma
             ep.refs["mask"] = jmask
         if st.index == 0 and st.kind == "conv" and c_log < Cp:
             ep.in_ch_live = c_log          # channel padding of a first layer: kernels that can skip it do
+        if path == "flat_gemm":       # (unpadded: every one of the row's H*W*Cp channels carries data)
+            Cp = c_log = H * W * Cp
         if path == "convT":
             ops.conv_bwd_data(sv.geom, t, plan.packed(st, "fwd", Cp), y, ep, live=(None, c_log))
         else:
@@ -719,6 +750,12 @@ def _param_grads(st: Stage, sv, g_pre, ld: int, grads, grad_dst, fold):
     elif db_path == "colsum":
         grads[id(m.bias)] = ops.colsum(B * P * Q, K, K, g_pre, out=grad_dst.get(id(m.bias)))
     dw = grads[id(m.weight)] = grad_dst[id(m.weight)] if id(m.weight) in grad_dst else torch.empty_like(m.weight)
+    if path == "flat_repack":             # rows in the pack's t*C + c order, re-packed into [O][C*h*w] right away
+        O, I, T = m.out_features, m.in_features, H * W
+        tmp = torch.empty(O, I, device=dw.device)
+        ops.conv_bwd_weight(g, sv.t, g_pre, tmp, I, O, I, 1, 0)      # (not deferred)
+        ops.pack_weights(tmp, dw, O, I // T, T, T, I, 1, I // T)
+        return
     if st.kind == "flat":                 # written in the view's layout [O][C][h][w] = the Linear's own [O][C*h*w]
         ops.conv_bwd_weight(g, sv.t, g_pre, dw, c_in, K, dw.stride(0), H * W, 1, db=fused_db, dy_ld=ld, defer=fold)
         return
@@ -815,7 +852,9 @@ def _data_grad(plan: ChainPlan, st: Stage, sv, g_pre, ld: int, pact, pslope, wan
         ops.conv_fwd(g, g_pre, plan.packed(st, "dgrad", Cp), gt, ep, live=(None, sv.c_log))
         yield
     else:
-        ops.conv_bwd_data(g, g_pre, plan.packed(st, "dgrad", Cp), gt, ep, in_ld=ld, live=(sv.c_log, None))
+        wc = H * W * Cp if rt.dgrad == "flat_gemm" else Cp          # (flat_gemm: the map is one unpadded row)
+        ops.conv_bwd_data(g, g_pre, plan.packed(st, "dgrad", wc), gt, ep, in_ld=ld,
+                          live=(wc if rt.dgrad == "flat_gemm" else sv.c_log, None))
         yield
     if bn is None:
         return gt
@@ -957,7 +996,9 @@ def chain_tangent_gen(plan: ChainPlan, saved, u0: torch.Tensor):
         ep = ops.epilogue(dact_y=sv.y if st.act != ACT_NONE else None, dact=st.act, dslope=st.slope)
         if st.index == 0 and sv.c_log < Cp:
             ep.in_ch_live = sv.c_log
-        ops.conv_fwd(sv.geom, us[-1], plan.packed(st, "fwd", Cp), u, ep, live=(sv.c_log, None))
+        flat = sv.route.fwd == "flat_gemm"                        # (the map is one unpadded row of geom.C channels)
+        ops.conv_fwd(sv.geom, us[-1], plan.packed(st, "fwd", sv.geom.C if flat else Cp), u, ep,
+                     live=(sv.geom.C if flat else sv.c_log, None))
         yield
         us.append(u)
     return us

@@ -1671,3 +1671,57 @@ def cf_select(logit, metric, target, pred=None, order=None, n_hit=None):
                                  _i32(pred, "pred", S), _i32(order, "order", S), _i32(n_hit, "n_hit", 1), _stream()),
                "ali_cf_select")
     return pred, order, n_hit
+
+
+# ---------------------------------------------------------------------- the counterfactual metrics (csrc/cfmetrics.hip)
+def mse(y, x, gscale=1.0, want_grad=True, tanh_out=False):
+    """``mean((y - x)^2)`` over all elements as a 0-d device tensor, and its gradient with respect to ``y`` times
+    ``gscale`` -- with ``tanh_out`` times ``1 - y^2``: the gradient of the pre-activation of the tanh that produced
+    ``y`` -- in one launch (include/ali_hip.h: ali_mse).  Returns (loss, grad or None)."""
+    lib = _lib.load()
+    if y.shape != x.shape or y.numel() == 0:
+        raise ValueError(f"mse: need two non-empty tensors of one shape, got {tuple(y.shape)} and {tuple(x.shape)}")
+    loss = torch.empty(1, dtype=torch.float32, device=y.device)
+    grad = torch.empty_like(y) if want_grad else None
+    ws = workspace(y.device)
+    _lib.check(lib.ali_mse(_chk(y, "y"), _chk(x, "x"), y.numel(), float(gscale), int(bool(tanh_out)), _chk(loss),
+                           _opt(grad), c_void_p(ws.data_ptr()), ws.numel(), _stream()), "ali_mse")
+    return loss.reshape(()), grad
+
+
+def cf_recon(x, recon, orig, target, out=None):
+    """The reconstruction columns of morphomnist_cf_metrics.py for B rows (include/ali_hip.h: ali_cf_recon): x [B, N],
+    recon [A, B, N] (any plane and row strides, unit element stride; plane A - 1 is the all-classes autoencoder), orig
+    and target int32 [B].  Returns [B, 4] = (l1, o_rec, t_rec, all_rec); a label outside [0, A - 1) gives NaN."""
+    lib = _lib.load()
+    if x.dim() != 2 or recon.dim() != 3 or tuple(recon.shape[1:]) != tuple(x.shape) or recon.shape[0] < 2:
+        raise ValueError(f"cf_recon: need x [B, N] and recon [A >= 2, B, N], got {tuple(x.shape)} and "
+                         f"{tuple(recon.shape)}")
+    A, B, N = recon.shape
+    if recon.stride(2) != 1 and N > 1:
+        raise ValueError("cf_recon: the elements of a recon row must be contiguous")
+    ld_row = recon.stride(1) if B > 1 else max(recon.stride(1), N)
+    if out is None:
+        out = torch.empty(B, 4, dtype=torch.float32, device=x.device)
+    _lib.check(lib.ali_cf_recon(_chk(x, "x"), _ptr(recon), ld_row, recon.stride(0), _i32(orig, "orig", B),
+                                _i32(target, "target", B), A, B, N, _chk(out, "out"), _stream()), "ali_cf_recon")
+    return out
+
+
+def oracle_scores(pred, ox, ocf):
+    """The oracle columns of mnist_oracle_scores.py for B rows (include/ali_hip.h: ali_oracle_scores): pred int32 [B],
+    ox and ocf [J, B, C] logits of the J oracles on the originals and on the counterfactuals (contiguous [B, C] planes,
+    the same plane stride in both: two halves of one buffer will do).  Returns (os int32
+    [B, J] = pred == ocf's first arg-max, lvs [B, J] = the Jensen-Shannon divergence of the two softmaxes)."""
+    lib = _lib.load()
+    if ox.dim() != 3 or ox.shape != ocf.shape:
+        raise ValueError(f"oracle_scores: need two [J, B, C] logit tensors, got {tuple(ox.shape)} and {tuple(ocf.shape)}")
+    J, B, C = ox.shape
+    for t in (ox, ocf):
+        if not (t.is_cuda and t.dtype == torch.float32 and t[0].is_contiguous() and t.stride(0) == ox.stride(0)):
+            raise ValueError("oracle_scores: need fp32 CUDA logits with contiguous [B, C] planes and one plane stride")
+    os_ = torch.empty(B, J, dtype=torch.int32, device=ox.device)
+    lvs = torch.empty(B, J, dtype=torch.float32, device=ox.device)
+    _lib.check(lib.ali_oracle_scores(_i32(pred, "pred", B), _ptr(ox), _ptr(ocf), max(ox.stride(0), B * C), J, B, C,
+                                     _i32(os_, "os"), _chk(lvs, "lvs"), _stream()), "ali_oracle_scores")
+    return os_, lvs

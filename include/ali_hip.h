@@ -569,6 +569,34 @@ int ali_gumbel_posterior(const float* logits, const int64_t* y, const float* g, 
                          const int64_t* dev_counter, uint64_t offset, int32_t N, int32_t C, float* noise, float* g_out,
                          ali_stream_t stream);
 
+/* The counterfactual metrics family (train_morphomnist_ae.py, morphomnist_cf_metrics.py, mnist_oracle_scores.py);
+ * csrc/cfmetrics.hip.  fp32 in and out, fp64 sums in a fixed order, no float atomics: bit-identical from run to run.
+ *
+ * ali_mse: loss[0] = mean_i (y_i - x_i)^2 over n elements;  grad[i] (optional) = 2 * gscale * (y_i - x_i) / n, times
+ *   1 - y_i^2 when tanh_out != 0 (y is then the output of a tanh and grad the gradient of its pre-activation).  One
+ *   launch of min(ceil(n / 1024), 1024) blocks with 16-byte accesses when y, x and grad are 16-byte aligned, of
+ *   min(ceil(n / 256), 1024) blocks element by element otherwise.  ws >= ALI_WS_RESERVED + 8 * min(ceil(n / 256),
+ *   1024) bytes serves both; the arrival counter is the last int of the reserved head and is left at zero.
+ * ali_cf_recon: x [B][N] contiguous; recon [A][B][N], element (a, b, j) at a * ld_plane + b * ld_row + j; orig,
+ *   target [B] int32 device labels; out [B][4] (16-byte aligned) =
+ *     { sum_j |x|,  sum_j (x - recon[orig])^2,  sum_j (x - recon[target])^2,  sum_j (recon[target] - recon[A-1])^2 }
+ *   (plane A - 1: the autoencoder of all classes).  A label outside [0, A - 1) indexes nothing: the columns that
+ *   depend on it are NaN.  One wave per row, no workspace.
+ * ali_oracle_scores: pred [B] int32; ox, ocf [J][B][C] logits of J oracles on the original and on the counterfactual,
+ *   element (j, b, c) of either at j * ld_j + b * C + c, C >= 1.  os[b][j] = (pred[b] == first arg-max of
+ *   ocf[j][b][:]);  lvs[b][j] = the Jensen-Shannon divergence 0.5 * (KL(p, m) + KL(q, m)), p = softmax(ox[j][b]),
+ *   q = softmax(ocf[j][b]) (max-shifted, fp64), m = (p + q) / 2, KL(a, m) = sum_c a_c * (log(a_c + 1e-6) -
+ *   log(m_c + 1e-6)).  One wave per (b, j).
+ * Non-finite inputs (what falls out, untested): comparisons with NaN are false, so a NaN logit never becomes the
+ *   arg-max -- torch.argmax would pick it -- and a row of NaN alone gives os = 0; its lvs is NaN.  NaN or infinite
+ *   images give NaN sums. */
+int ali_mse(const float* y, const float* x, int64_t n, float gscale, int32_t tanh_out, float* loss, float* grad,
+            void* ws, size_t ws_bytes, ali_stream_t stream);
+int ali_cf_recon(const float* x, const float* recon, int64_t ld_row, int64_t ld_plane, const int32_t* orig,
+                 const int32_t* target, int32_t A, int32_t B, int32_t N, float* out, ali_stream_t stream);
+int ali_oracle_scores(const int32_t* pred, const float* ox, const float* ocf, int64_t ld_j, int32_t J, int32_t B,
+                      int32_t C, int32_t* os, float* lvs, ali_stream_t stream);
+
 /* Attribute plumbing of one batch (mnist.py:47-55, audio_mnist.py:203-210, whalecalls.py:455): idx[b*n_cat + j] =
  * argmax of categorical attribute j (one-hot rows of n_classes[j] floats, or int32 when cat_is_int[j]; first maximum
  * like torch.argmax); cont[b*n_cont + j] = cont_in[j][b]. */
