@@ -26,7 +26,7 @@ from . import ops
 from .chain import chain_backward, chain_forward, get_plan, run_chain
 from .classify import nhwc_input
 from .graphs import GraphCache
-from .step import FlatGroup
+from .trainer import FlatGroup, Stepper
 
 
 def _latent_rows(z: torch.Tensor, latent: int) -> torch.Tensor:
@@ -65,7 +65,7 @@ def _reconstruct(E, G, x_nhwc, out_rows=None):
     return y.reshape(y.shape[0], -1)
 
 
-class AeStepper:
+class AeStepper(Stepper):
     """One iteration of train_morphomnist_ae.py:100-104, hand scheduled (no autograd engine):
 
         opt.zero_grad(); loss = (x - G(E(x))).square().mean(); loss.backward(); opt.step()
@@ -79,8 +79,6 @@ class AeStepper:
 
     def __init__(self, E, G, lr=1e-4, betas=(0.5, 0.9), eps=1e-8, capture=False):
         self.E, self.G = E, G
-        self.capture = capture
-        self._graphs = GraphCache()
         self.on_device = next(E.parameters()).is_cuda
         if self.on_device != next(G.parameters()).is_cuda:
             raise ValueError("AeStepper: E and G live on different devices")
@@ -89,10 +87,9 @@ class AeStepper:
             self.pE, self.pG = get_plan(E.chain_view()), get_plan(G.chain_view())
             self.latent = G.fc.in_features
             self.opt = FlatGroup(params, lr, betas, eps)
-            for plan in (self.pE, self.pG):
-                plan.cache.make_static()
         else:
             self.opt = torch.optim.Adam(params, lr=lr, betas=betas, eps=eps)
+        self._adopt([(self.opt, [self.pE, self.pG])] if self.on_device else [], capture)
 
     @torch.no_grad()
     def step(self, x):
@@ -101,15 +98,7 @@ class AeStepper:
         if not self.on_device:
             return self._step_torch(x)
         x = x.reshape((-1, 1) + tuple(x.shape[-2:])).float()
-        if not self.capture:
-            return self._step(x)
-        return self._graphs(self._step, (x,), (self.E.training, self.G.training), self.opt.state_tensors(),
-                            self._restored)
-
-    def _restored(self):
-        self.opt.resync()
-        for plan in (self.pE, self.pG):
-            plan.cache.refresh()
+        return self._run(self._step, (x,), (self.E.training, self.G.training))
 
     def _step(self, x):
         B, latent = x.shape[0], self.latent
@@ -121,9 +110,7 @@ class AeStepper:
         gz, _ = chain_backward(self.pG, sG, g_pre.reshape(y.shape), latent, True, True, views, gy_pre=True)
         gz = gz.reshape(B, -1)[:, :latent].contiguous().reshape(z.shape)
         chain_backward(self.pE, sE, gz, 1, False, True, views)
-        self.opt.adam()
-        for plan in (self.pE, self.pG):
-            plan.cache.refresh()
+        self._update(self.opt)
         return {"loss": loss}
 
     def _step_torch(self, x):

@@ -19,7 +19,8 @@ import torch.nn.functional as F
 from . import ops
 from .chain import chain_backward, chain_forward, get_plan
 from .graphs import GraphCache
-from .step import FlatGroup, GeneratorSampler
+from .step import GeneratorSampler
+from .trainer import FlatGroup, Stepper
 
 
 def nhwc_input(x: torch.Tensor) -> torch.Tensor:
@@ -28,7 +29,7 @@ def nhwc_input(x: torch.Tensor) -> torch.Tensor:
     return F.pad(x, (0, (-x.shape[-1]) % 4)).contiguous()
 
 
-class ClassifierStepper:
+class ClassifierStepper(Stepper):
     """One training step of a classifier stack, hand scheduled:
 
         opt.zero_grad(); pred = model(x); loss = CrossEntropyLoss()(pred, y); loss.backward(); opt.step()
@@ -40,15 +41,13 @@ class ClassifierStepper:
 
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, capture=False):
         self.model = model
-        self.capture = capture
-        self._graphs = GraphCache()
         self.on_device = next(model.parameters()).is_cuda
         if self.on_device:
             self.plan = get_plan(model)
             self.opt = FlatGroup(list(model.parameters()), lr, betas, eps)
-            self.plan.cache.make_static()
         else:
             self.opt = torch.optim.Adam(model.parameters(), lr=lr, betas=betas, eps=eps)
+        self._adopt([(self.opt, [self.plan])] if self.on_device else [], capture)
 
     @torch.no_grad()
     def step(self, x, y):
@@ -56,14 +55,7 @@ class ClassifierStepper:
             raise ValueError("ClassifierStepper.step: the batch and the model live on different devices")
         if not self.on_device:
             return self._step_torch(x, y)
-        y = y.float()
-        if not self.capture:
-            return self._step(x, y)
-        return self._graphs(self._step, (x, y), (self.model.training,), self.opt.state_tensors(), self._restored)
-
-    def _restored(self):
-        self.opt.resync()
-        self.plan.cache.refresh()
+        return self._run(self._step, (x, y.float()), (self.model.training,))
 
     def _step(self, x, y):
         B = x.shape[0]
@@ -71,8 +63,7 @@ class ClassifierStepper:
         logits, saved = chain_forward(self.plan, nhwc_input(x), self.model.training, c_log, True)
         out2, glogit, _ = ops.softmax_xent(logits.reshape(B, -1), y.contiguous())
         chain_backward(self.plan, saved, glogit.reshape(logits.shape), c_log, False, True, self.opt.grad_views)
-        self.opt.adam()
-        self.plan.cache.refresh()
+        self._update(self.opt)
         return {"loss": out2[0], "hits": out2[1]}
 
     def _step_torch(self, x, y):

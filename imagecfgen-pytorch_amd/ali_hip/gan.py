@@ -24,8 +24,7 @@ from . import ops
 from . import source as _source
 from .chain import (chain_backward, chain_backward_keep, chain_forward, chain_param_grads, chain_tangent, get_plan,
                     saved_rows, tangent_param_grads)
-from .graphs import GraphCache
-from .step import FlatGroup
+from .trainer import FlatGroup, Stepper, load_module_state_, module_state_cpu
 
 LATENT_DIM = 100
 LATENT_LD = 128          # channel stride of the Generator's input rows: % 32 == 0 -> the GEMM's uniform-tap loop
@@ -96,7 +95,7 @@ def gradient_penalty(disc, interpolates):
     return GradientPenaltyFn.apply(plan, x, *plan.params())
 
 
-class GanStepper:
+class GanStepper(Stepper):
     """One iteration of gans/audio_mnist.py:287-337, hand scheduled (no autograd engine):
 
         if ctr % d_updates_per_g_update == 0:  z ~ N;  loss_G = BCE(D(G(z)), 1) | -D(G(z)).mean();  Adam(G)
@@ -135,7 +134,6 @@ class GanStepper:
         self.G, self.D = G, D
         self.loss_mode, self.penalty_weight = loss_mode, float(penalty_weight)
         self.k = int(d_updates_per_g_update)
-        self.capture = capture
         self.seed = _source.DEFAULT_Z_SEED if seed is None else int(seed)
         self.pG, self.pD = get_plan(G.layers), get_plan(D.layers)
         self.opt_g = FlatGroup(list(G.parameters()), lr, betas, eps)
@@ -148,11 +146,9 @@ class GanStepper:
             self.gp_views[id(p)] = self.gp_grad[off:off + p.numel()].view(p.shape)
             off += p.numel()
         self.gp_weight_views = {id(st.mod.weight): self.gp_views[id(st.mod.weight)] for st in self.pD.stages}
-        for plan in (self.pG, self.pD):
-            plan.cache.make_static()
+        self._adopt([(self.opt_g, [self.pG]), (self.opt_d, [self.pD])], capture)
         self.iter_t = torch.zeros(1, dtype=torch.int64, device=dev)     # iterations done: keys the draws
         self.ctr = 0                                                    # host mirror: decides the G step
-        self._graphs = GraphCache()
 
     # ------------------------------------------------------------------ draws
     def _z(self, given, B, slot, dev):
@@ -173,8 +169,7 @@ class GanStepper:
             out, _, gl = ops.wgan_critic(None, logit.reshape(B), 1.0)
         gx, _ = chain_backward(self.pD, sD, gl.reshape(logit.shape), 1, True, need_params=False, gx_planes=(0,))
         chain_backward(self.pG, sG, _one_plane(gx).reshape(gen.shape), LATENT_DIM, False, True, self.opt_g.grad_views)
-        self.opt_g.adam()
-        self.pG.cache.refresh()
+        self._update(self.opt_g)
         return out[0]
 
     def _d_step_gan(self, B, x_real, x_fake):
@@ -226,35 +221,25 @@ class GanStepper:
             res["loss_D"] = self._d_step_gan(B, x_real, x_fake)
         else:
             res["loss_D"] = self._d_step_wgan(B, x_real, x_fake, None if eps is None else eps.reshape(B).float().contiguous())
-        self.opt_d.adam()
-        self.pD.cache.refresh()
+        self._update(self.opt_d)
         res["DG"], res["DE"] = self._scores(B, x_real, self._z(z_s, B, 2, dev))
         ops.add_i64_multi([self.iter_t], [1])
         return res
 
     # ------------------------------------------------------------------ capture, state
-    def _restored(self):
-        for g, plan in ((self.opt_g, self.pG), (self.opt_d, self.pD)):
-            g.resync()
-            plan.cache.refresh()
-
     @torch.no_grad()
     def step(self, images, z_g=None, z_d=None, z_s=None, eps=None):
         if not images.is_cuda:
             raise ValueError("GanStepper.step: the batch must live on the model's CUDA device")
         do_g = self.ctr % self.k == 0
         self.ctr += 1
-        if not self.capture:
-            return self._iteration(do_g, images, z_g, z_d, z_s, eps)
-        return self._graphs(lambda *a: self._iteration(do_g, *a), (images, z_g, z_d, z_s, eps),
-                            (do_g, self.G.training, self.D.training),
-                            self.opt_g.state_tensors() + self.opt_d.state_tensors() + [self.iter_t], self._restored)
+        return self._run(lambda *a: self._iteration(do_g, *a), (images, z_g, z_d, z_s, eps),
+                         (do_g, self.G.training, self.D.training), [self.iter_t])
 
     def state_dict(self):
         """Resumable checkpoint: the two module state dicts, both Adam states in ``torch.optim.Adam.state_dict()``
         format, the iteration counter and the seed that key the draws.  Tensors are cloned to the CPU."""
-        sd = {f"{n}_state_dict": {k: v.detach().cpu().clone() for k, v in m.state_dict().items()}
-              for n, m in (("G", self.G), ("D", self.D))}
+        sd = {f"{n}_state_dict": module_state_cpu(m) for n, m in (("G", self.G), ("D", self.D))}
         sd.update(optimizer_G=self.opt_g.torch_state_dict(), optimizer_D=self.opt_d.torch_state_dict(),
                   iteration=int(self.iter_t.item()), z_seed=self.seed)
         return sd
@@ -264,9 +249,7 @@ class GanStepper:
         seed is a launch argument: the graphs are dropped)."""
         with torch.no_grad():
             for n, m in (("G", self.G), ("D", self.D)):
-                src = sd[f"{n}_state_dict"]
-                for k, v in m.state_dict().items():
-                    v.copy_(src[k])
+                load_module_state_(m, sd[f"{n}_state_dict"])
             self.opt_g.load_torch_state_dict(sd["optimizer_G"])
             self.opt_d.load_torch_state_dict(sd["optimizer_D"])
             self.ctr = int(sd.get("iteration", 0))

@@ -33,132 +33,7 @@ from . import chain as _chain
 from .chain import (chain_backward, chain_backward_gen, chain_forward, chain_forward_gen, drive, get_plan,
                     run_parallel, slice_saved)
 from .graphs import GraphCache, _Graphed
-
-
-class FlatGroup:
-    """Parameters re-pointed into one flat buffer + flat grad / exp_avg / exp_avg_sq buffers.
-
-    ``layouts`` (optional, {id(param): strides}): the element order a parameter takes inside its segment of the flat
-    buffers -- a dense permutation given as the strides of the (logically unchanged) parameter tensor.  The stepper
-    asks for the forward GEMM's weight layout (`[K][R*S][C]`: torch's channels_last for a Conv2d weight), so that the
-    optimiser step itself leaves the weights in kernel layout and half of the re-pack disappears; Adam is elementwise
-    and does not care.  Gradients, exp_avg and exp_avg_sq use the same order (``*_views``)."""
-
-    def __init__(self, params, lr, betas, eps, layouts=None, twin16=False):
-        """``twin16``: keep an fp16 twin of the whole flat parameter buffer, written by the Adam launch itself (fp16-MFMA
-        path: a conv weight whose segment is laid out as the forward GEMM's pack needs no re-pack launch at all -- the
-        fp32 segment IS the pack and ``flat16``'s segment its twin)."""
-        self.params = list(params)
-        dev = self.params[0].device
-        n = sum(p.numel() for p in self.params)
-        self.n = n
-        self.flat = torch.empty(n, device=dev)
-        self.flat16 = torch.empty(n, dtype=torch.float16, device=dev) if twin16 else None
-        self.grad = torch.zeros(n, device=dev)
-        self.m = torch.zeros(n, device=dev)
-        self.v = torch.zeros(n, device=dev)
-        self.grad_views, self.m_views, self.v_views = {}, [], []
-        layouts = layouts or {}
-        off = 0
-        with torch.no_grad():
-            for p in self.params:
-                k = p.numel()
-                st = layouts.get(id(p))
-
-                def view(buf):
-                    seg = buf[off:off + k]
-                    return seg.view(p.shape) if st is None else torch.as_strided(seg, p.shape, st)
-                w = view(self.flat)
-                w.copy_(p.detach())
-                p.data = w
-                if self.flat16 is not None:      # the segment's twin, found by chain.packed through the parameter
-                    p._ali_flat16 = self.flat16[off:off + k]
-                gv = view(self.grad)
-                p.grad = gv
-                self.grad_views[id(p)] = gv
-                self.m_views.append(view(self.m))
-                self.v_views.append(view(self.v))
-                off += k
-        self.sync16()
-        self.lr, self.betas, self.eps = lr, betas, eps
-        self.steps = 0
-        self.step_t = torch.zeros(1, dtype=torch.int32, device=dev)   # device-side count of completed steps (graph replays)
-        self.arrive = torch.zeros(1, dtype=torch.int32, device=dev) if dev.type == "cuda" else None
-
-    def sync16(self):
-        """re-round the fp16 twin after the parameters were changed by anything but ``adam`` (load_state, restore)"""
-        if self.flat16 is not None:
-            self.flat16.copy_(self.flat)
-
-    def state_tensors(self):
-        """what a pass that must not count (a graph's warm-up) clones and puts back; then ``resync``"""
-        return [self.flat, self.m, self.v, self.step_t]
-
-    def resync(self):
-        """the state tensors were rewritten on the device: the host's step count and the fp16 twin follow"""
-        self.steps = int(self.step_t.item())
-        self.sync16()
-
-    @staticmethod
-    def logical(views):
-        """the buffer behind ``views`` as one flat tensor in the parameters' own (row-major) element order"""
-        return torch.cat([v.reshape(-1) for v in views])
-
-    def grad_logical(self):
-        """the flat gradient in the parameters' own element order (tests, diagnostics)"""
-        return self.logical(list(self.grad_views.values()))
-
-    def load_logical(self, views, flat):
-        off = 0
-        for v in views:
-            v.copy_(flat[off:off + v.numel()].view(v.shape))
-            off += v.numel()
-
-    def adam(self, grad_scale=1.0):
-        self.steps += 1
-        # the kernel runs step step_t + 1 and its last block advances step_t: no launch for the counter
-        ops.adam(self.flat, self.grad, self.m, self.v, self.lr, self.betas[0], self.betas[1], self.eps, self.steps,
-                 dev_step=self.step_t, grad_scale=grad_scale, arrive=self.arrive, p16=self.flat16)
-
-    # torch.optim-like surface for callers that keep the returned optimisers
-    def zero_grad(self):
-        self.grad.zero_()
-
-    def step(self):
-        self.adam()
-
-    def state_dict(self):
-        # the device-side count is the authoritative one: HIP-graph replays do not run the host-side increment
-        self.steps = int(self.step_t.item())
-        return {"step": self.steps, "exp_avg": self.logical(self.m_views), "exp_avg_sq": self.logical(self.v_views),
-                "lr": self.lr, "betas": self.betas, "eps": self.eps}
-
-    def torch_state_dict(self):
-        """this group as a ``torch.optim.Adam.state_dict()`` (per-parameter moments in the parameters' own layout, CPU
-        clones): ``torch.optim.Adam(params, ...).load_state_dict(...)`` takes it"""
-        step = int(self.step_t.item())
-        proto = torch.optim.Adam([torch.zeros(1)], lr=self.lr, betas=tuple(self.betas), eps=self.eps).state_dict()
-        pg = dict(proto["param_groups"][0], params=list(range(len(self.params))))
-        state = {i: {"step": torch.tensor(float(step)), "exp_avg": m.detach().cpu().clone().contiguous(),
-                     "exp_avg_sq": v.detach().cpu().clone().contiguous()}
-                 for i, (m, v) in enumerate(zip(self.m_views, self.v_views))}
-        return {"state": state, "param_groups": [pg]}
-
-    def load_torch_state_dict(self, sd):
-        """inverse of ``torch_state_dict`` (also takes the state dict of a ``torch.optim.Adam`` over the same parameters;
-        parameters without state get zero moments); in place, so captured graphs stay valid"""
-        with torch.no_grad():
-            steps = 0
-            for i, (m, v) in enumerate(zip(self.m_views, self.v_views)):
-                st = sd["state"].get(i)
-                if st is None:
-                    m.zero_(), v.zero_()
-                    continue
-                m.copy_(st["exp_avg"].to(m.device))
-                v.copy_(st["exp_avg_sq"].to(v.device))
-                steps = int(st["step"])
-            self.steps = steps
-            self.step_t.fill_(steps)
+from .trainer import FlatGroup, Stepper, load_module_state_, module_state_cpu
 
 
 class MnistFamily:
@@ -224,6 +99,23 @@ def _plane_count(tables, cont):
     """conv input planes [image | one per embedding table | continuous attributes]: (logical count, padded to 4)"""
     n_log = 1 + len(tables) + (0 if cont is None else cont.shape[1])
     return n_log, (n_log + 3) // 4 * 4
+
+
+def _e_planes(fam, x, idx, cont):
+    """the Encoder's conv input for a batch ``x`` ([B,H,W] or [B,1,H,W]): (planes [B,H,W,Cpad], logical plane count)"""
+    B = x.shape[0]
+    H, W = fam.hw
+    n_log, cpad = _plane_count(fam.e_tables, cont)
+    x0 = ops.assemble_planes(x.reshape(B, H, W).float().contiguous(), idx, [t.detach() for t in fam.e_tables], cont,
+                             B, H, W, cpad)
+    return x0, n_log
+
+
+def _e_plane_grads(fam, g_x0, x0, idx, out_for):
+    """embedding-table gradients from ``g_x0``, the gradient of ``x0`` or of its embedding planes, into ``out_for(table)``"""
+    gofs = 0 if (g_x0 is not None and g_x0.shape[-1] == len(fam.e_tables)) else 1
+    for j, t in enumerate(fam.e_tables):
+        ops.plane_table_grad(g_x0.contiguous(), gofs + j, x0, 1 + j, idx, j, t.shape[0], out=out_for(t))
 
 
 def _g_input(fam, z, onehots, cont, alloc=None):
@@ -818,9 +710,7 @@ class AliStepper:
         """Adopt the weights / buffers of another (e.g. CPU, reference-trained) E, G, D and, optionally, the
         exp_avg / exp_avg_sq / step of their torch.optim.Adam optimisers; kernel-layout copies are refreshed."""
         for src, dst in ((E_src, self.E), (G_src, self.G), (D_src, self.D)):
-            sd = src.state_dict()
-            for k, v in dst.state_dict().items():
-                v.copy_(sd[k])
+            load_module_state_(dst, src.state_dict())
         _chain.drop_pending_batch_counts()      # the adopted num_batches_tracked already include them
         for group, opt, mods in ((self.opt_eg, opt_e, (E_src, G_src)), (self.opt_d, opt_d, (D_src,))):
             if opt is None:
@@ -849,8 +739,7 @@ class AliStepper:
             # the device-side count is the authoritative one: graph replays do not run the host-side increment
             return {"step": int(g.step_t.item()), "exp_avg": g.logical(g.m_views).cpu(),
                     "exp_avg_sq": g.logical(g.v_views).cpu()}
-        sd = {f"{n}_state_dict": {k: v.detach().cpu().clone() for k, v in m.state_dict().items()}
-              for n, m in (("E", self.E), ("G", self.G), ("D", self.D))}
+        sd = {f"{n}_state_dict": module_state_cpu(m) for n, m in (("E", self.E), ("G", self.G), ("D", self.D))}
         sd.update(optimizer_E=opt(self.opt_eg), optimizer_D=opt(self.opt_d), iteration=int(self.iter_t.item()),
                   dropout_seed=_dropout._state["seed"])
         if self._z_used:
@@ -862,9 +751,7 @@ class AliStepper:
         everything is copied in place, so captured HIP graphs stay valid."""
         with torch.no_grad():
             for n, m in (("E", self.E), ("G", self.G), ("D", self.D)):
-                src = sd[f"{n}_state_dict"]
-                for k, v in m.state_dict().items():
-                    v.copy_(src[k])
+                load_module_state_(m, sd[f"{n}_state_dict"])
             for g, key in ((self.opt_eg, "optimizer_E"), (self.opt_d, "optimizer_D")):
                 o = sd.get(key)
                 if o is None:
@@ -997,7 +884,7 @@ class AliStepper:
         return ent.out
 
 
-class FinetuneStepper:
+class FinetuneStepper(Stepper):
     """Encoder fine-tuning against a frozen Generator, hand scheduled (reference
     finetune_mnist_bigan.py:64-85, finetune_audio_mnist_bigan.py:62-91, finetune_whale_bigan.py:52-77 with
     ``--metric mse``):
@@ -1025,23 +912,16 @@ class FinetuneStepper:
             raise ValueError(f"metric='ssim' needs images of at least 11x11 (the window), got {self.family.hw}")
         self.pE, self.pG = get_plan(E.layers), get_plan(G.layers)
         self.opt_e = FlatGroup(list(E.parameters()), lr, betas, eps)
-        self.pE.cache.make_static()
-        self.capture = capture
-        self._graphs = GraphCache()
+        self._adopt([(self.opt_e, [self.pE])], capture)       # (G is frozen: its packs follow its parameter versions)
 
     @torch.no_grad()
     def step(self, x, a):
         if self.metric == "ssim" and x.dim() != 4:
             raise ValueError(f"metric='ssim' needs x as [B,1,H,W], got {tuple(x.shape)}")
         a = self.family.used(a)
-        if not (self.capture and x.is_cuda):
+        if not x.is_cuda:
             return self._step(x, a)
-        return self._graphs(self._step, (x, a), (self.E.training, self.G.training), self.opt_e.state_tensors(),
-                            self._restored)
-
-    def _restored(self):
-        self.opt_e.resync()
-        self.pE.cache.refresh()
+        return self._run(self._step, (x, a), (self.E.training, self.G.training))
 
     def _step(self, x, a):
         fam = self.family
@@ -1049,9 +929,7 @@ class FinetuneStepper:
         H, W = fam.hw
         pairwise = x.dim() == 3 and B > 1          # [B,H,W] - [B,1,H,W] broadcasts to [B,B,H,W] (whale script)
         idx, cont, onehots = fam.conditioning(a)
-        n_log, cpad = _plane_count(fam.e_tables, cont)
-        x0 = ops.assemble_planes(x.reshape(B, H, W).float().contiguous(), idx, [t.detach() for t in fam.e_tables],
-                                 cont, B, H, W, cpad)
+        x0, n_log = _e_planes(fam, x, idx, cont)
         codes, sE = chain_forward(self.pE, x0, self.E.training, n_log, True)
         zin = codes.reshape(B, -1)
         gin, g_log = _g_input(fam, zin, onehots, cont)
@@ -1083,11 +961,8 @@ class FinetuneStepper:
         emb = tuple(range(1, 1 + len(fam.e_tables)))       # only these planes of E's input gradient are consumed
         g_x0, _ = chain_backward(self.pE, sE, g_codes.reshape(codes.shape), n_log, bool(emb), True, dst,
                                  gx_planes=emb or None)
-        gofs = 0 if (g_x0 is not None and g_x0.shape[-1] == len(emb)) else 1
-        for j, t in enumerate(fam.e_tables):
-            ops.plane_table_grad(g_x0.contiguous(), gofs + j, x0, 1 + j, idx, j, t.shape[0], out=dst[id(t)])
-        self.opt_e.adam()
-        self.pE.cache.refresh()
+        _e_plane_grads(fam, g_x0, x0, idx, lambda t: dst[id(t)])
+        self._update(self.opt_e)
         return {"rec": rec, "latent": latent}
 
 

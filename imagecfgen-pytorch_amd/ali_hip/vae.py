@@ -24,7 +24,8 @@ from . import ops
 from . import source as _source
 from .chain import chain_backward, chain_forward, get_plan
 from .graphs import GraphCache
-from .step import FlatGroup, MnistFamily, SpectFamily, _plane_count, mean_of_rounds
+from .step import MnistFamily, SpectFamily, _e_plane_grads, _e_planes, mean_of_rounds
+from .trainer import FlatGroup, Stepper
 
 DECODER_LOG_VAR = -5.0          # log-variance of p(x | z) (mnist.py:95, audio_mnist.py:282, whalecalls.py:332)
 
@@ -86,10 +87,7 @@ class VaeCore:
         fam = self.fam
         idx, cont, onehots = cond
         B = x.shape[0]
-        H, W = fam.hw
-        n_log, cpad = _plane_count(fam.e_tables, cont)
-        x0 = ops.assemble_planes(x.reshape(B, H, W).float().contiguous(), idx, [t.detach() for t in fam.e_tables], cont,
-                                 B, H, W, cpad)
+        x0, n_log = _e_planes(fam, x, idx, cont)
         training = self.vae.training
         feat, sE = chain_forward(self.pE, x0, training, n_log, save)
         L = fam.latent
@@ -164,9 +162,7 @@ class VaeCore:
         g_x0, gr = chain_backward(self.pE, st.sE, gfeat.reshape(st.sE[-1].y.shape), st.n_log, bool(emb), True, grad_dst,
                                   gx_planes=emb or None)
         grads.update(gr)
-        gofs = 0 if (g_x0 is not None and g_x0.shape[-1] == len(emb)) else 1
-        for j, t in enumerate(fam.e_tables):
-            ops.plane_table_grad(g_x0.contiguous(), gofs + j, st.x0, 1 + j, st.idx, j, t.shape[0], out=out_for(t))
+        _e_plane_grads(fam, g_x0, st.x0, st.idx, out_for)
         return grads
 
 
@@ -233,7 +229,7 @@ def elbo_torch(vae, x, c, eps, kl_weight):
     return lp - kl_weight * dkl, lp, dkl
 
 
-class VaeStepper:
+class VaeStepper(Stepper):
     """One training step of a conditional VAE, hand scheduled:
 
         opt.zero_grad(); loss = -vae.elbo(x, c, num_samples, kl_weight=kl_weight); loss.backward(); opt.step()
@@ -249,19 +245,16 @@ class VaeStepper:
                  eps=1e-8):
         self.vae = vae
         self.kl_weight, self.num_samples = float(kl_weight), int(num_samples)
-        self.capture = capture
         self.seed = _source.DEFAULT_Z_SEED if seed is None else int(seed)
-        self._graphs = GraphCache()
         self.on_device = next(vae.parameters()).is_cuda
         if self.on_device:
             self.core = core_of(vae)
             self.opt = FlatGroup(list(vae.parameters()), lr, betas, eps)
-            for plan in self.core.plans():
-                plan.cache.make_static()
-            self.draws = torch.zeros(1, dtype=torch.int64, device=self.opt.flat.device)   # steps that drew in the kernel
         else:
             self.opt = torch.optim.Adam(vae.parameters(), lr=lr, betas=betas, eps=eps)
-            self.draws = 0
+        self._adopt([(self.opt, self.core.plans())] if self.on_device else [], capture)
+        # steps that drew in the kernel
+        self.draws = torch.zeros(1, dtype=torch.int64, device=self.opt.flat.device) if self.on_device else 0
 
     @torch.no_grad()
     def step(self, x, c, eps=None):
@@ -270,15 +263,7 @@ class VaeStepper:
         if not self.on_device:
             return self._step_torch(x, c, eps)
         c = self.core.fam.used(c)
-        if not self.capture:
-            return self._step(x, c, eps)
-        return self._graphs(self._step, (x, c, eps), (self.vae.training,), self.opt.state_tensors() + [self.draws],
-                            self._restored)
-
-    def _restored(self):
-        self.opt.resync()
-        for plan in self.core.plans():
-            plan.cache.refresh()
+        return self._run(self._step, (x, c, eps), (self.vae.training,), [self.draws])
 
     def _step(self, x, c, eps=None):
         core = self.core
@@ -286,9 +271,7 @@ class VaeStepper:
         if eps is None:
             ops.add_i64_multi([self.draws], [1])
         core.backward(st, self.kl_weight, grad_dst=self.opt.grad_views)
-        self.opt.adam()
-        for plan in core.plans():
-            plan.cache.refresh()
+        self._update(self.opt)
         return {"loss": st.out3[1], "logp": st.out3[0], "kl": st.out3[2]}
 
     def _step_torch(self, x, c, eps):
