@@ -35,6 +35,7 @@ struct Tuning {
   int no_dma16;                             // ALI_NO_DMA16=1: fp16 twins are always staged through registers (A/B of the LDS-DMA loop)
   int no_clean;                             // ALI_NO_CLEAN=1: the general k-loop on every tile of the fp32 gconv / wgrad kernels (A/B, tests)
   int no_t1_mfma;                           // ALI_NO_T1_MFMA=1: the VALU gather forms of the direct one-channel kernels (A/B)
+  int no_uniform;                           // ALI_NO_UNIFORM=1: every tile of the fp32 gconv kernel takes the general (per-row) prologue (A/B, tests)
 };
 inline Tuning read_tuning() {
   {
@@ -52,6 +53,7 @@ inline Tuning read_tuning() {
     v.no_s2_first = (int)num("ALI_NO_S2_FIRST");
     v.no_dma16 = (int)num("ALI_NO_DMA16");
     v.no_clean = (int)num("ALI_NO_CLEAN");
+    v.no_uniform = (int)num("ALI_NO_UNIFORM");
     return v;
   }
 }

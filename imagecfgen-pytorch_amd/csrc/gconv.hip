@@ -81,6 +81,7 @@ struct GDesc {
   const int* order;         // AliEpilogue.tile_order (M-tile ids, longest k-loop first) or null
   int ldi;                  // pixel pitch of the gathered operand (floats): Cin, or AliEpilogue.in_ld
   int no_clean;        // ALI_NO_CLEAN=1: every tile takes the general fp32 k-loop (A/B, tests)
+  int no_uniform;      // 0 in launches of the UNI kernel instances (some phase can hold uniform tiles), else 1
   int f16;             // AliEpilogue.mfma_f16: fp16 operands on v_mfma_f32_32x32x16_f16 where the fast path applies
   const _Float16* in16;   // AliEpilogue.in16 / w16 / out16 (fp16 twins of in / w / out), or null
   const _Float16* w16;
@@ -117,7 +118,9 @@ constexpr int LDH = 40;      // fp16 LDS rows: 32 halves + 8 pad = 80 B (16-B al
 // The kernel's body.  (bx_, by_, bz_) = the block's 3-D index in a plain launch; u_ = its linear index in a 1-D
 // ("lin1d": tail-split / cost-ordered) launch.  A job of a multi-job launch (gconv_multi_kernel) passes the same values,
 // decoded from its share of that launch's 1-D grid.
-template <int BM, int BN, int WAVES_M, int WAVES_N, int MODE, int F16 = 0, int NT = 256>
+// UNI: the instance also holds the uniform-tile prologue (fp32 MODE 2; launched only where the host found a phase whose
+// tiles are uniform, so every other launch runs the kernel without it)
+template <int BM, int BN, int WAVES_M, int WAVES_N, int MODE, int F16 = 0, int NT = 256, bool UNI = false>
 __device__ __forceinline__ void gconv_body(const GDesc& d, const int bx_, const int by_, const int bz_, const int u_) {
   constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N;
   constexpr int TM = WM / 32, TN = WN / 32;
@@ -203,72 +206,155 @@ __device__ __forceinline__ void gconv_body(const GDesc& d, const int bx_, const 
   const int Cin = d.Cin, Hin = d.Hin, Win = d.Win;
   const int ntaps = P.nr * P.ns;
 
-  if (t < kMaxTaps) {
-    int v = 0;
-    if (t < ntaps) {
-      const int ir = t / P.ns, is = t - ir * P.ns;
-      v = (P.dh[ir] & 0xff) | ((P.dw[is] & 0xff) << 8) | (((int)P.wr[ir] * d.S + (int)P.ws[is]) << 16);
+  // Uniform tile (fp32 MODE 2; DESIGN.md 3.1 "Fixed cost of a tile"): rows are ordered (pixel, image) and B is a
+  // multiple of BM, so every row of the tile sits at ONE pixel position and the row's image is m0 % B + row.  The tap
+  // mask, the live-tap list, the smallest tap offset and the gather offsets then follow from block-uniform scalars: no
+  // per-row division, no LDS atomics, no barrier in front of the first gathers (issued in the k-loop's preamble below,
+  // where the row tables and s_live are written while they are in flight).  Every value the k-loop and the epilogue
+  // consume is what the general prologue produces for the same tile.  (M = Hq * Wq * B, so such a phase has no ragged
+  // last tile: m0 + BM <= P.M always holds here.)
+  static_assert(!UNI || (MODE == 2 && F16 == 0), "the uniform prologue exists for the fp32 uniform-tap loop only");
+  const bool uniform = UNI && d.no_uniform == 0 && P.pixmajor != 0 && (d.B % BM) == 0;
+  // {dh, dw, weight tap} of tap tp from the phase's grid tables (selects on kernel arguments: no memory access).  The
+  // tables are read ONCE into scalars: every further reference to the descriptor counts against the limit up to which
+  // the compiler keeps a by-value kernel argument in the argument segment instead of copying it to scratch.
+  // (The general path packs the weight tap into 8 bits of s_tap; taps are at most kMaxGrid^2 - 1 = 24, so both agree.)
+  static_assert(kMaxGrid == 5, "tap_geom finds a tap's row with four comparisons");
+  int g_dh[kMaxGrid] = {}, g_dw[kMaxGrid] = {}, g_wt[kMaxGrid] = {}, g_ws[kMaxGrid] = {};
+  if (uniform) {
+#pragma unroll
+    for (int k = 0; k < kMaxGrid; ++k) {
+      g_dh[k] = P.dh[k];
+      g_dw[k] = P.dw[k];
+      g_wt[k] = (int)P.wr[k] * d.S;
+      g_ws[k] = P.ws[k];
     }
-    s_tap[t] = v;
   }
-  if (t == 0) { s_tapmask = 0u; s_clean = 1; s_dmin = 0x7fffffff; }
-
-  const float rW = 1.0f / (float)P.Wq, rH = 1.0f / (float)P.Hq, rB = 1.0f / (float)d.B;
-  auto decode = [&](int m, int& img, int& qh, int& qw) {
-    if (P.pixmajor) {
-      int pix;
-      fast_divmod(m, d.B, rB, pix, img);
-      fast_divmod(pix, P.Wq, rW, qh, qw);
-    } else {
-      int t2;
-      fast_divmod(m, P.Wq, rW, t2, qw);
-      fast_divmod(t2, P.Hq, rH, img, qh);
+  const int g_ns = P.ns;
+  auto tap_geom = [&](int tp, int& dh, int& dw, int& wt) __attribute__((always_inline)) {
+    const int ir = (tp >= g_ns) + (tp >= 2 * g_ns) + (tp >= 3 * g_ns) + (tp >= 4 * g_ns), is = tp - ir * g_ns;
+    int wr = 0, ws = 0;
+    dh = 0; dw = 0;
+#pragma unroll
+    for (int k = 0; k < kMaxGrid; ++k) {
+      dh = k == ir ? g_dh[k] : dh;
+      wr = k == ir ? g_wt[k] : wr;
+      dw = k == is ? g_dw[k] : dw;
+      ws = k == is ? g_ws[k] : ws;
     }
+    wt = wr + ws;
   };
-  for (int r = t; r < BM; r += NT) {
-    const int m = m0 + r;
-    int off = -1, img = 0;
-    if (m < P.M) {
-      int qh, qw;
-      decode(m, img, qh, qw);
-      off = ((img * d.Hout + P.oh0 + qh * P.ostep) * d.Wout + (P.ow0 + qw * P.ostep)) * d.ldo;
-    }
-    s_rowoff[r] = off;
-    s_rowimg[r] = img;
-  }
-
-  // ---- per-thread gather rows: element offset of the row's base pixel and a bit mask of the taps that hit the input
   const int c4 = t & 7;
   const int r0 = t >> 3;
   int aoff[AP], aih[AP], aiw[AP];
   unsigned amask[AP];
-  unsigned blockmask = 0u;
-#pragma unroll
-  for (int i = 0; i < AP; ++i) {
-    const int m = m0 + r0 + RPP * i;
-    const bool valid = m < P.M;
-    int qw, qh, img;
-    decode(valid ? m : 0, img, qh, qw);
-    aih[i] = qh * P.mult;
-    aiw[i] = qw * P.mult;
-    aoff[i] = ((img * Hin + aih[i]) * Win + aiw[i]) * d.ldi;
+  unsigned tapmask_u = 0u;
+  int dmin_u = 0, img0_u = 0, rowoff0_u = 0;
+  if (uniform) {
+    const unsigned pix = (unsigned)m0 / (unsigned)d.B;
+    const int img0 = m0 - (int)pix * d.B;
+    const int qh = (int)(pix / (unsigned)P.Wq), qw = (int)pix - qh * P.Wq;
+    const int ih = qh * P.mult, iw = qw * P.mult;
     unsigned wbits = 0u, mk = 0u;
+    int dhmin = 127, dwmin = 127;
     for (int is = 0; is < P.ns; ++is)
-      if ((unsigned)(aiw[i] + P.dw[is]) < (unsigned)Win) wbits |= 1u << is;
+      if ((unsigned)(iw + P.dw[is]) < (unsigned)Win) { wbits |= 1u << is; dwmin = min(dwmin, (int)P.dw[is]); }
     for (int ir = 0; ir < P.nr; ++ir)
-      if ((unsigned)(aih[i] + P.dh[ir]) < (unsigned)Hin) mk |= wbits << (ir * P.ns);
-    amask[i] = valid ? mk : 0u;
-    blockmask |= amask[i];
-  }
-  __syncthreads();
-  if (c4 == 0 && blockmask) atomicOr(&s_tapmask, blockmask);
-  __syncthreads();
-  const unsigned tapmask = s_tapmask;
-  if (MODE == 2 && F16 == 0) {   // clean-tile test, row part: read behind the next barrier
-    bool mine = true;
+      if ((unsigned)(ih + P.dh[ir]) < (unsigned)Hin) { mk |= wbits << (ir * P.ns); dhmin = min(dhmin, (int)P.dh[ir]); }
+    tapmask_u = mk;
+    // the live taps are the product {live ir} x {live is}: their smallest offset is that of (min dh, min dw)
+    dmin_u = ((dhmin * Win + dwmin) * d.ldi) * 4;
+    img0_u = img0;
+    rowoff0_u = ((img0 * d.Hout + P.oh0 + qh * P.ostep) * d.Wout + (P.ow0 + qw * P.ostep)) * d.ldo;
 #pragma unroll
-    for (int i = 0; i < AP; ++i) mine = mine && (amask[i] & tapmask) == tapmask;
-    if (!mine) s_clean = 0;
+    for (int i = 0; i < AP; ++i) {
+      aoff[i] = (((img0 + r0 + RPP * i) * Hin + ih) * Win + iw) * d.ldi;
+      amask[i] = mk;
+    }
+  }
+  // the uniform tile's tables: output offset and image of every row (affine in the row), live taps compacted
+  auto uniform_tables = [&]() __attribute__((always_inline)) {
+    for (int r = t; r < BM; r += NT) {
+      s_rowoff[r] = rowoff0_u + r * (d.Hout * d.Wout * d.ldo);
+      s_rowimg[r] = img0_u + r;
+    }
+    if (t < ntaps && ((tapmask_u >> t) & 1u)) {
+      const int pos = __popc(tapmask_u & ((1u << t) - 1u));
+      int dh, dw, wt;
+      tap_geom(t, dh, dw, wt);
+      s_live[pos][0] = ((dh * Win + dw) * d.ldi) * 4;
+      s_live[pos][1] = (wt * Cin) * 4;
+      s_live[pos][2] = (int)(1u << t);
+      s_live[pos][3] = 0;
+    }
+  };
+
+  unsigned tapmask = tapmask_u;
+  if (!uniform) {
+    // ---- general prologue: every row decoded on its own, tap masks combined through LDS
+    if (t < kMaxTaps) {
+      int v = 0;
+      if (t < ntaps) {
+        const int ir = t / P.ns, is = t - ir * P.ns;
+        v = (P.dh[ir] & 0xff) | ((P.dw[is] & 0xff) << 8) | (((int)P.wr[ir] * d.S + (int)P.ws[is]) << 16);
+      }
+      s_tap[t] = v;
+    }
+    if (t == 0) { s_tapmask = 0u; s_clean = 1; s_dmin = 0x7fffffff; }
+
+    const float rW = 1.0f / (float)P.Wq, rH = 1.0f / (float)P.Hq, rB = 1.0f / (float)d.B;
+    auto decode = [&](int m, int& img, int& qh, int& qw) {
+      if (P.pixmajor) {
+        int pix;
+        fast_divmod(m, d.B, rB, pix, img);
+        fast_divmod(pix, P.Wq, rW, qh, qw);
+      } else {
+        int t2;
+        fast_divmod(m, P.Wq, rW, t2, qw);
+        fast_divmod(t2, P.Hq, rH, img, qh);
+      }
+    };
+    for (int r = t; r < BM; r += NT) {
+      const int m = m0 + r;
+      int off = -1, img = 0;
+      if (m < P.M) {
+        int qh, qw;
+        decode(m, img, qh, qw);
+        off = ((img * d.Hout + P.oh0 + qh * P.ostep) * d.Wout + (P.ow0 + qw * P.ostep)) * d.ldo;
+      }
+      s_rowoff[r] = off;
+      s_rowimg[r] = img;
+    }
+
+    // per-thread gather rows: element offset of the row's base pixel and a bit mask of the taps that hit the input
+    unsigned blockmask = 0u;
+#pragma unroll
+    for (int i = 0; i < AP; ++i) {
+      const int m = m0 + r0 + RPP * i;
+      const bool valid = m < P.M;
+      int qw, qh, img;
+      decode(valid ? m : 0, img, qh, qw);
+      aih[i] = qh * P.mult;
+      aiw[i] = qw * P.mult;
+      aoff[i] = ((img * Hin + aih[i]) * Win + aiw[i]) * d.ldi;
+      unsigned wbits = 0u, mk = 0u;
+      for (int is = 0; is < P.ns; ++is)
+        if ((unsigned)(aiw[i] + P.dw[is]) < (unsigned)Win) wbits |= 1u << is;
+      for (int ir = 0; ir < P.nr; ++ir)
+        if ((unsigned)(aih[i] + P.dh[ir]) < (unsigned)Hin) mk |= wbits << (ir * P.ns);
+      amask[i] = valid ? mk : 0u;
+      blockmask |= amask[i];
+    }
+    __syncthreads();
+    if (c4 == 0 && blockmask) atomicOr(&s_tapmask, blockmask);
+    __syncthreads();
+    tapmask = s_tapmask;
+    if (MODE == 2 && F16 == 0) {   // clean-tile test, row part: read behind the next barrier
+      bool mine = true;
+#pragma unroll
+      for (int i = 0; i < AP; ++i) mine = mine && (amask[i] & tapmask) == tapmask;
+      if (!mine) s_clean = 0;
+    }
   }
 
   // the epilogue's bias values, requested now: by the end of the k-loop they have long arrived (a dependent load in
@@ -304,27 +390,30 @@ __device__ __forceinline__ void gconv_body(const GDesc& d, const int bx_, const 
   if (MODE >= 2) {
     // ================= uniform-tap fast path (MODE 2) / small power-of-two channel stride (MODE 3) =================
     // live taps, compacted: {byte offset into the activation, byte offset into the weight row, tap bit}
-    if (MODE == 3) {   // all taps in order (no compaction); entries past the last tap are dead
-      if (t < kMaxTaps + 8) {
-        const bool live = t < ntaps && ((tapmask >> t) & 1u);
-        const int tv = s_tap[t < kMaxTaps ? t : 0];
+    // (a uniform tile writes its tables in the k-loop's preamble, behind the first gathers)
+    if (!uniform) {
+      if (MODE == 3) {   // all taps in order (no compaction); entries past the last tap are dead
+        if (t < kMaxTaps + 8) {
+          const bool live = t < ntaps && ((tapmask >> t) & 1u);
+          const int tv = s_tap[t < kMaxTaps ? t : 0];
+          const int dh = (signed char)(tv & 0xff), dw = (signed char)((tv >> 8) & 0xff), wt = (tv >> 16) & 0xff;
+          s_live[t][0] = ((dh * Win + dw) * d.ldi) * 4;
+          s_live[t][1] = live ? (wt * Cin) * 4 : (int)0xFFFFFF00u;
+          s_live[t][2] = live ? (int)(1u << t) : 0;
+          s_live[t][3] = 0;
+        }
+      } else if (t < ntaps && ((tapmask >> t) & 1u)) {
+        const int pos = __popc(tapmask & ((1u << t) - 1u));
+        const int tv = s_tap[t];
         const int dh = (signed char)(tv & 0xff), dw = (signed char)((tv >> 8) & 0xff), wt = (tv >> 16) & 0xff;
-        s_live[t][0] = ((dh * Win + dw) * d.ldi) * 4;
-        s_live[t][1] = live ? (wt * Cin) * 4 : (int)0xFFFFFF00u;
-        s_live[t][2] = live ? (int)(1u << t) : 0;
-        s_live[t][3] = 0;
+        s_live[pos][0] = ((dh * Win + dw) * d.ldi) * 4;
+        if (F16 == 0) atomicMin(&s_dmin, ((dh * Win + dw) * d.ldi) * 4);
+        s_live[pos][1] = (wt * Cin) * 4;
+        s_live[pos][2] = (int)(1u << t);
+        s_live[pos][3] = 0;
       }
-    } else if (t < ntaps && ((tapmask >> t) & 1u)) {
-      const int pos = __popc(tapmask & ((1u << t) - 1u));
-      const int tv = s_tap[t];
-      const int dh = (signed char)(tv & 0xff), dw = (signed char)((tv >> 8) & 0xff), wt = (tv >> 16) & 0xff;
-      s_live[pos][0] = ((dh * Win + dw) * d.ldi) * 4;
-      if (F16 == 0) atomicMin(&s_dmin, ((dh * Win + dw) * d.ldi) * 4);
-      s_live[pos][1] = (wt * Cin) * 4;
-      s_live[pos][2] = (int)(1u << t);
-      s_live[pos][3] = 0;
+      __syncthreads();
     }
-    __syncthreads();
     const int tpt = MODE == 3 ? BK / Cin : 1;                 // whole taps per k-tile (MODE 3)
     const int tsub = MODE == 3 ? (c4 * 4) / Cin : 0;          // this thread's tap inside the k-tile
     const int ccol = MODE == 3 ? (c4 * 4) % Cin : c4 * 4;     // this thread's channel offset inside the tap / chunk
@@ -622,30 +711,24 @@ __device__ __forceinline__ void gconv_body(const GDesc& d, const int bx_, const 
       // a CU (small layers, split-K tails) has ~1.5 iterations to cover the memory latency instead of ~0.5.
       int q = qb;
       int li = q / cpt, ch = q - li * cpt;
-      {
-        const Ctx c0 = tile_ctx(li, ch, true);
+      auto first_gathers = [&](const Ctx& c0, const Ctx& c1) __attribute__((always_inline)) {
 #pragma unroll
         for (int i = 0; i < AP; ++i) load_a(c0, i, Set0{});
 #pragma unroll
         for (int j = 0; j < BP; ++j) load_b(c0, j, Set0{});
-        if (++ch == cpt) { ch = 0; ++li; }
-        const Ctx c1 = tile_ctx(li, ch, q + 1 < qe);
 #pragma unroll
         for (int i = 0; i < AP; ++i) load_a(c1, i, Set1{});
 #pragma unroll
         for (int j = 0; j < BP; ++j) load_b(c1, j, Set1{});
-      }
-      store_tile(0);
-      if (++ch == cpt) { ch = 0; ++li; }
-      Ctx cxn = tile_ctx(li, ch, q + 2 < qe);
+      };
       // Clean tile: every row is a real row (an absent row has an empty tap mask, so it clears s_clean
       // like a row that misses a live tap), every live tap hits the input for every row and every weight row exists -- no gather of the k-loop can be dead, so the selects above decide nothing.  The clean loop
       // keeps a constant per-thread voffset; the block-uniform tap / chunk offset travels as the scalar soffset.  The
       // hardware adds soffset unsigned, so the A voffset is biased by the smallest live tap offset (still the address of
       // a real pixel of the row: in range).  Tiles past qe are fetched through a descriptor of 0 records: zeros, no
       // memory traffic, exactly what the general loop stages.  Same slots, same LDS image, same k order: same bits.
-      const bool clean = F16 == 0 && MODE == 2 && d.no_clean == 0 && n0 + BN <= d.Cout &&
-                         __builtin_amdgcn_readfirstlane(s_clean) != 0;
+      bool clean = false;
+      Ctx cxn = {0, 0, 0u};
       struct CCtx { int sa, sb; unsigned na, nb; };
       unsigned aoffC[AP];
       int dmin = 0, tap_sa = 0, tap_sb = 0;
@@ -663,12 +746,75 @@ __device__ __forceinline__ void gconv_body(const GDesc& d, const int bx_, const 
         return cc;
       };
       CCtx ccn = {0, 0, 0u, 0u};
-      if (clean) {
-        dmin = __builtin_amdgcn_readfirstlane(s_dmin);
+      if (uniform) {
+        // The constants of tiles q, q+1 and q+2 from scalars: mcur = the live taps from tile q's tap on (tap li of the
+        // compacted list = the li-th set bit of the tile's mask; past the last live tap it stays there, as tile_ctx
+        // and clean_tap clamp).  Nothing here waits for LDS: the gathers of the first two k-tiles leave before the
+        // tables are written, and the one barrier in front of the loop publishes tables and k-tile 0 together.
+        unsigned mcur = tapmask;
+        for (int k = 0; k < li; ++k) mcur &= mcur - 1u;
+        int tdoff = 0, twoff = 0;
+        unsigned tbit = 0u;
+        auto cur_tap = [&]() __attribute__((always_inline)) {
+          const int tp = __builtin_ctz(mcur);
+          int dh, dw, wt;
+          tap_geom(tp, dh, dw, wt);
+          tdoff = ((dh * Win + dw) * d.ldi) * 4;
+          twoff = (wt * Cin) * 4;
+          tbit = 1u << tp;
+        };
+        auto uctx = [&](bool live) __attribute__((always_inline)) -> Ctx {
+          Ctx cx;
+          cx.doff = tdoff + ch * (BK * 4);
+          cx.woff = live ? twoff + ch * (BK * 4) : (int)OOB;
+          cx.bit = live ? tbit : 0u;
+          return cx;
+        };
+        auto advance = [&]() __attribute__((always_inline)) {
+          if (++ch == cpt) {
+            ch = 0;
+            ++li;
+            const unsigned nx = mcur & (mcur - 1u);
+            if (nx) { mcur = nx; cur_tap(); }
+          }
+        };
+        cur_tap();
+        const Ctx c0 = uctx(true);
+        advance();
+        const Ctx c1 = uctx(q + 1 < qe);
+        first_gathers(c0, c1);
+        uniform_tables();
+        advance();
+        cxn = uctx(q + 2 < qe);
+        clean = d.no_clean == 0 && n0 + BN <= d.Cout;
+        if (clean) {
+          // (block-uniform by construction; pinned in SGPRs like the general path's, or the loop's scalar offsets
+          // would be fed through a waterfall loop)
+          dmin = __builtin_amdgcn_readfirstlane(dmin_u);
 #pragma unroll
-        for (int i = 0; i < AP; ++i) aoffC[i] = aoffB[i] + (unsigned)dmin;
-        clean_tap(li);
-        ccn = clean_ctx(ch, q + 2 < qe);
+          for (int i = 0; i < AP; ++i) aoffC[i] = aoffB[i] + (unsigned)dmin;
+          tap_sa = __builtin_amdgcn_readfirstlane(tdoff - dmin);
+          tap_sb = __builtin_amdgcn_readfirstlane(twoff);
+          ccn = clean_ctx(ch, q + 2 < qe);
+        }
+        store_tile(0);
+      } else {
+        const Ctx c0 = tile_ctx(li, ch, true);
+        if (++ch == cpt) { ch = 0; ++li; }
+        const Ctx c1 = tile_ctx(li, ch, q + 1 < qe);
+        first_gathers(c0, c1);
+        store_tile(0);
+        if (++ch == cpt) { ch = 0; ++li; }
+        cxn = tile_ctx(li, ch, q + 2 < qe);
+        clean = F16 == 0 && MODE == 2 && d.no_clean == 0 && n0 + BN <= d.Cout &&
+                __builtin_amdgcn_readfirstlane(s_clean) != 0;
+        if (clean) {
+          dmin = __builtin_amdgcn_readfirstlane(s_dmin);
+#pragma unroll
+          for (int i = 0; i < AP; ++i) aoffC[i] = aoffB[i] + (unsigned)dmin;
+          clean_tap(li);
+          ccn = clean_ctx(ch, q + 2 < qe);
+        }
       }
       auto load_ac = [&](const CCtx& cc, int i, auto SET) {
         const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void*)d.in, 0, cc.na, 0x00020000);
@@ -776,6 +922,10 @@ __device__ __forceinline__ void gconv_body(const GDesc& d, const int bx_, const 
       } else {
         run(std::false_type{});
       }
+    }
+    if (uniform && qb >= qe) {   // nothing to multiply (an empty split-K slice, no live tap): the epilogue still needs the rows
+      uniform_tables();
+      __syncthreads();
     }
   } else {
     // ================= generic path (first layers: channel stride not a multiple of 32) =================
@@ -1104,9 +1254,9 @@ __device__ __forceinline__ void gconv_body(const GDesc& d, const int bx_, const 
   else run_epilogue(F_{}, F_{}, BN0{}, false, d.out);
 }
 
-template <int BM, int BN, int WAVES_M, int WAVES_N, int MODE, int F16 = 0>
+template <int BM, int BN, int WAVES_M, int WAVES_N, int MODE, int F16 = 0, bool UNI = false>
 __global__ __launch_bounds__(256, 2) void gconv_kernel(const GDesc d) {
-  gconv_body<BM, BN, WAVES_M, WAVES_N, MODE, F16>(d, blockIdx.x, blockIdx.y, blockIdx.z, blockIdx.x);
+  gconv_body<BM, BN, WAVES_M, WAVES_N, MODE, F16, 256, UNI>(d, blockIdx.x, blockIdx.y, blockIdx.z, blockIdx.x);
 }
 
 // 512-thread variant (the LDS-DMA fp16 loop: 8 waves, one block per CU)
@@ -1124,7 +1274,7 @@ __global__ __launch_bounds__(512, 1) void gconv_kernel512(const GDesc d) {
 constexpr int kGJobs = 4;
 struct GJobs { int n, pad_; int blk0[kGJobs]; int gx[kGJobs], gy[kGJobs]; GDesc j[kGJobs]; };
 static_assert(sizeof(GJobs) <= 4000, "kernel argument segment");
-template <int BM, int BN, int WAVES_M, int WAVES_N, int MODE, int F16 = 0>
+template <int BM, int BN, int WAVES_M, int WAVES_N, int MODE, int F16 = 0, bool UNI = false>
 __global__ __launch_bounds__(256, 2) void gconv_multi_kernel(const GJobs jobs) {
   int k = 0;
 #pragma unroll 1
@@ -1133,7 +1283,7 @@ __global__ __launch_bounds__(256, 2) void gconv_multi_kernel(const GJobs jobs) {
   const int u = blockIdx.x - jobs.blk0[k];
   const int gx = jobs.gx[k], gy = jobs.gy[k];
   const int t2 = u / gx;
-  gconv_body<BM, BN, WAVES_M, WAVES_N, MODE, F16>(jobs.j[k], u - t2 * gx, t2 % gy, t2 / gy, u);
+  gconv_body<BM, BN, WAVES_M, WAVES_N, MODE, F16, 256, UNI>(jobs.j[k], u - t2 * gx, t2 % gy, t2 / gy, u);
 }
 
 struct TileCfg { int bm, bn; };
@@ -1360,6 +1510,12 @@ static int finalize_and_launch(GDesc& d, void* ws, size_t ws_bytes, hipStream_t 
     d.lin1d = 1;
   }
   d.no_clean = tuning().no_clean;
+  // uniform tiles (the kernel's uniform prologue): fp32 uniform-tap launches with a phase whose rows are ordered
+  // (pixel, image) and whose tiles hold one pixel position each.  Only such launches run the UNI kernel instances.
+  bool any_uni = false;
+  for (int i = 0; i < d.nphase; ++i) any_uni = any_uni || (d.ph[i].pixmajor && d.B % tc.bm == 0);
+  any_uni = any_uni && uni && !d.f16 && tuning().no_uniform == 0;
+  d.no_uniform = any_uni ? 0 : 1;
   d.ctr = reinterpret_cast<int*>(ws);
   d.ws = reinterpret_cast<float*>(ws_payload(ws));
   dim3 grid(tiles, ntile_n, S), block(256);
@@ -1385,6 +1541,7 @@ static int finalize_and_launch(GDesc& d, void* ws, size_t ws_bytes, hipStream_t 
   do {                                                                                                  \
     if (op16) hipLaunchKernelGGL((gconv_kernel<BM_, BN_, WMM, WNN, 2, 2>), grid, block, 0, stream, d);  \
     else if (f16) hipLaunchKernelGGL((gconv_kernel<BM_, BN_, WMM, WNN, 2, 1>), grid, block, 0, stream, d); \
+    else if (any_uni) hipLaunchKernelGGL((gconv_kernel<BM_, BN_, WMM, WNN, 2, 0, true>), grid, block, 0, stream, d); \
     else if (uni) hipLaunchKernelGGL((gconv_kernel<BM_, BN_, WMM, WNN, 2>), grid, block, 0, stream, d); \
     else if (pow2) hipLaunchKernelGGL((gconv_kernel<BM_, BN_, WMM, WNN, 3>), grid, block, 0, stream, d);  \
     else if (vec) hipLaunchKernelGGL((gconv_kernel<BM_, BN_, WMM, WNN, 1>), grid, block, 0, stream, d); \
@@ -1967,14 +2124,19 @@ extern "C" int ali_gemm_launch_multi(int32_t n, const AliGemmJob* jobs, ali_stre
       if (cnt == 1) {
         const GJobRec& r = all[j0];
         dim3 grid(r.gx, r.gy, r.gz);
-        if (v == 0) hipLaunchKernelGGL((gconv_kernel<64, 64, 2, 2, 2>), grid, dim3(256), 0, stream, r.d);
+        if (r.d.no_uniform == 0) {
+          if (v == 0) hipLaunchKernelGGL((gconv_kernel<64, 64, 2, 2, 2, 0, true>), grid, dim3(256), 0, stream, r.d);
+          else hipLaunchKernelGGL((gconv_kernel<128, 32, 4, 1, 2, 0, true>), grid, dim3(256), 0, stream, r.d);
+        } else if (v == 0) hipLaunchKernelGGL((gconv_kernel<64, 64, 2, 2, 2>), grid, dim3(256), 0, stream, r.d);
         else hipLaunchKernelGGL((gconv_kernel<128, 32, 4, 1, 2>), grid, dim3(256), 0, stream, r.d);
       } else {
         GJobs gj;
         memset(&gj, 0, sizeof(gj));
         long long blocks = 0;
+        bool any_uni = false;            // one job with uniform tiles: the whole launch runs the UNI instance
         for (size_t i = 0; i < cnt; ++i) {
           const GJobRec& r = all[j0 + i];
+          any_uni = any_uni || r.d.no_uniform == 0;
           gj.j[i] = r.d;
           gj.gx[i] = r.gx; gj.gy[i] = r.gy;
           gj.blk0[i] = (int)blocks;
@@ -1982,7 +2144,10 @@ extern "C" int ali_gemm_launch_multi(int32_t n, const AliGemmJob* jobs, ali_stre
         }
         gj.n = (int)cnt;
         if (blocks > (1LL << 30)) { set_error("ali_gemm_launch_multi: grid too large"); return ALI_ERR_BAD_ARG; }
-        if (v == 0) hipLaunchKernelGGL((gconv_multi_kernel<64, 64, 2, 2, 2>), dim3((unsigned)blocks), dim3(256), 0, stream, gj);
+        if (any_uni) {
+          if (v == 0) hipLaunchKernelGGL((gconv_multi_kernel<64, 64, 2, 2, 2, 0, true>), dim3((unsigned)blocks), dim3(256), 0, stream, gj);
+          else hipLaunchKernelGGL((gconv_multi_kernel<128, 32, 4, 1, 2, 0, true>), dim3((unsigned)blocks), dim3(256), 0, stream, gj);
+        } else if (v == 0) hipLaunchKernelGGL((gconv_multi_kernel<64, 64, 2, 2, 2>), dim3((unsigned)blocks), dim3(256), 0, stream, gj);
         else hipLaunchKernelGGL((gconv_multi_kernel<128, 32, 4, 1, 2>), dim3((unsigned)blocks), dim3(256), 0, stream, gj);
       }
       int rc = check_launch("gconv_multi_kernel");
