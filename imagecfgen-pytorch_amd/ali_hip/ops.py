@@ -1725,3 +1725,61 @@ def oracle_scores(pred, ox, ocf):
     _lib.check(lib.ali_oracle_scores(_i32(pred, "pred", B), _ptr(ox), _ptr(ocf), max(ox.stride(0), B * C), J, B, C,
                                      _i32(os_, "os"), _chk(lvs, "lvs"), _stream()), "ali_oracle_scores")
     return os_, lvs
+
+
+# ---------------------------------------------------------------------- the counterfactual identity metrics (csrc/cfeval.hip)
+def _pitched_rows(t, name):
+    """a [rows, D] fp32 CUDA view with unit column stride -> (pointer, row pitch in floats)"""
+    if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.numel() > 0
+            and (t.shape[1] == 1 or t.stride(1) == 1)):
+        raise ValueError(f"{name}: need a non-empty [rows, D] fp32 CUDA view with unit column stride, got {t.dtype} "
+                         f"{tuple(t.shape)} strides {tuple(t.stride())}")
+    ld = t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+    if ld < t.shape[1]:
+        raise ValueError(f"{name}: rows overlap (row stride {ld} < {t.shape[1]} columns)")
+    return c_void_p(t.data_ptr()), ld
+
+
+def _f64(t, shape, name):
+    if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
+        raise ValueError(f"{name}: need a contiguous float64 CUDA tensor of shape {tuple(shape)}")
+    return c_void_p(t.data_ptr())
+
+
+def group_moments(rows, order, start, n_owners, n_classes):
+    """The bank of ``manifold_err`` (include/ali_hip.h: ali_group_moments): rows [N, D] (any row pitch), order int32
+    [<= N] = the row indices sorted by cell (stable), start int32 [O * C + 1] = the cells' offsets into it, cell =
+    owner * C + class.  Returns (S, Q [O * C, D], TS, TQ [C, D]) in float64: column sums and sums of squares per cell
+    and per class."""
+    lib = _lib.load()
+    O, C = int(n_owners), int(n_classes)
+    ptr, ld = _pitched_rows(rows, "rows")
+    N, D = rows.shape
+    dev = rows.device
+    S, Q = (torch.empty(O * C, D, dtype=torch.float64, device=dev) for _ in range(2))
+    TS, TQ = (torch.empty(C, D, dtype=torch.float64, device=dev) for _ in range(2))
+    _lib.check(lib.ali_group_moments(ptr, ld, N, D, _i32(order, "order"), order.numel(), _i32(start, "start", O * C + 1),
+                                     O, C, _f64(S, S.shape, "S"), _f64(Q, Q.shape, "Q"), _f64(TS, TS.shape, "TS"),
+                                     _f64(TQ, TQ.shape, "TQ"), _stream()), "ali_group_moments")
+    return S, Q, TS, TQ
+
+
+def manifold_err(cf, owner, cls, S, Q, TS, TQ, cnt, tcnt, out=None):
+    """(same, other, ratio) per row of cf [M, D] (any row pitch) against the bank of ``group_moments`` (include/ali_hip.h:
+    ali_manifold_err): owner, cls int32 [M] on the device, cnt int32 [O * C], tcnt int32 [C].  Returns out [M, 3]."""
+    lib = _lib.load()
+    ptr, ld = _pitched_rows(cf, "cf")
+    M, D = cf.shape
+    C = TS.shape[0]
+    O = S.shape[0] // max(C, 1)
+    if out is None:
+        out = torch.empty(M, 3, dtype=torch.float32, device=cf.device)
+    if tuple(out.shape) != (M, 3):
+        raise ValueError(f"manifold_err: out must be [{M}, 3], got {tuple(out.shape)}")
+    ws = workspace(cf.device)
+    _lib.check(lib.ali_manifold_err(ptr, ld, M, D, _i32(owner, "owner", M), _i32(cls, "cls", M),
+                                    _f64(S, (O * C, D), "S"), _f64(Q, (O * C, D), "Q"), _f64(TS, (C, D), "TS"),
+                                    _f64(TQ, (C, D), "TQ"), _i32(cnt, "cnt", O * C), _i32(tcnt, "tcnt", C), O, C,
+                                    _chk(out, "out"), c_void_p(ws.data_ptr()), ws.numel(), _stream()),
+               "ali_manifold_err")
+    return out

@@ -597,6 +597,49 @@ int ali_cf_recon(const float* x, const float* recon, int64_t ld_row, int64_t ld_
 int ali_oracle_scores(const int32_t* pred, const float* ox, const float* ocf, int64_t ld_j, int32_t J, int32_t B,
                       int32_t C, int32_t* os, float* lvs, ali_stream_t stream);
 
+/* The counterfactual identity metrics (audiomnist_cf_eval.py:93-131: the mean squared distance of a counterfactual to
+ * the real recordings of its own subject and target class over the one to every other subject's); csrc/cfeval.hip.
+ * For a cell (owner, class) of n bank rows b_j with column sums S and column sums of squares Q,
+ *   sum_j ||a - b_j||^2 = sum_k (n a_k^2 - 2 a_k S_k + Q_k),
+ * so the bank is read once (ali_group_moments) and a counterfactual row costs one pass over its own D columns
+ * (ali_manifold_err).  Moments are fp64: the products of fp32 values are exact there, and the cancellation inside a
+ * column keeps 1e-16 of n a^2.  fp64 sums in a fixed order, no float atomics (bit-identical from run to run), no host
+ * reads, no allocation: every launch can be recorded into a HIP graph.  Arguments are checked before the launch
+ * (ALI_ERR_BAD_ARG, message in ali_last_error); 1 <= O * C <= 65535; cell = owner * C + class.
+ *
+ * ali_group_moments: rows [N][D] fp32, row r at r * ld (ld >= D); order [n_order] int32 (n_order <= N): the indices of
+ *   the rows that belong to a cell, sorted by cell, stable (ascending row inside a cell); start [O * C + 1] int32: the
+ *   cell's rows are order[start[cell] .. start[cell + 1]).  S, Q [O * C][D] double: the column sums and column sums of
+ *   squares of each cell, its rows added in ascending row order from 0; an empty cell gives +0.  TS, TQ [C][D] double:
+ *   the fold of that class's cells in ascending owner order from 0, so that a class held by one owner has TS - S == 0
+ *   exactly.  Two launches (column chunks x cells, column chunks x classes), no workspace; 16-byte loads and stores
+ *   when D % 4 == 0, ld % 4 == 0 and rows, S, Q are 16-byte aligned, one element at a time otherwise -- the same bits
+ *   either way.  order and start are device data: an index outside [0, N) adds nothing, offsets are clamped to
+ *   [0, n_order].
+ * ali_manifold_err: cf [M][D] fp32, row m at m * ld (ld >= D), 1 <= M <= 65535; owner, cls [M] DEVICE int32 (one graph
+ *   serves every batch); the four moment arrays; cnt [O * C], tcnt [C] int32: the rows per cell and per class.
+ *   out3 [M][3] = (same, other, ratio): with n = cnt[cell],
+ *     same  = sum_k (n a_k^2 - 2 a_k S_k + Q_k) / n
+ *     other = the same expression on (TS - S, TQ - Q, tcnt[class] - n)
+ *     ratio = same / other
+ *   evaluated in double per column, accumulated in double, each rounded to fp32 once (ratio from the unrounded two).
+ *   The reference's 0 / 0 is written out, not left to the arithmetic: n == 0 gives same = NaN; tcnt - n == 0 gives
+ *   other = NaN; an owner outside [0, O) with a valid class -- a subject the bank has never seen -- gives same = NaN
+ *   and other over the whole class; a class outside [0, C) gives three NaNs; ratio is NaN when either part is.  A row
+ *   equal to the only row of its cell gives same == 0 exactly.  A row is split over min(ceil(D / 4096), 64) blocks;
+ *   ws >= ALI_WS_RESERVED + 16 * M * that many bytes (two fp64 partials per row and block); the block that arrives
+ *   last folds each row's partials in block order; the arrival counter is the last int of the reserved head and is
+ *   left at zero.  16-byte loads when D % 4 == 0, ld % 4 == 0 and cf and the moment arrays are 16-byte aligned.
+ * Non-finite inputs (what falls out, untested): a NaN or infinite element makes the sums of its row (cf) or of its
+ *   cell and class (bank) NaN. */
+int ali_group_moments(const float* rows, int64_t ld, int32_t N, int32_t D, const int32_t* order, int32_t n_order,
+                      const int32_t* start, int32_t O, int32_t C, double* S, double* Q, double* TS, double* TQ,
+                      ali_stream_t stream);
+int ali_manifold_err(const float* cf, int64_t ld, int32_t M, int32_t D, const int32_t* owner, const int32_t* cls,
+                     const double* S, const double* Q, const double* TS, const double* TQ, const int32_t* cnt,
+                     const int32_t* tcnt, int32_t O, int32_t C, float* out3, void* ws, size_t ws_bytes,
+                     ali_stream_t stream);
+
 /* Attribute plumbing of one batch (mnist.py:47-55, audio_mnist.py:203-210, whalecalls.py:455): idx[b*n_cat + j] =
  * argmax of categorical attribute j (one-hot rows of n_classes[j] floats, or int32 when cat_is_int[j]; first maximum
  * like torch.argmax); cont[b*n_cont + j] = cont_in[j][b]. */
