@@ -29,27 +29,11 @@ products run on the fp32-MFMA GEMM (``ops.conv_fwd``, 1x1); ``ali_gl_init`` / ``
 """
 import math
 
-import numpy as np
 import torch
 
 from . import ops
 from .graphs import GraphCache
-from .source import _COUNTER_MUL, _M64, _mix64, _mix64_int
-
-_PHASE_STREAM = 0x474C504841534531            # csrc/griffinlim.hip: kPhaseStream
-
-
-def uniform_reference(seed, counter, n, offset=0):
-    """Host recipe of the initial phases ``ali_gl_init`` draws: a float32 CPU tensor [2, n], row 0 the real and row 1
-    the imaginary parts of elements ``offset .. offset + n`` (element e = (b*F + f)*T + t of a [B,F,T] batch) of the
-    stream keyed by (seed, counter).  Both are 24-bit fields (bits 40..63 / 16..39) of ``mix64(key ^ e)`` over 2^24:
-    exact in fp32, in [0, 1), bit-equal to the device's."""
-    key = _mix64_int(_mix64_int(_mix64_int(int(seed) & _M64) ^ (int(counter) * _COUNTER_MUL & _M64)) ^ _PHASE_STREAM)
-    g = np.arange(n, dtype=np.uint64) + np.uint64(int(offset) & _M64)
-    r = _mix64(np.uint64(key) ^ g)
-    re = (r >> np.uint64(40)).astype(np.float64) / 16777216.0
-    im = ((r >> np.uint64(16)) & np.uint64(0xFFFFFF)).astype(np.float64) / 16777216.0
-    return torch.from_numpy(np.stack([re, im]).astype(np.float32))
+from .rng import phase_reference as uniform_reference  # noqa: F401  (the host recipe of ali_gl_init's phases)
 
 
 def default_length(n_fft, hop, T):

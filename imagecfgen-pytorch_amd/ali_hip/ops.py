@@ -819,28 +819,30 @@ def rowmask_mul(x, mask, B, rows_per_img, C, out=None):
     return out
 
 
+def _rng_args(seed, ctr, offset=0):
+    """(seed, counter pointer, offset) as the launchers of the counter RNG take them (csrc/ali_rng.h): seed and offset
+    reduced to 64 bits, the counter None or a one-element int64 CUDA tensor"""
+    if ctr is not None and not (torch.is_tensor(ctr) and ctr.is_cuda and ctr.dtype == torch.int64 and ctr.numel() == 1):
+        raise ValueError("need a one-element int64 CUDA tensor as device counter")
+    return int(seed) & (2 ** 64 - 1), None if ctr is None else c_void_p(ctr.data_ptr()), int(offset) & (2 ** 64 - 1)
+
+
 def dropout_mask(seed, offset, p, B, C, device, dev_counter=None):
-    lib = _lib.load()
+    seed, ctr, offset = _rng_args(seed, dev_counter, offset)
     out = torch.empty(B, C, dtype=torch.float32, device=device)
-    ctr = None
-    if dev_counter is not None:
-        assert dev_counter.is_cuda and dev_counter.dtype == torch.int64
-        ctr = c_void_p(dev_counter.data_ptr())
-    _lib.check(lib.ali_dropout_mask(seed, offset, ctr, p, _chk(out), out.numel(), _stream()), "ali_dropout_mask")
+    _lib.check(_lib.load().ali_dropout_mask(seed, offset, ctr, p, _chk(out), out.numel(), _stream()), "ali_dropout_mask")
     return out
 
 
 def dropout_mask_multi(seed, dev_counter, seg_end, seg_p, seg_clog, seg_cpad, out):
     """one launch for all masks of an iteration; seg_* are host lists (see ali_hip.h)."""
-    lib = _lib.load()
     n = len(seg_end)
     ends = (ctypes.c_int64 * n)(*seg_end)
     ps = (ctypes.c_float * n)(*seg_p)
     cl = (ctypes.c_int32 * n)(*seg_clog)
     cp = (ctypes.c_int32 * n)(*seg_cpad)
-    ctr = None if dev_counter is None else c_void_p(dev_counter.data_ptr())
-    _lib.check(lib.ali_dropout_mask_multi(seed, ctr, ends, ps, cl, cp, n, _chk(out), _stream()),
-               "ali_dropout_mask_multi")
+    _lib.check(_lib.load().ali_dropout_mask_multi(*_rng_args(seed, dev_counter)[:2], ends, ps, cl, cp, n, _chk(out),
+                                                  _stream()), "ali_dropout_mask_multi")
     return out
 
 
@@ -848,11 +850,7 @@ def normal_fill(seed, out, dev_counter=None, offset=0):
     """out (contiguous fp32 CUDA, any shape, 4-byte aligned: slices are fine) <- N(0,1) draws ``offset .. offset +
     numel`` of the latent stream keyed by (seed, *dev_counter) (include/ali_hip.h: ali_normal_fill;
     ``ali_hip.source.normal_reference`` gives the same values on the host)."""
-    ctr = None
-    if dev_counter is not None:
-        assert dev_counter.is_cuda and dev_counter.dtype == torch.int64
-        ctr = c_void_p(dev_counter.data_ptr())
-    _lib.check(_lib.load().ali_normal_fill(int(seed) & (2 ** 64 - 1), ctr, int(offset), _chk(out, "out"), out.numel(),
+    _lib.check(_lib.load().ali_normal_fill(*_rng_args(seed, dev_counter, offset), _chk(out, "out"), out.numel(),
                                            _stream()), "ali_normal_fill")
     return out
 
@@ -1022,14 +1020,6 @@ def spect_post(y, B, T, F, out, mean=None, std=None, clip_k=3.0):
 GL_SRC_IMAGE, GL_SRC_LOG, GL_SRC_SPEC = 0, 1, 2
 
 
-def _counter_ptr(t):
-    if t is None:
-        return None
-    if not (t.is_cuda and t.dtype == torch.int64 and t.numel() == 1):
-        raise ValueError("need a one-element int64 CUDA tensor as device counter")
-    return c_void_p(t.data_ptr())
-
-
 def gl_check(n_fft, win, hop, T, length=0):
     """the window-envelope condition of ``torch.istft`` for T frames (include/ali_hip.h: ali_gl_check; host only):
     True / False, ``ValueError`` unless 0 < hop <= win <= n_fft"""
@@ -1047,8 +1037,8 @@ def gl_init(src, mode, mag, X, power=2.0, mean=None, std=None, stds_kept=3.0, an
     re, im = (None, None) if angles0 is None else angles0
     _lib.check(_lib.load().ali_gl_init(_chk(src, "src"), B, F, T, mode, _opt(mean, "mean"), _opt(std, "std"),
                                        float(stds_kept), float(power), _opt(re, "angles0.re"), _opt(im, "angles0.im"),
-                                       int(bool(rand_init)), int(seed) & (2 ** 64 - 1), _counter_ptr(dev_counter),
-                                       int(offset), _chk(mag, "mag"), _chk(X, "X"), _stream()), "ali_gl_init")
+                                       int(bool(rand_init)), *_rng_args(seed, dev_counter, offset), _chk(mag, "mag"),
+                                       _chk(X, "X"), _stream()), "ali_gl_init")
     return mag, X
 
 
@@ -1057,7 +1047,7 @@ def gl_ola(fr, renv, n_fft, hop, length, out, final=False, frames_per_block=0, a
     (include/ali_hip.h: ali_gl_ola)"""
     B, T, win = fr.shape
     _lib.check(_lib.load().ali_gl_ola(_chk(fr, "fr"), _chk(renv, "renv"), renv.numel(), B, T, n_fft, win, hop, int(length),
-                                      int(bool(final)), _chk(out, "out"), int(frames_per_block), _counter_ptr(advance),
+                                      int(bool(final)), _chk(out, "out"), int(frames_per_block), _rng_args(0, advance)[1],
                                       _stream()), "ali_gl_ola")
     return out
 
@@ -1141,9 +1131,8 @@ def gp_mix(x_real, x_fake, eps=None, seed=0, dev_counter=None, offset=0, out=Non
     if eps is not None and eps.numel() != B:
         raise ValueError(f"gp_mix: eps holds {eps.numel()} values for {B} images")
     eps_out = torch.empty(B, dtype=torch.float32, device=x_real.device)
-    _lib.check(_lib.load().ali_gp_mix(pr, _chk(x_fake, "x_fake"), _opt(eps, "eps"), int(seed) & (2 ** 64 - 1),
-                                      _counter_ptr(dev_counter), int(offset), B, P, _chk(out, "xhat"), _chk(eps_out),
-                                      _stream()), "ali_gp_mix")
+    _lib.check(_lib.load().ali_gp_mix(pr, _chk(x_fake, "x_fake"), _opt(eps, "eps"), *_rng_args(seed, dev_counter, offset),
+                                      B, P, _chk(out, "xhat"), _chk(eps_out), _stream()), "ali_gp_mix")
     return out, eps_out
 
 
@@ -1289,8 +1278,8 @@ def gumbel_posterior(logits, y, g=None, seed=0, dev_counter=None, offset=0, want
     noise = torch.empty_like(logits)
     g_out = torch.empty_like(logits) if want_g else None
     _lib.check(_lib.load().ali_gumbel_posterior(_chk(logits, "logits"), c_void_p(y.data_ptr()), _opt(g, "g"),
-                                                int(seed) & (2 ** 64 - 1), _counter_ptr(dev_counter), int(offset), N, C,
-                                                _chk(noise), _opt(g_out), _stream()), "ali_gumbel_posterior")
+                                                *_rng_args(seed, dev_counter, offset), N, C, _chk(noise), _opt(g_out),
+                                                _stream()), "ali_gumbel_posterior")
     return noise, g_out
 
 
@@ -1473,15 +1462,11 @@ def vae_latent_fwd(mean, log_var, S, out, k=0.5, eps=None, seed=0, dev_counter=N
     ptrs, ncls, isint = _attr_arrays(onehots)
     tptr = (c_void_p * max(len(tables), 1))(*[t.data_ptr() for t in tables])
     kl = torch.empty(1, dtype=torch.float32, device=mean.device) if want_kl else None
-    ctr = None
-    if dev_counter is not None:
-        assert dev_counter.is_cuda and dev_counter.dtype == torch.int64
-        ctr = c_void_p(dev_counter.data_ptr())
     ws = workspace(mean.device)
     _lib.check(lib.ali_vae_latent_fwd(
         _row_view(mean, L, "mean"), _row_view(log_var, L, "log_var"), mean.stride(0),
         None if eps is None else c_void_p(eps.data_ptr()), None if eps_out is None else c_void_p(eps_out.data_ptr()),
-        int(seed) & (2 ** 64 - 1), ctr, int(offset), S, B, L, float(k), ptrs, ncls, isint, tptr, len(tables),
+        *_rng_args(seed, dev_counter, offset), S, B, L, float(k), ptrs, ncls, isint, tptr, len(tables),
         _opt(cont, "cont"), 0 if cont is None else cont.shape[1], int(write_cond), ld, _chk(out, "out"), _opt(kl),
         c_void_p(ws.data_ptr()), ws.numel(), _stream()), "ali_vae_latent_fwd")
     return kl, (eps if eps is not None else eps_out)

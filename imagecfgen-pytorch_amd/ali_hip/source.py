@@ -4,89 +4,15 @@
 ``DeviceDataset``   the images, attributes and attribute statistics of a MorphoMNIST-style data set, uploaded once;
                     an epoch is one uploaded permutation, a batch one slice of it, and ``AliStepper.step_indexed``
                     assembles the batch on the device (``ali_batch_gather``) inside its captured iteration.
-``normal_reference``  the definition of the latent generator ``ali_normal_fill`` implements, evaluated in fp64 on the
-                    host: anyone who wants the latents of a run reproduces them from (z_seed, iteration, index).
+``normal_reference``  the latent generator ``ali_normal_fill`` implements, in fp64 on the host; it and the other host
+                    references of the device's draws live in ``ali_hip.rng`` and are re-exported here.
 """
 import numpy as np
 import torch
 
 from . import ops
-
-DEFAULT_Z_SEED = 0x5EED
-_LATENT_STREAM = 0x4C4154454E545A31          # csrc/elementwise.hip: kLatentStream
-_COUNTER_MUL = 0xD1B54A32D192ED03
-_M64 = (1 << 64) - 1
-
-
-def _mix64(z):
-    """splitmix64's finaliser (csrc/elementwise.hip: mix64) on a uint64 array"""
-    with np.errstate(over="ignore"):
-        z = z + np.uint64(0x9E3779B97F4A7C15)
-        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-        return z ^ (z >> np.uint64(31))
-
-
-def _mix64_int(z):
-    return int(_mix64(np.array([z & _M64], dtype=np.uint64))[0])
-
-
-def rank_seed(z_seed, rank):
-    """the seed data-parallel rank ``rank`` draws its latents with (rank 0: ``z_seed`` itself)"""
-    z_seed = int(z_seed) & _M64
-    return z_seed if rank == 0 else _mix64_int(z_seed ^ (rank * _COUNTER_MUL & _M64))
-
-
-def latent_bits(seed, counter, n, offset=0):
-    """The integers behind elements ``offset .. offset + n`` of the latent stream keyed by (seed, counter):
-    (k1 in [1, 2^24], k2 in [0, 2^24), odd) -- element g = offset + i is
-    ``sqrt(-2 ln(k1 / 2^24)) * (sin if odd else cos)(2 pi k2 / 2^24)``, k1 / k2 being bits 40..63 / 16..39 of
-    ``mix64(key ^ (g >> 1))``."""
-    key = _mix64_int(_mix64_int(_mix64_int(int(seed)) ^ (int(counter) * _COUNTER_MUL & _M64)) ^ _LATENT_STREAM)
-    g = np.arange(n, dtype=np.uint64) + np.uint64(int(offset) & _M64)
-    r = _mix64(np.uint64(key) ^ (g >> np.uint64(1)))
-    k1 = (r >> np.uint64(40)).astype(np.int64) + 1
-    k2 = ((r >> np.uint64(16)) & np.uint64(0xFFFFFF)).astype(np.int64)
-    return k1, k2, (g & np.uint64(1)).astype(bool)
-
-
-def normal_reference(seed, counter, n, offset=0):
-    """fp64 host evaluation of ``ali_normal_fill(seed, &counter, offset, out, n)``: a float64 CPU tensor [n].  The
-    integers are exact on both sides; the device differs by the rounding of its fp32 log / sqrt / sin / cos only."""
-    k1, k2, odd = latent_bits(seed, counter, n, offset)
-    rad = np.sqrt(-2.0 * np.log(k1 / 16777216.0))
-    ang = (2.0 * np.pi) * (k2 / 16777216.0)
-    return torch.from_numpy(rad * np.where(odd, np.sin(ang), np.cos(ang)))
-
-
-_GP_STREAM = 0x47504D4958455053              # csrc/gan.hip: kGpStream
-
-
-def uniform_reference(seed, counter, n, offset=0):
-    """host evaluation of the per-image ``eps`` that ``ali_gp_mix(eps=NULL, seed, &counter, offset, B=n, ...)`` draws: a
-    float32 CPU tensor [n], exact (k / 2^24, k the top 24 bits of ``mix64(key ^ g)`` under the latent key mixed once
-    more with the stream's constant)."""
-    key = _mix64_int(_mix64_int(_mix64_int(int(seed)) ^ (int(counter) * _COUNTER_MUL & _M64)) ^ _LATENT_STREAM)
-    key = _mix64_int(key ^ _GP_STREAM)
-    g = np.arange(n, dtype=np.uint64) + np.uint64(int(offset) & _M64)
-    k = (_mix64(np.uint64(key) ^ g) >> np.uint64(40)).astype(np.int64)
-    return torch.from_numpy((k / 16777216.0).astype(np.float32))
-
-
-_GUMBEL_STREAM = 0x47554D42454C3031           # csrc/flow.hip: kGumbelStream
-
-
-def gumbel_reference(seed, counter, n, offset=0):
-    """fp64 host evaluation of the Gumbel(0, 1) draws of ``ali_gumbel_posterior(g=NULL, seed, &counter, offset, ...)``:
-    a float64 CPU tensor [n], element e = offset + row * C + class.  g = -log(-log u) with u = (k + 0.5) / 2^24
-    strictly inside (0, 1), k the top 24 bits of ``mix64(key ^ e)`` under the latent key mixed once more with the
-    stream's constant.  k is exact on both sides; the device evaluates the logarithms in fp64 too and rounds g to fp32
-    once, so ``gumbel_reference(...).float()`` is what it stores, up to the last bit of the device's log."""
-    key = _mix64_int(_mix64_int(_mix64_int(int(seed)) ^ (int(counter) * _COUNTER_MUL & _M64)) ^ _LATENT_STREAM)
-    key = _mix64_int(key ^ _GUMBEL_STREAM)
-    e = np.arange(n, dtype=np.uint64) + np.uint64(int(offset) & _M64)
-    k = (_mix64(np.uint64(key) ^ e) >> np.uint64(40)).astype(np.float64)
-    return torch.from_numpy(-np.log(-np.log((k + 0.5) / 16777216.0)))
+from .rng import (DEFAULT_Z_SEED, gumbel_reference, latent_bits, normal_reference, rank_seed,  # noqa: F401
+                  uniform_reference)
 
 
 class DeviceDataset:

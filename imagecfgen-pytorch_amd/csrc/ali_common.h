@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include "../../include/ali_hip.h"
+#include "ali_rng.h"   // the counter RNG: mix64, the stream keys, normal_pair / normal_at
 
 namespace ali {
 
@@ -78,35 +79,6 @@ inline size_t ws_payload_bytes(size_t bytes) { return bytes > kWsReserved ? byte
 // entry points: the ABI's stream handle as HIP's, and whether a base pointer allows 16-byte accesses
 #define ST(s) ((hipStream_t)(s))
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-// splitmix64's finaliser: the hash of the counter RNG (Dropout2d masks, latents: elementwise.hip; Griffin-Lim phases:
-// griffinlim.hip).  A stream's key is mix64(mix64(seed) ^ counter * kCounterMul), one more round per stream constant.
-constexpr uint64_t kCounterMul = 0xD1B54A32D192ED03ull;
-__host__ __device__ __forceinline__ uint64_t mix64(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-// The latent stream of ali_normal_fill (elementwise.hip; ali_hip/source.py: normal_reference): element g is one half of
-// the Box-Muller pair of hash g >> 1 under the key mix64(mix64(mix64(seed) ^ counter * kCounterMul) ^ kLatentStream).
-constexpr uint64_t kLatentStream = 0x4C4154454E545A31ull;
-__device__ __forceinline__ void normal_pair(uint64_t key, uint64_t pair, float& c, float& s) {
-  const uint64_t r = mix64(key ^ pair);
-  const float u1 = (float)((uint32_t)(r >> 40) + 1u) * (1.f / 16777216.f);
-  const float u2 = (float)((uint32_t)(r >> 16) & 0xFFFFFFu) * (1.f / 16777216.f);
-  const float rad = sqrtf(-2.f * logf(u1));
-  float sn, cs;
-  sincospif(2.f * u2, &sn, &cs);        // (the angle 2*pi*u2 without rounding 2*pi*u2 itself)
-  c = rad * cs;
-  s = rad * sn;
-}
-__device__ __forceinline__ float normal_at(uint64_t key, uint64_t g) {
-  float c, s;
-  normal_pair(key, g >> 1, c, s);
-  return (g & 1) ? s : c;
-}
 
 __device__ __forceinline__ float apply_act(float v, int act, float slope) {
   if (act == ALI_ACT_LEAKY) return v > 0.f ? v : v * slope;

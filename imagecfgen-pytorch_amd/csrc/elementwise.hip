@@ -204,16 +204,15 @@ __global__ void rowmask_mul_kernel(const float* __restrict__ x, const float* __r
   }
 }
 
-// splitmix64-based counter RNG (mix64: ali_common.h): one draw per (seed, offset + i)
+// the counter RNG (ali_rng.h): one draw per (seed, offset + i)
 __global__ void dropout_mask_kernel(uint64_t seed, uint64_t offset, const long long* __restrict__ dev_counter, float p,
                                     float* __restrict__ out, long long n) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const long long step = (long long)gridDim.x * blockDim.x;
   const float keep = 1.f - p, inv = 1.f / (1.f - p);
-  const uint64_t key = mix64(mix64(seed) ^ (dev_counter ? (uint64_t)dev_counter[0] * 0xD1B54A32D192ED03ull : 0ull));
+  const uint64_t key = rng_base_key(seed, dev_counter);
   for (; i < n; i += step) {
-    const uint64_t r = mix64(key ^ (offset + (uint64_t)i));
-    const float u = (float)(r >> 40) * (1.f / 16777216.f);
+    const float u = (float)hi24(hash_at(key, offset + (uint64_t)i)) * kInv24;
     out[i] = u < keep ? inv : 0.f;
   }
 }
@@ -229,7 +228,7 @@ __global__ void dropout_mask_multi_kernel(uint64_t seed, const long long* __rest
   const long long d0 = segs.draw_start[s];
   const int clog = segs.clog[s], cpad = segs.cpad[s];
   const float p = segs.p[s], keep = 1.f - p, inv = 1.f / (1.f - p);
-  const uint64_t key = mix64(mix64(seed) ^ (dev_counter ? (uint64_t)dev_counter[0] * 0xD1B54A32D192ED03ull : 0ull));
+  const uint64_t key = rng_base_key(seed, dev_counter);
   const long long step = (long long)gridDim.x * blockDim.x;
   float* o = out + lo;
   for (long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += step) {
@@ -240,8 +239,7 @@ __global__ void dropout_mask_multi_kernel(uint64_t seed, const long long* __rest
       if (c >= clog) { o[j] = 1.f; continue; }
       di = b * clog + c;
     }
-    const uint64_t r = mix64(key ^ (uint64_t)(d0 + di));
-    const float u = (float)(r >> 40) * (1.f / 16777216.f);
+    const float u = (float)hi24(hash_at(key, (uint64_t)(d0 + di))) * kInv24;
     o[j] = u < keep ? inv : 0.f;
   }
 }
@@ -1019,19 +1017,16 @@ __global__ void __launch_bounds__(256) copy_multi_kernel(const CopyJobs jobs) {
 }
 
 // ---- device-side input pipeline: the latent draw and the batch assembly of a training iteration ---------------------
-// z ~ N(0,1) from the counter RNG of the Dropout2d masks.  Element g = offset + i is one half of the Box-Muller pair
-// of hash g >> 1 (even g: cosine, odd g: sine), so a value depends on (seed, counter, g) only -- not on the launch
-// geometry, the split of a buffer over launches or the alignment of ``out``.  u1 in (0,1] and u2 in [0,1) are the
-// hash's bits 40..63 and 16..39.  kLatentStream separates the latents' keys from the masks' (one more mix64 round
-// over the masks' key).  ali_hip/source.py: normal_reference is the same recipe in fp64.
-// (kLatentStream, normal_pair, normal_at: ali_common.h -- csrc/vae.hip draws from the same stream)
+// z ~ N(0,1) from the latent stream of the counter RNG (ali_rng.h: latent_key, normal_pair, normal_at; csrc/vae.hip
+// draws from the same stream; ali_hip/rng.py: normal_reference is the same recipe in fp64).  A value depends on
+// (seed, counter, g = offset + i) only -- not on the launch geometry, the split of a buffer over launches or the
+// alignment of ``out``.
 // ``head`` elements in front of the first 16-byte boundary of ``out`` and the < 4 behind the last whole vector are
 // stored one by one by block 0; everything between as float4.
 __global__ void __launch_bounds__(kEwBlock)
 normal_fill_kernel(uint64_t seed, const long long* __restrict__ dev_counter, uint64_t offset, float* __restrict__ out,
                    long long n, int head) {
-  const uint64_t key = mix64(mix64(mix64(seed) ^ (dev_counter ? (uint64_t)dev_counter[0] * 0xD1B54A32D192ED03ull : 0ull))
-                             ^ kLatentStream);
+  const uint64_t key = latent_key(rng_base_key(seed, dev_counter));
   const long long nvec = (n - head) >> 2, tail0 = head + 4 * nvec;
   const long long step = (long long)gridDim.x * blockDim.x;
   for (long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += step) {

@@ -42,7 +42,6 @@ constexpr double kBnEps = 1e-5;
 constexpr double kHalfLog2Pi = 0.91893853320467274178;
 constexpr double kBound = 3.0;
 constexpr double kPMin = (double)FLT_MIN, kPMax = 1.0 - (double)FLT_EPSILON;
-constexpr uint64_t kGumbelStream = 0x47554D42454C3031ull;   // one more mix64 round over the latent key
 
 struct FlowParams {
   double g, log_g, beta;
@@ -482,7 +481,7 @@ constexpr int kGumbelWaves = 4;
 
 // Gumbel(0, 1) = -log(-log u), u = (k + 0.5) / 2^24 strictly inside (0, 1): the top 24 bits of the hash of element e
 __device__ __forceinline__ float gumbel_at(uint64_t key, uint64_t e) {
-  const double u = ((double)(uint32_t)(mix64(key ^ e) >> 40) + 0.5) * (1.0 / 16777216.0);
+  const double u = ((double)hi24(hash_at(key, e)) + 0.5) * (double)kInv24;
   return (float)-log(-log(u));
 }
 
@@ -491,8 +490,7 @@ gumbel_posterior_kernel(const float* __restrict__ logits, const long long* __res
                         uint64_t seed, const long long* __restrict__ dev_counter, uint64_t offset, int N, int C,
                         float* __restrict__ noise, float* __restrict__ g_out) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const uint64_t key = mix64(mix64(mix64(mix64(seed) ^ (dev_counter ? (uint64_t)dev_counter[0] * kCounterMul : 0ull))
-                                   ^ kLatentStream) ^ kGumbelStream);
+  const uint64_t key = gumbel_key(rng_base_key(seed, dev_counter));
   for (long long n = (long long)blockIdx.x * kGumbelWaves + wave; n < N; n += (long long)gridDim.x * kGumbelWaves) {
     const float* z = logits + n * C;
     const long long yn = y[n];

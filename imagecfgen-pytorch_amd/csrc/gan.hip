@@ -19,14 +19,11 @@ namespace ali {
 constexpr int kGpThreads = 1024;
 constexpr int kGpWaves = kGpThreads / 64;
 constexpr int kMixThreads = 256;
-constexpr uint64_t kGpStream = 0x47504D4958455053ull;     // one more mix64 round over the latent key: eps is a stream of its own
 
 struct GpPart { unsigned long long pen_bits; unsigned long long norm_bits; };
 
-// uniform in [0, 1): the top 24 bits of the hash of image g under the stream's key
-__device__ __forceinline__ float gp_uniform(uint64_t key, uint64_t g) {
-  return (float)(uint32_t)(mix64(key ^ g) >> 40) * (1.f / 16777216.f);
-}
+// uniform in [0, 1): the top 24 bits of the hash of image g under the stream's key (ali_rng.h: gp_key)
+__device__ __forceinline__ float gp_uniform(uint64_t key, uint64_t g) { return (float)hi24(hash_at(key, g)) * kInv24; }
 
 // The products and the sum are rounded one by one -- contraction into a fused multiply-add is switched off for this
 // function -- so the result is torch's fp32 statement eps * x_real + (1 - eps) * x_fake bit for bit.
@@ -46,9 +43,7 @@ gp_mix_kernel(const float* __restrict__ x_real, const float* __restrict__ x_fake
   if (eps_in) {
     e = eps_in[b];
   } else {
-    const uint64_t key = mix64(mix64(mix64(mix64(seed) ^ (dev_counter ? (uint64_t)dev_counter[0] * kCounterMul : 0ull))
-                                     ^ kLatentStream) ^ kGpStream);
-    e = gp_uniform(key, offset + (uint64_t)b);
+    e = gp_uniform(gp_key(rng_base_key(seed, dev_counter)), offset + (uint64_t)b);
   }
   if (eps_out && blockIdx.x == 0 && threadIdx.x == 0) eps_out[b] = e;
   const float om = 1.f - e;

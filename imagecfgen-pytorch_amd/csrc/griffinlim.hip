@@ -15,8 +15,6 @@
 
 namespace ali {
 
-
-constexpr uint64_t kPhaseStream = 0x474C504841534531ull;   // "GLPHASE1": separates the phases' keys from masks / latents
 constexpr int kGlBlock = 256;
 
 // ---- ali_gl_init ---------------------------------------------------------------------------------------------------
@@ -28,8 +26,7 @@ gl_init_kernel(const float* __restrict__ src, int F, int T, int mode, const floa
   __shared__ float tile[3][32][33];
   const int b = blockIdx.z, t0 = blockIdx.x * 32, f0 = blockIdx.y * 32;
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;   // 32 x 8
-  const uint64_t key = mix64(mix64(mix64(seed) ^ (dev_counter ? (uint64_t)dev_counter[0] * kCounterMul : 0ull))
-                             ^ kPhaseStream);
+  const uint64_t key = phase_key(rng_base_key(seed, dev_counter));
   for (int r = ty; r < 32; r += 8) {                        // rows = frequencies, columns = frames (contiguous in src)
     const int f = f0 + r, t = t0 + tx;
     float m = 0.f, re = 0.f, im = 0.f;
@@ -43,9 +40,9 @@ gl_init_kernel(const float* __restrict__ src, int F, int T, int mode, const floa
         re = a0_re[e];
         im = a0_im[e];
       } else if (rand_init) {                               // both parts from one hash: disjoint 24-bit fields, exact in fp32
-        const uint64_t h = mix64(key ^ (offset + (uint64_t)e));
-        re = (float)(uint32_t)(h >> 40) * (1.f / 16777216.f);
-        im = (float)((uint32_t)(h >> 16) & 0xFFFFFFu) * (1.f / 16777216.f);
+        const uint64_t h = hash_at(key, offset + (uint64_t)e);
+        re = (float)hi24(h) * kInv24;
+        im = (float)lo24(h) * kInv24;
       } else {
         re = 1.f;
       }

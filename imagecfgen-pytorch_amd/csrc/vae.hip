@@ -4,7 +4,7 @@
 //   latent forward   z[s,b,:] = mean[b] + eps[s,b] * exp(k * log_var[b]) written into columns 0..L of the decoder's input
 //                    rows [S*B][ld], the conditioning columns behind them ([onehot_j @ table_j | cont | 0], the row of
 //                    ali_g_input) in the same launch, and sum_b dkl_b, dkl_b = 0.5 sum_l (e^lv + mean^2 - 1 - lv).
-//                    eps is given or drawn here from the latent stream of ali_normal_fill (ali_common.h: normal_at).
+//                    eps is given or drawn here from the latent stream of ali_normal_fill (ali_rng.h: normal_at).
 //   log-likelihood   mean_b (1/S) sum_s log N(x_b; xhat_sb, e^log_var I), the loss -(lp - kl_weight * mean_b dkl) and
 //                    gxhat = gscale * (xhat - x) * e^-log_var / (S*B).
 //   latent backward  the [B][2L]-style head gradient from the decoder input gradient's columns 0..L, and the sum over s of
@@ -58,8 +58,7 @@ vae_latent_fwd_kernel(const float* __restrict__ mean, const float* __restrict__ 
   const float* v = lv + (long long)b * head_ld;
   float* o = out + row * ld;
   uint64_t key = 0;
-  if (!eps_in)
-    key = mix64(mix64(mix64(seed) ^ (dev_counter ? (uint64_t)dev_counter[0] * kCounterMul : 0ull)) ^ kLatentStream);
+  if (!eps_in) key = latent_key(rng_base_key(seed, dev_counter));
   double acc = 0.0;
   for (int l = threadIdx.x; l < L; l += kVaeBlock) {
     const double mv = (double)m[l], vv = (double)v[l];
