@@ -466,6 +466,15 @@ __device__ __forceinline__ void wgrad_fast_body(const WDesc& d, const unsigned x
         }
         __syncthreads();
       }
+    } else if (do_db && t < BN) {
+      // An empty slab still owns its row of dbws, which the fold adds: the split rounds its slabs up to whole k-tiles,
+      // so the last ones of a launch can start past npix (840 pixels in 13 slabs of 96: four of them).  The other loops
+      // reach their store below with dbacc = 0; this one used to leave the row as the workspace had it.
+      const int n = n0 + t;
+      if (n < d.Cd_log) {
+        if (d.splitk > 1) d.dbws[(long long)bz_ * d.Cd + n] = 0.f;
+        else d.db[n] = 0.f;
+      }
     }
   } else if constexpr (F16 == 1 && TAB) {
     if (pix_begin < pix_end) {

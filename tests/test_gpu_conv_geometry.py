@@ -216,8 +216,9 @@ def _tile_name():
     return "x".join(os.environ.get(k, "-") for k in ("ALI_BM", "ALI_BN", "ALI_WBM", "ALI_WBN"))
 
 
-def check(c, r, name, got, what=None):
-    """both bounds of the module docstring for output ``name`` of case ``c``; prints the figures before it asserts"""
+def check(c, r, name, got, what=None, prefix="GEOM", cap_only=CAP_ONLY):
+    """both bounds of the module docstring for output ``name`` of case ``c``; prints the figures before it asserts
+    (``prefix`` / ``cap_only``: the line tag and the CAP_ONLY table of the fp16 module, which shares this function)"""
     ref, f32 = r["ref"][name], r["f32"][name]
     got = got.detach().double().cpu()
     assert got.shape == ref.shape, (c.id, name, got.shape, ref.shape)
@@ -225,11 +226,11 @@ def check(c, r, name, got, what=None):
     e_dev = (got - ref).abs().max().item()
     e_cpu = (f32.double() - ref).abs().max().item()
     label = what or name
-    print(f"GEOM case={c.id} tile={_tile_name()} out={label} e_dev={e_dev:.3e} e_cpu={e_cpu:.3e} "
+    print(f"{prefix} case={c.id} tile={_tile_name()} out={label} e_dev={e_dev:.3e} e_cpu={e_cpu:.3e} "
           f"ratio={e_dev / max(e_cpu, 1e-300):.2f} rel={e_dev / max(scale, 1e-300):.2e}")
     assert not math.isnan(e_dev), f"{c.id} {label}: NaN left in the output"
     assert e_dev <= RTOL * scale, f"{c.id} {label}: max err {e_dev:.3e} vs {RTOL} * {scale:.3e}"
-    if (c.id, name) not in CAP_ONLY:
+    if (c.id, name) not in cap_only:
         assert e_dev <= YARD * e_cpu, f"{c.id} {label}: max err {e_dev:.3e} > {YARD} * {e_cpu:.3e} (CPU fp32)"
 
 
