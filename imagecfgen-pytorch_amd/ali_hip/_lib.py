@@ -31,6 +31,13 @@ class AliEpilogue(Structure):
                 ("in_ch_live", c_int32), ("bn_slots", c_int32), ("dact_y16", c_void_p)]
 
 
+class AliConvPlan(Structure):
+    _fields_ = [(n, c_int32) for n in ("route", "bm", "bn", "mode", "f16", "uni", "threads", "ntile_m", "ntile_n",
+                                       "tile_rows", "pixel_major", "splitk", "kt_per_split", "tail_split", "tail_u0",
+                                       "lin1d", "xcd_chunk", "ordered", "grid_x", "grid_y", "grid_z", "job_variant",
+                                       "empty")]
+
+
 class AliWgradFold(Structure):
     _fields_ = [("ws", c_void_p), ("dst", c_void_p), ("dbws", c_void_p), ("db", c_void_p),
                 ("slab", c_int64), ("s_dc", c_int64), ("s_gc", c_int64), ("s_tap", c_int64),
@@ -60,6 +67,8 @@ SIGNATURES = {
     "ali_conv_writes_out16": (c_int32, [POINTER(AliConvGeom), c_int32]),
     "ali_conv_uses_f16": (c_int32, [POINTER(AliConvGeom), c_int32, POINTER(AliEpilogue)]),
     "ali_conv_tile_order": (c_int32, [POINTER(AliConvGeom), c_int32, c_int32, c_void_p, c_int32]),
+    "ali_conv_plan": (c_int32, [POINTER(AliConvGeom), c_int32, POINTER(AliEpilogue), c_size_t, c_int32, c_int32,
+                                POINTER(AliConvPlan)]),
     "ali_conv_fwd": (c_int32, [POINTER(AliConvGeom), c_void_p, c_void_p, c_void_p, POINTER(AliEpilogue), c_void_p,
                                c_size_t, c_void_p]),
     "ali_conv_bwd_data": (c_int32, [POINTER(AliConvGeom), c_void_p, c_void_p, c_void_p, POINTER(AliEpilogue),

@@ -3,6 +3,7 @@ stream from ``torch.cuda.current_stream()``).  PyTorch is plumbing here: memory,
 streams, autograd bookkeeping.  Every function requires CUDA fp32 contiguous
 tensors and raises otherwise -- there is no fallback path.
 """
+import collections
 import ctypes
 from ctypes import byref, c_void_p
 
@@ -157,6 +158,22 @@ def conv_mtiles(g: AliConvGeom, which: int):
         n = _lib.load().ali_conv_mtiles(byref(g), which, f16, byref(rows), byref(pm))
         hit = _MTILES[key] = (n, rows.value, bool(pm.value))
     return hit
+
+
+ConvPlan = collections.namedtuple("ConvPlan", [n for n, _ in _lib.AliConvPlan._fields_])
+
+
+def conv_plan(g: AliConvGeom, which: int, ep: AliEpilogue = None, ws_bytes=None, as_job=False) -> ConvPlan:
+    """What ali_conv_fwd (0) / ali_conv_bwd_data (1) would launch for ``g`` and ``ep`` (default: a plain epilogue of the
+    current ``precision``) with a workspace of ``ws_bytes`` (default: the size ``workspace`` allocates), recorded as a
+    ``gemm_batch`` job when ``as_job`` (include/ali_hip.h: AliConvPlan).  Host side only: nothing is launched."""
+    if ep is None:
+        ep = AliEpilogue(mfma_f16=int(_PRECISION["f16"]))
+    ws_bytes = _WS_BYTES if ws_bytes is None else int(ws_bytes)
+    plan = _lib.AliConvPlan()
+    _lib.check(_lib.load().ali_conv_plan(byref(g), which, byref(ep), ws_bytes, int(ws_bytes > 0), int(bool(as_job)),
+                                         byref(plan)), "ali_conv_plan")
+    return ConvPlan(*(getattr(plan, n) for n in ConvPlan._fields))
 
 
 class KernelProfile:

@@ -146,7 +146,7 @@ __device__ __forceinline__ void gconv_body(const GDesc& d, const int bx_, const 
   const int wm = wave / WAVES_N, wn = wave % WAVES_N;
 
   // Which (m-tile bx, n-tile by, k-slice bz of nsplit) this block is.  Plain launches: the 3-D block index.  "Tail split"
-  // launches (all-resident grids of 1-4 tiles per CU, see finalize_and_launch): a 1-D grid whose first tail_u0 blocks
+  // launches (all-resident grids of 1-4 tiles per CU, see plan_conv): a 1-D grid whose first tail_u0 blocks
   // take one whole tile each (multiples of the CU count: every CU the same number) and whose remaining blocks share
   // the left-over tiles tail_split ways along K -- so the left-over costs every CU 1/tail_split of a tile instead of
   // costing a few CUs a whole one while the rest idle.
@@ -1320,46 +1320,6 @@ static TileCfg pick_tile(long long M, int N, bool f16, int cin) {
   return best;
 }
 
-// tile shape, row order and M-tile count of a launch (everything the grid's x extent depends on)
-// dma_ok: the launch may use the 256 x 256 LDS-DMA fp16 kernel (both fp16 twins present, see finalize_and_launch); the
-// host-side queries (ali_conv_mtiles / ali_conv_tile_order) never say so -- such launches carry no fused BatchNorm, and a
-// dispatch-order table of another tile count is ignored by the launch
-static int plan_tiles(GDesc& d, bool vec, TileCfg& tc, int& max_taps, bool dma_ok = false) {
-  long long Mtot = 0;
-  max_taps = 0;
-  for (int i = 0; i < d.nphase; ++i) {
-    Mtot += d.ph[i].M;
-    if (d.ph[i].nr * d.ph[i].ns > max_taps) max_taps = d.ph[i].nr * d.ph[i].ns;
-    if (d.ph[i].M >= (1 << 24)) { set_error("gconv: more than 2^24 rows in one phase"); return -1; }
-  }
-  const bool f16_loop = d.f16 && vec && (d.Cin % BK) == 0;
-  const long long Mpick = Mtot * (tuning().tile_m_scale > 0 ? tuning().tile_m_scale : 1);
-  tc = pick_tile(Mpick, d.Cout, f16_loop, d.Cin);
-  if (tuning().bm > 0 && tuning().bn > 0) { tc.bm = tuning().bm; tc.bn = tuning().bn; }
-  if (tc.bm > 128 && !dma_ok) tc = pick_tile(Mpick, d.Cout, f16_loop, d.Cin);      // (a forced 256 x 256 applies to DMA launches only)
-  if (dma_ok && tuning().bm == 0) {
-    // 256 x 256 as soon as it fills the chip once (one block per CU).  Stand-alone (scratch/ub/dma_gemm.hip, a 1-D
-    // "convolution" with the layers' reuse): 881-1008 TF/s against 700-840 of the 128 x 128 register-staged loop.  Inside
-    // the ESRF iteration the forward convolutions 128 -> 256 ... 512 -> 1024 gain 5-8 % (697 -> 732, 781 -> 842, 783 ->
-    // 849 TF/s); launches in sub-pixel phases (data gradients: 786 -> 591) and tiny pixel-major maps (7 x 7: 911 -> 810)
-    // LOSE -- a 256-row tile spans two pixel positions, so fewer padding taps are skipped tile-wide, and there is no
-    // cost-ordered dispatch table for this tile: they keep the 128 x 128 loop.
-    const long long b256 = ((Mpick + 255) / 256) * (long long)((d.Cout + 255) / 256);
-    const bool plain = d.nphase == 1 && (long long)d.ph[0].Hq * d.ph[0].Wq >= 200;
-    if (plain && d.Cout >= 256 && b256 >= (kNumCU * 3) / 4) { tc.bm = 256; tc.bn = 256; }
-  }
-  if (!vec && tc.bn == 128) tc.bn = 64;
-  int tiles = 0;
-  for (int i = 0; i < d.nphase; ++i) {
-    // small maps with a large batch: order rows (pixel, image) so that every M-tile sees one pixel position
-    // and the taps falling outside the input (padding, 1x1 -> 3x3 transposed convs) are skipped tile-wide
-    d.ph[i].pixmajor = (d.ph[i].Hq * d.ph[i].Wq <= 1024 && d.B >= 64) ? 1 : 0;
-    d.ph[i].tile0 = tiles;
-    tiles += (d.ph[i].M + tc.bm - 1) / tc.bm;
-  }
-  return tiles;
-}
-
 // k-loop length (live taps) of every M-tile of a launch whose rows are ordered (pixel, image): the taps that fall
 // outside the input are skipped tile-wide, so edge tiles of padded / transposed convolutions are short.  Mirrors the
 // kernel's amask / tapmask computation.  Returns false when some phase is not pixel-major (tiles mix positions).
@@ -1386,181 +1346,60 @@ static bool tile_costs(const GDesc& d, int bm, std::vector<int>& cost) {
   return true;
 }
 
-// A recorded launch (AliGemmJob): everything finalize_and_launch decided, for ali_gemm_launch_multi
+// Everything the host decides for one ali_conv_fwd / ali_conv_bwd_data call.  plan_conv (below) is the only place that
+// decides; the launch (run_gemm), ali_conv_plan and the host queries read it.  AliConvPlan is its public image.
+enum { kRouteGemm = 0, kRouteFirst = 1, kRouteS2First = 2 };    // gconv_kernel* / conv_first_kernel / conv_s2_first_kernel
+struct GPlan {
+  int route;
+  int bm, bn;                                    // tile
+  int mode, f16, uni, threads;                   // kernel instance: MODE 0..3, F16 0..3, UNI, 256 / 512 threads
+  int ntile_m, ntile_n, tile_rows, pixel_major;  // grid shape (first-conv routes: one "tile" per image)
+  int splitk, kt_per_split, tail_split, tail_u0, lin1d, xcd_chunk;
+  int ordered;                                   // the caller's tile_order is followed
+  int grid_x, grid_y, grid_z;
+  int job_variant;                               // -1: launched at once; 0 / 1: recorded, <64,64> / <128,32> multi-job kernel
+  int empty;                                     // nothing to launch
+};
+static_assert(sizeof(GPlan) == sizeof(AliConvPlan), "AliConvPlan mirrors GPlan field by field");
+
+// A recorded launch (AliGemmJob): the descriptor and what ali_gemm_launch_multi needs of the plan
 struct GJobRec {
   uint64_t state;          // 1 = recorded
-  int variant;             // 0: <64,64,..,MODE 2> fp32, 1: <128,32,..,MODE 2> fp32 (the variants a multi-job kernel exists for)
+  int variant;             // GPlan.job_variant
   int gx, gy, gz;          // its own grid
   int cost;                // k-tiles per block (order of the jobs inside a combined launch)
   GDesc d;
 };
 static_assert(sizeof(GJobRec) <= sizeof(AliGemmJob), "AliGemmJob too small");
 
-static int finalize_and_launch(GDesc& d, void* ws, size_t ws_bytes, hipStream_t stream, bool vec, bool dense_k,
-                               AliGemmJob* job = nullptr) {
-  TileCfg tc;
-  int max_taps = 0;
-  const bool uni = vec && (d.Cin % BK) == 0;
-  // (fp16 launches are never recorded as jobs of a combined launch: a job pointer does not matter here)
-  const bool dma_ok = d.f16 && uni && d.in16 && d.w16 && (d.Cin % 64) == 0 && !d.ep.bn_part && d.ep.in_ld <= 0 &&
-                      tuning().no_dma16 == 0 && tuning().splitk == 0;
-  const int tiles = plan_tiles(d, vec, tc, max_taps, dma_ok);
-  if (tiles < 0) return ALI_ERR_BAD_ARG;
-  const bool dma = tc.bm == 256;
-  const int max_nkt = (max_taps * d.Cin + BK - 1) / BK;
-  const bool pow2 = vec && (d.Cin == 4 || d.Cin == 8 || d.Cin == 16) && max_taps <= kMaxTaps;
-  if (d.ep.bn_part) {
-    const AliEpilogue& e = d.ep;
-    bool ok = (e.bn_mode == 1 || e.bn_mode == 2) && !e.dact_y;
-    if (e.bn_mode == 2) ok = ok && !e.mask && e.bn_x && e.bn_mean && e.bn_invstd && e.bn_groups <= 1;
-    if (e.bn_mode == 1 && e.bn_groups > 1) {
-      ok = ok && d.nphase == 1 && d.B % e.bn_groups == 0;
-      const long long rows_g = (long long)(d.B / e.bn_groups) * (d.ph[0].pixmajor ? 1 : d.ph[0].Hq * d.ph[0].Wq);
-      ok = ok && rows_g % tc.bm == 0 && (!d.ph[0].pixmajor || d.B % tc.bm == 0);
-    }
-    if (!ok) { set_error("gconv: bad fused BatchNorm epilogue (see AliEpilogue / ali_conv_mtiles)"); return ALI_ERR_BAD_ARG; }
-    if (e.bn_slots > 0 && e.bn_slots != tiles) {
-      set_error("gconv: bn_part was sized for %d slots, this launch has %d M-tiles (stale ali_conv_mtiles result?)", e.bn_slots, tiles);
-      return ALI_ERR_BAD_ARG;
-    }
+// The kernel instances: (tile, MODE, F16, UNI) -> the stand-alone kernel and, for the two tiles whose fp32 uniform-tap
+// launches can be recorded as jobs, the multi-job kernel.  A tile without an instance runs the 64 x 64 one.
+struct GInstance {
+  void (*one)(const GDesc);
+  void (*multi)(const GJobs);
+};
+template <int BM, int BN, int WAVES_M, int WAVES_N>
+static GInstance tile_instance(int mode, int f16, bool uni) {
+  if (f16 == 2) return {gconv_kernel<BM, BN, WAVES_M, WAVES_N, 2, 2>, nullptr};
+  if (f16 == 1) return {gconv_kernel<BM, BN, WAVES_M, WAVES_N, 2, 1>, nullptr};
+  if (mode == 3) return {gconv_kernel<BM, BN, WAVES_M, WAVES_N, 3>, nullptr};
+  if (mode == 1) return {gconv_kernel<BM, BN, WAVES_M, WAVES_N, 1>, nullptr};
+  if (mode == 0) return {gconv_kernel<BM, BN, WAVES_M, WAVES_N, 0>, nullptr};
+  if constexpr ((BM == 64 && BN == 64) || (BM == 128 && BN == 32)) {
+    if (uni) return {gconv_kernel<BM, BN, WAVES_M, WAVES_N, 2, 0, true>, gconv_multi_kernel<BM, BN, WAVES_M, WAVES_N, 2, 0, true>};
+    return {gconv_kernel<BM, BN, WAVES_M, WAVES_N, 2>, gconv_multi_kernel<BM, BN, WAVES_M, WAVES_N, 2>};
+  } else {
+    if (uni) return {gconv_kernel<BM, BN, WAVES_M, WAVES_N, 2, 0, true>, nullptr};
+    return {gconv_kernel<BM, BN, WAVES_M, WAVES_N, 2>, nullptr};
   }
-  const int ntile_n = (d.Cout + tc.bn - 1) / tc.bn;
-  d.ldi = d.Cin;
-  if (d.ep.in_ld > 0 || d.ep.out_ld > 0) {     // operands that are column ranges of wider row-major buffers
-    if ((d.ep.in_ld > 0 && (d.ep.in_ld < d.Cin || (vec && d.ep.in_ld % 4))) ||
-        (d.ep.out_ld > 0 && (d.ep.out_ld < d.Cout || d.ep.bn_part))) {
-      set_error("gconv: bad in_ld / out_ld (>= the channel count, in_ld % 4 == 0 for vector gathers, no out_ld with fused BatchNorm)");
-      return ALI_ERR_BAD_ARG;
-    }
-    if (d.ep.in_ld > 0) d.ldi = d.ep.in_ld;
-    if (d.ep.out_ld > 0) d.ldo = d.ep.out_ld;
-  }
-  d.out_elems = (long long)d.B * d.Hout * d.Wout * d.ldo;
-  const long long in_elems = ((long long)d.B * d.Hin * d.Win - 1) * d.ldi + d.Cin;
-  const long long w_elems = (long long)d.Cout * d.ldw;
-  if (d.out_elems >= (1LL << 31) || in_elems >= (1LL << 30) || w_elems >= (1LL << 29)) {
-    set_error("gconv: tensor too large for 32-bit byte offsets");
-    return ALI_ERR_BAD_ARG;
-  }
-  d.in_bytes = (unsigned)(in_elems * 4);
-  d.w_bytes = (unsigned)(w_elems * 4);
-  // split-K when the grid cannot give every CU two blocks.  All blocks of such a grid are resident at once, so the
-  // launch lasts as long as the fullest CU: n = ceil(blocks*S / CUs) blocks of nkt/S k-tiles each, a little slower
-  // per block when the CU holds fewer than 4, plus about half a k-tile of slab traffic per slab
-  // (scratch/sweep_splitk.py).  Data-gradient launches skip dead taps tile by tile, so their k-depth is not known
-  // here: they keep the plain "two blocks per CU" rule.
-  int S = 1;
-  const long long blocks = (long long)tiles * ntile_n;
-  if (blocks < 2 * kNumCU && max_nkt >= 8 && dense_k) {
-    static const double eff[5] = {1.0, 0.82, 0.96, 0.99, 1.0};
-    double best = 1e30;
-    for (int sc = 1; sc <= 8 && max_nkt / sc >= 4; ++sc) {
-      if (sc > 1 && (size_t)sc * d.out_elems * sizeof(float) > ws_payload_bytes(ws_bytes)) break;
-      const long long n = (blocks * sc + kNumCU - 1) / kNumCU;
-      const double cost = (double)n / sc / eff[n < 4 ? n : 4] * max_nkt + (sc > 1 ? 0.5 * sc : 0.0);
-      if (cost < 0.97 * best) { best = cost; S = sc; }
-    }
-  } else if (blocks < 2 * kNumCU && max_nkt >= 8) {
-    S = (int)((2 * kNumCU + blocks - 1) / blocks);
-    if (S > max_nkt / 4) S = max_nkt / 4;
-    if (S > 32) S = 32;
-    while (S > 1 && (size_t)S * d.out_elems * sizeof(float) > ws_payload_bytes(ws_bytes)) --S;
-    if (S < 1) S = 1;
-  }
-  if (tuning().splitk > 0 && (size_t)tuning().splitk * d.out_elems * sizeof(float) <= ws_payload_bytes(ws_bytes))
-    S = tuning().splitk;
-  if (dma) S = 1;                      // (the LDS-DMA kernel runs whole k-loops only)
-  if (blocks > (long long)(kWsReserved / sizeof(int)) || !ws) S = 1;   // one arrival counter per tile
-  while (S > 1 && (long long)S * d.out_elems * 4 >= 0xFF000000LL) --S;  // slabs addressed with 32-bit byte offsets
-  d.splitk = S;
-  d.kt_per_split = (max_nkt + S - 1) / S;
-  if (d.kt_per_split < 1) d.kt_per_split = 1;
-  d.ntile_m = tiles;
-  d.ntile_n = ntile_n;
-  // Tail split.  A grid of 1-4 tiles per CU is resident all at once and lasts as long as the fullest CU: 576 tiles on
-  // 256 CUs cost 3 tile-times although the chip only has 2.25 to do.  The first floor(blocks / CUs) * CUs tiles run
-  // whole; the R left-over tiles are cut Sr ways along K (Sr * R <= CUs: one piece per CU), folded in the kernel
-  // like any split-K tile.  Only those R tiles pay slab traffic.  (uniform-tap loops only; fp32 and fp16 alike)
-  d.tail_split = 1;
-  d.tail_u0 = 0;
-  if (S == 1 && uni && ws && blocks > kNumCU && blocks < 4 * kNumCU && blocks <= (long long)(kWsReserved / sizeof(int))
-      && tuning().splitk == 0 && !dma) {
-    const int R = (int)(blocks % kNumCU);
-    int Sr = 1;
-    while (R > 0 && Sr * 2 <= 8 && Sr * 2 * R <= kNumCU && max_nkt / (Sr * 2) >= 4) Sr *= 2;
-    if (Sr > 1 && (size_t)Sr * d.out_elems * sizeof(float) <= ws_payload_bytes(ws_bytes) &&
-        (long long)Sr * d.out_elems * 4 < 0xFF000000LL) {
-      d.tail_split = Sr;
-      d.tail_u0 = (int)(blocks - R);
-    }
-  }
-  // cost-ordered dispatch (AliEpilogue.tile_order / ali_conv_tile_order): only launches whose blocks each own a whole
-  // k-loop or a tail-split share of one
-  d.order = nullptr;
-  if (d.ep.tile_order && uni && S == 1 && d.ep.tile_order_n == tiles && tuning().no_order == 0)
-    d.order = reinterpret_cast<const int*>(d.ep.tile_order);
-  d.lin1d = (d.tail_split > 1 || d.order) ? 1 : 0;
-  if (d.tail_split == 1) d.tail_u0 = (int)blocks;
-  // XCD-contiguous tile order for deep grids of (image, pixel)-ordered rows (see the kernel's decoding)
-  d.xcd_chunk = 0;
-  bool img_major = d.nphase >= 1;
-  for (int i = 0; i < d.nphase; ++i) img_major = img_major && !d.ph[i].pixmajor;
-  if (!d.lin1d && S == 1 && !job && img_major && blocks >= 8LL * kNumCU && blocks < (1LL << 30) && tuning().no_xcd == 0) {
-    d.xcd_chunk = (int)((blocks + 7) / 8);
-    d.lin1d = 1;
-  }
-  d.no_clean = tuning().no_clean;
-  // uniform tiles (the kernel's uniform prologue): fp32 uniform-tap launches with a phase whose rows are ordered
-  // (pixel, image) and whose tiles hold one pixel position each.  Only such launches run the UNI kernel instances.
-  bool any_uni = false;
-  for (int i = 0; i < d.nphase; ++i) any_uni = any_uni || (d.ph[i].pixmajor && d.B % tc.bm == 0);
-  any_uni = any_uni && uni && !d.f16 && tuning().no_uniform == 0;
-  d.no_uniform = any_uni ? 0 : 1;
-  d.ctr = reinterpret_cast<int*>(ws);
-  d.ws = reinterpret_cast<float*>(ws_payload(ws));
-  dim3 grid(tiles, ntile_n, S), block(256);
-  if (d.lin1d) grid = dim3(d.tail_u0 + (int)(blocks - d.tail_u0) * d.tail_split, 1, 1);
-  if (d.xcd_chunk) grid = dim3(8 * d.xcd_chunk, 1, 1);
-  if (tiles == 0 || d.out_elems == 0) return ALI_OK;
-  const bool f16 = d.f16 && uni;
-  const bool op16 = f16 && d.in16 && d.w16 && (d.Cin % 64) == 0;
-  if (!d.f16) d.out16 = nullptr;    // twins are left by mfma_f16 launches only -- also by those of them that keep fp32
-                                    // arithmetic (first layers): their consumers then read fp16 operands from memory
-  if (job && uni && !f16 && ((tc.bm == 64 && tc.bn == 64) || (tc.bm == 128 && tc.bn == 32))) {
-    GJobRec r;
-    memset(&r, 0, sizeof(r));
-    r.state = 1;
-    r.variant = tc.bm == 64 ? 0 : 1;
-    r.gx = (int)grid.x; r.gy = (int)grid.y; r.gz = (int)grid.z;
-    r.cost = (max_nkt + S - 1) / S;
-    r.d = d;
-    memcpy(job, &r, sizeof(r));
-    return ALI_OK;
-  }
-#define LAUNCH(BM_, BN_, WMM, WNN)                                                                    \
-  do {                                                                                                  \
-    if (op16) hipLaunchKernelGGL((gconv_kernel<BM_, BN_, WMM, WNN, 2, 2>), grid, block, 0, stream, d);  \
-    else if (f16) hipLaunchKernelGGL((gconv_kernel<BM_, BN_, WMM, WNN, 2, 1>), grid, block, 0, stream, d); \
-    else if (any_uni) hipLaunchKernelGGL((gconv_kernel<BM_, BN_, WMM, WNN, 2, 0, true>), grid, block, 0, stream, d); \
-    else if (uni) hipLaunchKernelGGL((gconv_kernel<BM_, BN_, WMM, WNN, 2>), grid, block, 0, stream, d); \
-    else if (pow2) hipLaunchKernelGGL((gconv_kernel<BM_, BN_, WMM, WNN, 3>), grid, block, 0, stream, d);  \
-    else if (vec) hipLaunchKernelGGL((gconv_kernel<BM_, BN_, WMM, WNN, 1>), grid, block, 0, stream, d); \
-    else hipLaunchKernelGGL((gconv_kernel<BM_, BN_, WMM, WNN, 0>), grid, block, 0, stream, d);          \
-  } while (0)
-  if (dma) {
-    if (tc.bn != 256 || !op16) { set_error("gconv: no kernel for this tile"); return ALI_ERR_BAD_ARG; }
-    block = dim3(512);
-    hipLaunchKernelGGL((gconv_kernel512<256, 256, 2, 4, 2, 3>), grid, block, 0, stream, d);
-    return check_launch("gconv_kernel512");
-  }
-  if (tc.bm > 128 || tc.bn > 128) { set_error("gconv: no kernel for this tile"); return ALI_ERR_BAD_ARG; }
-  else if (tc.bm == 128 && tc.bn == 128) LAUNCH(128, 128, 2, 2);
-  else if (tc.bm == 128 && tc.bn == 64) LAUNCH(128, 64, 2, 2);
-  else if (tc.bm == 128 && tc.bn == 32) LAUNCH(128, 32, 4, 1);
-  else if (tc.bm == 64 && tc.bn == 128) LAUNCH(64, 128, 2, 2);
-  else LAUNCH(64, 64, 2, 2);
-#undef LAUNCH
-  return check_launch("gconv_kernel");
+}
+static GInstance gconv_instance(int bm, int bn, int mode, int f16, bool uni) {
+  if (f16 == 3) return {gconv_kernel512<256, 256, 2, 4, 2, 3>, nullptr};
+  if (bm == 128 && bn == 128) return tile_instance<128, 128, 2, 2>(mode, f16, uni);
+  if (bm == 128 && bn == 64) return tile_instance<128, 64, 2, 2>(mode, f16, uni);
+  if (bm == 128 && bn == 32) return tile_instance<128, 32, 4, 1>(mode, f16, uni);
+  if (bm == 64 && bn == 128) return tile_instance<64, 128, 2, 2>(mode, f16, uni);
+  return tile_instance<64, 64, 2, 2>(mode, f16, uni);
 }
 
 static bool geom_ok(const AliConvGeom* g) {
@@ -1571,9 +1410,8 @@ static bool geom_ok(const AliConvGeom* g) {
   return true;
 }
 
-static void fill_epilogue(GDesc& d, const AliEpilogue* ep) {
-  if (ep) d.ep = *ep;
-  else memset(&d.ep, 0, sizeof(d.ep));
+static void fill_epilogue(GDesc& d, const AliEpilogue& ep) {
+  d.ep = ep;
   d.f16 = d.ep.mfma_f16 != 0;
   d.in16 = reinterpret_cast<const _Float16*>(d.ep.in16);
   d.w16 = reinterpret_cast<const _Float16*>(d.ep.w16);
@@ -1951,46 +1789,312 @@ static bool setup_bwd_data(const AliConvGeom* g, GDesc& d) {
   return true;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// The planner: every launch rule of ali_conv_fwd (which = 0) / ali_conv_bwd_data (1), once.  Pure host code: no HIP
+// call, no operand dereferenced (the epilogue's pointers are compared with null only).  Fills the GDesc fields the host
+// owns -- all but in / w / out / ws / ctr -- and the plan, in this order: route; gather loop and
+// arithmetic; phases; tile and row order; epilogue and size checks; split along K; tail split; dispatch order; XCD
+// chunks; uniform tiles; grid; job variant; kernel instance.
+// query: the plan for a caller that builds per-tile tables before it has operands (ali_conv_mtiles,
+// ali_conv_tile_order).  Such a caller passes no fp16 twins -- so the 256 x 256 tile is never planned -- and an ample
+// workspace; the flag adds: the GEMM grid even where the row-walking first-layer kernel (no M-tiles, no tables) would
+// run, blocks that own whole k-loops or tail-split shares of one (the only launches that follow a dispatch order: no
+// grid-wide split, forced or not), and no operand sizes to check.
+static int plan_conv(const AliConvGeom* g, int which, const AliEpilogue& ep, size_t ws_bytes, bool has_ws, bool as_job,
+                     bool query, GDesc& d, GPlan& p) {
+  const char* fn = which == 0 ? "ali_conv_fwd" : "ali_conv_bwd_data";
+  memset(&d, 0, sizeof(d));
+  memset(&p, 0, sizeof(p));
+  p.job_variant = -1;
+  if (!geom_ok(g)) { set_error("%s: bad argument", fn); return ALI_ERR_BAD_ARG; }
+  const bool want16 = ep.mfma_f16 != 0;
+  // --- route
+  if (which == 0 && conv_first_ok(g, nullptr, want16)) {
+    // (the slot count ali_conv_mtiles reports depends on the geometry alone: an epilogue the per-image kernel cannot
+    // serve is an error here rather than a silent change of the partial layout)
+    if (conv_first_ok(g, &ep, false)) {
+      if (ep.bn_part && ep.bn_slots > 0 && ep.bn_slots != g->B) {
+        set_error("ali_conv_fwd: bn_part was sized for %d slots, the per-image kernel leaves %d", ep.bn_slots, g->B);
+        return ALI_ERR_BAD_ARG;
+      }
+      p.route = kRouteFirst; p.threads = 256;
+      p.ntile_m = g->B; p.tile_rows = g->P * g->Q;           // one slot per image
+      p.grid_x = g->B; p.grid_y = p.grid_z = 1;
+      return ALI_OK;
+    }
+    if (ep.bn_part) { set_error("ali_conv_fwd: epilogue not supported for this first-layer geometry"); return ALI_ERR_BAD_ARG; }
+    // (no partials requested: the GEMM kernel serves the epilogue the per-image kernel cannot)
+  }
+  if (which == 0 && !query && conv_s2_first_ok(g, &ep)) {
+    p.route = kRouteS2First; p.threads = 256; p.f16 = want16 ? 1 : 0;
+    p.grid_x = (g->P + 3) / 4; p.grid_y = g->B; p.grid_z = 1;
+    return ALI_OK;
+  }
+  // --- gather loop and arithmetic of the GEMM kernel: the gathered channel count alone (ali_conv_uses_f16 reads p.f16
+  // whatever is rejected further down)
+  const int cin = which == 0 ? g->C : g->K;
+  const bool vec = (cin % 4) == 0, uni = vec && (cin % BK) == 0;
+  p.route = kRouteGemm; p.threads = 256;
+  p.f16 = (want16 && uni) ? 1 : 0;             // (2: twins read, 3: LDS-DMA kernel -- below, with the tile)
+  // --- phases
+  fill_epilogue(d, ep);
+  if (which == 0) setup_fwd(g, d);
+  else if (!setup_bwd_data(g, d)) return ALI_ERR_BAD_ARG;
+  const bool dense_k = which == 0 && g->pad == 0;
+  const int forced_split = query ? 0 : tuning().splitk;
+  long long Mtot = 0;
+  int max_taps = 0;
+  for (int i = 0; i < d.nphase; ++i) {
+    Mtot += d.ph[i].M;
+    if (d.ph[i].nr * d.ph[i].ns > max_taps) max_taps = d.ph[i].nr * d.ph[i].ns;
+    if (d.ph[i].M >= (1 << 24)) { set_error("gconv: more than 2^24 rows in one phase"); return ALI_ERR_BAD_ARG; }
+  }
+  const int max_nkt = (max_taps * d.Cin + BK - 1) / BK;
+  const bool pow2 = vec && (d.Cin == 4 || d.Cin == 8 || d.Cin == 16) && max_taps <= kMaxTaps;
+  p.mode = uni ? 2 : pow2 ? 3 : vec ? 1 : 0;
+  // --- tile, row order and M-tile count (everything the grid's x extent depends on)
+  // dma_ok: the launch may use the 256 x 256 LDS-DMA fp16 kernel: both fp16 twins, no fused BatchNorm, dense rows
+  const bool dma_ok = d.f16 && uni && d.in16 && d.w16 && (d.Cin % 64) == 0 && !ep.bn_part && ep.in_ld <= 0 &&
+                      tuning().no_dma16 == 0 && forced_split == 0;
+  const long long Mpick = Mtot * (tuning().tile_m_scale > 0 ? tuning().tile_m_scale : 1);
+  TileCfg tc = pick_tile(Mpick, d.Cout, p.f16 != 0, d.Cin);
+  if (tuning().bm > 0 && tuning().bn > 0) { tc.bm = tuning().bm; tc.bn = tuning().bn; }
+  if (tc.bm > 128 && !dma_ok) tc = pick_tile(Mpick, d.Cout, p.f16 != 0, d.Cin);      // (a forced 256 x 256 applies to DMA launches only)
+  if (dma_ok && tuning().bm == 0) {
+    // 256 x 256 as soon as it fills the chip once (one block per CU).  Stand-alone (scratch/ub/dma_gemm.hip, a 1-D
+    // "convolution" with the layers' reuse): 881-1008 TF/s against 700-840 of the 128 x 128 register-staged loop.  Inside
+    // the ESRF iteration the forward convolutions 128 -> 256 ... 512 -> 1024 gain 5-8 % (697 -> 732, 781 -> 842, 783 ->
+    // 849 TF/s); launches in sub-pixel phases (data gradients: 786 -> 591) and tiny pixel-major maps (7 x 7: 911 -> 810)
+    // LOSE -- a 256-row tile spans two pixel positions, so fewer padding taps are skipped tile-wide, and there is no
+    // cost-ordered dispatch table for this tile: they keep the 128 x 128 loop.
+    const long long b256 = ((Mpick + 255) / 256) * (long long)((d.Cout + 255) / 256);
+    const bool plain = d.nphase == 1 && (long long)d.ph[0].Hq * d.ph[0].Wq >= 200;
+    if (plain && d.Cout >= 256 && b256 >= (kNumCU * 3) / 4) { tc.bm = 256; tc.bn = 256; }
+  }
+  if (!vec && tc.bn == 128) tc.bn = 64;
+  int tiles = 0;
+  for (int i = 0; i < d.nphase; ++i) {
+    // small maps with a large batch: order rows (pixel, image) so that every M-tile sees one pixel position
+    // and the taps falling outside the input (padding, 1x1 -> 3x3 transposed convs) are skipped tile-wide
+    d.ph[i].pixmajor = (d.ph[i].Hq * d.ph[i].Wq <= 1024 && d.B >= 64) ? 1 : 0;
+    d.ph[i].tile0 = tiles;
+    tiles += (d.ph[i].M + tc.bm - 1) / tc.bm;
+  }
+  const bool dma = tc.bm == 256;
+  const int ntile_n = (d.Cout + tc.bn - 1) / tc.bn;
+  const long long blocks = (long long)tiles * ntile_n;
+  p.bm = tc.bm; p.bn = tc.bn;
+  p.ntile_m = d.ntile_m = tiles;
+  p.ntile_n = d.ntile_n = ntile_n;
+  p.tile_rows = tc.bm; p.pixel_major = d.ph[0].pixmajor;
+  // --- epilogue and size checks
+  if (ep.bn_part) {
+    bool ok = (ep.bn_mode == 1 || ep.bn_mode == 2) && !ep.dact_y;
+    if (ep.bn_mode == 2) ok = ok && !ep.mask && ep.bn_x && ep.bn_mean && ep.bn_invstd && ep.bn_groups <= 1;
+    if (ep.bn_mode == 1 && ep.bn_groups > 1) {
+      ok = ok && d.nphase == 1 && d.B % ep.bn_groups == 0;
+      const long long rows_g = (long long)(d.B / ep.bn_groups) * (d.ph[0].pixmajor ? 1 : d.ph[0].Hq * d.ph[0].Wq);
+      ok = ok && rows_g % tc.bm == 0 && (!d.ph[0].pixmajor || d.B % tc.bm == 0);
+    }
+    if (!ok) { set_error("gconv: bad fused BatchNorm epilogue (see AliEpilogue / ali_conv_mtiles)"); return ALI_ERR_BAD_ARG; }
+    if (ep.bn_slots > 0 && ep.bn_slots != tiles) {
+      set_error("gconv: bn_part was sized for %d slots, this launch has %d M-tiles (stale ali_conv_mtiles result?)", ep.bn_slots, tiles);
+      return ALI_ERR_BAD_ARG;
+    }
+  }
+  d.ldi = d.Cin;
+  if (ep.in_ld > 0 || ep.out_ld > 0) {     // operands that are column ranges of wider row-major buffers
+    if ((ep.in_ld > 0 && (ep.in_ld < d.Cin || (vec && ep.in_ld % 4))) ||
+        (ep.out_ld > 0 && (ep.out_ld < d.Cout || ep.bn_part))) {
+      set_error("gconv: bad in_ld / out_ld (>= the channel count, in_ld % 4 == 0 for vector gathers, no out_ld with fused BatchNorm)");
+      return ALI_ERR_BAD_ARG;
+    }
+    if (ep.in_ld > 0) d.ldi = ep.in_ld;
+    if (ep.out_ld > 0) d.ldo = ep.out_ld;
+  }
+  d.out_elems = (long long)d.B * d.Hout * d.Wout * d.ldo;
+  const long long in_elems = ((long long)d.B * d.Hin * d.Win - 1) * d.ldi + d.Cin;
+  const long long w_elems = (long long)d.Cout * d.ldw;
+  if (!query && (d.out_elems >= (1LL << 31) || in_elems >= (1LL << 30) || w_elems >= (1LL << 29))) {
+    set_error("gconv: tensor too large for 32-bit byte offsets");
+    return ALI_ERR_BAD_ARG;
+  }
+  d.in_bytes = (unsigned)(in_elems * 4);
+  d.w_bytes = (unsigned)(w_elems * 4);
+  // --- split-K when the grid cannot give every CU two blocks.  All blocks of such a grid are resident at once, so the
+  // launch lasts as long as the fullest CU: n = ceil(blocks*S / CUs) blocks of nkt/S k-tiles each, a little slower
+  // per block when the CU holds fewer than 4, plus about half a k-tile of slab traffic per slab
+  // (scratch/sweep_splitk.py).  Data-gradient launches skip dead taps tile by tile, so their k-depth is not known
+  // here: they keep the plain "two blocks per CU" rule.
+  int S = 1;
+  if (!query && blocks < 2 * kNumCU && max_nkt >= 8 && dense_k) {
+    static const double eff[5] = {1.0, 0.82, 0.96, 0.99, 1.0};
+    double best = 1e30;
+    for (int sc = 1; sc <= 8 && max_nkt / sc >= 4; ++sc) {
+      if (sc > 1 && (size_t)sc * d.out_elems * sizeof(float) > ws_payload_bytes(ws_bytes)) break;
+      const long long n = (blocks * sc + kNumCU - 1) / kNumCU;
+      const double cost = (double)n / sc / eff[n < 4 ? n : 4] * max_nkt + (sc > 1 ? 0.5 * sc : 0.0);
+      if (cost < 0.97 * best) { best = cost; S = sc; }
+    }
+  } else if (!query && blocks < 2 * kNumCU && max_nkt >= 8) {
+    S = (int)((2 * kNumCU + blocks - 1) / blocks);
+    if (S > max_nkt / 4) S = max_nkt / 4;
+    if (S > 32) S = 32;
+    while (S > 1 && (size_t)S * d.out_elems * sizeof(float) > ws_payload_bytes(ws_bytes)) --S;
+    if (S < 1) S = 1;
+  }
+  if (forced_split > 0 && (size_t)forced_split * d.out_elems * sizeof(float) <= ws_payload_bytes(ws_bytes)) S = forced_split;
+  if (dma) S = 1;                      // (the LDS-DMA kernel runs whole k-loops only: no slab code in its register budget)
+  if (blocks > (long long)(kWsReserved / sizeof(int)) || !has_ws) S = 1;   // one arrival counter per tile
+  while (S > 1 && (long long)S * d.out_elems * 4 >= 0xFF000000LL) --S;  // slabs addressed with 32-bit byte offsets
+  p.splitk = d.splitk = S;
+  d.kt_per_split = (max_nkt + S - 1) / S;
+  if (d.kt_per_split < 1) d.kt_per_split = 1;
+  p.kt_per_split = d.kt_per_split;
+  // --- tail split.  A grid of 1-4 tiles per CU is resident all at once and lasts as long as the fullest CU: 576 tiles on
+  // 256 CUs cost 3 tile-times although the chip only has 2.25 to do.  The first floor(blocks / CUs) * CUs tiles run
+  // whole; the R left-over tiles are cut Sr ways along K (Sr * R <= CUs: one piece per CU), folded in the kernel
+  // like any split-K tile.  Only those R tiles pay slab traffic.  (uniform-tap loops only; fp32 and fp16 alike)
+  d.tail_split = 1;
+  d.tail_u0 = 0;
+  if (S == 1 && uni && has_ws && blocks > kNumCU && blocks < 4 * kNumCU && blocks <= (long long)(kWsReserved / sizeof(int))
+      && forced_split == 0 && !dma) {
+    const int R = (int)(blocks % kNumCU);
+    int Sr = 1;
+    while (R > 0 && Sr * 2 <= 8 && Sr * 2 * R <= kNumCU && max_nkt / (Sr * 2) >= 4) Sr *= 2;
+    if (Sr > 1 && (size_t)Sr * d.out_elems * sizeof(float) <= ws_payload_bytes(ws_bytes) &&
+        (long long)Sr * d.out_elems * 4 < 0xFF000000LL) {
+      d.tail_split = Sr;
+      d.tail_u0 = (int)(blocks - R);
+    }
+  }
+  // --- cost-ordered dispatch (AliEpilogue.tile_order / ali_conv_tile_order): only launches whose blocks each own a
+  // whole k-loop or a tail-split share of one
+  d.order = nullptr;
+  if (ep.tile_order && uni && S == 1 && ep.tile_order_n == tiles && tuning().no_order == 0)
+    d.order = reinterpret_cast<const int*>(ep.tile_order);
+  p.ordered = d.order ? 1 : 0;
+  d.lin1d = (d.tail_split > 1 || d.order) ? 1 : 0;
+  if (d.tail_split == 1) d.tail_u0 = (int)blocks;
+  // --- XCD-contiguous tile order for deep grids of (image, pixel)-ordered rows (see the kernel's decoding)
+  d.xcd_chunk = 0;
+  bool img_major = d.nphase >= 1;
+  for (int i = 0; i < d.nphase; ++i) img_major = img_major && !d.ph[i].pixmajor;
+  if (!d.lin1d && S == 1 && !as_job && img_major && blocks >= 8LL * kNumCU && blocks < (1LL << 30) && tuning().no_xcd == 0) {
+    d.xcd_chunk = (int)((blocks + 7) / 8);
+    d.lin1d = 1;
+  }
+  p.tail_split = d.tail_split; p.tail_u0 = d.tail_u0; p.lin1d = d.lin1d; p.xcd_chunk = d.xcd_chunk;
+  d.no_clean = tuning().no_clean;
+  // --- uniform tiles (the kernel's uniform prologue): fp32 uniform-tap launches with a phase whose rows are ordered
+  // (pixel, image) and whose tiles hold one pixel position each.  Only such launches run the UNI kernel instances.
+  bool any_uni = false;
+  for (int i = 0; i < d.nphase; ++i) any_uni = any_uni || (d.ph[i].pixmajor && d.B % tc.bm == 0);
+  any_uni = any_uni && uni && !d.f16 && tuning().no_uniform == 0;
+  d.no_uniform = any_uni ? 0 : 1;
+  p.uni = any_uni ? 1 : 0;
+  // --- grid
+  p.grid_x = tiles; p.grid_y = ntile_n; p.grid_z = S;
+  if (d.lin1d) { p.grid_x = d.tail_u0 + (int)(blocks - d.tail_u0) * d.tail_split; p.grid_y = p.grid_z = 1; }
+  if (d.xcd_chunk) p.grid_x = 8 * d.xcd_chunk;
+  p.empty = (tiles == 0 || d.out_elems == 0) ? 1 : 0;
+  if (p.empty || query) return ALI_OK;           // (a query asks about the grid, not about a kernel)
+  // --- kernel instance, or the record of a combined launch
+  const bool op16 = p.f16 != 0 && d.in16 && d.w16 && (d.Cin % 64) == 0;
+  if (op16) p.f16 = dma ? 3 : 2;
+  if (dma) p.threads = 512;
+  if (!d.f16) d.out16 = nullptr;    // twins are left by mfma_f16 launches only -- also by those of them that keep fp32
+                                    // arithmetic (first layers): their consumers then read fp16 operands from memory
+  // (fp16 launches are never recorded as jobs of a combined launch)
+  if (as_job && uni && p.f16 == 0 && ((tc.bm == 64 && tc.bn == 64) || (tc.bm == 128 && tc.bn == 32))) {
+    p.job_variant = tc.bm == 64 ? 0 : 1;
+    return ALI_OK;
+  }
+  if (dma ? (tc.bn != 256 || !op16) : (tc.bm > 128 || tc.bn > 128)) { set_error("gconv: no kernel for this tile"); return ALI_ERR_BAD_ARG; }
+  return ALI_OK;
+}
+
+// The executor: records the job or launches the plan's kernel instance on the plan's grid.
+static int run_gemm(const GDesc& d, const GPlan& p, hipStream_t stream, AliGemmJob* job) {
+  if (p.empty) return ALI_OK;
+  if (p.job_variant >= 0) {
+    GJobRec r;
+    memset(&r, 0, sizeof(r));
+    r.state = 1;
+    r.variant = p.job_variant;
+    r.gx = p.grid_x; r.gy = p.grid_y; r.gz = p.grid_z;
+    r.cost = p.kt_per_split;
+    r.d = d;
+    memcpy(job, &r, sizeof(r));
+    return ALI_OK;
+  }
+  hipLaunchKernelGGL(gconv_instance(p.bm, p.bn, p.mode, p.f16, p.uni != 0).one, dim3(p.grid_x, p.grid_y, p.grid_z),
+                     dim3(p.threads), 0, stream, d);
+  return check_launch(p.threads == 512 ? "gconv_kernel512" : "gconv_kernel");
+}
+
+static AliEpilogue epilogue_or_none(const AliEpilogue* ep) {
+  AliEpilogue e;
+  if (ep) e = *ep;
+  else memset(&e, 0, sizeof(e));
+  return e;
+}
+
+// a = x, out = y (which = 0) / a = dy, out = dx (1)
+static int conv_impl(int which, const AliConvGeom* g, const float* a, const float* w, float* out, const AliEpilogue* ep,
+                     void* ws, size_t ws_bytes, ali_stream_t stream, AliGemmJob* job) {
+  if (!a || !w || !out) { set_error("%s: bad argument", which == 0 ? "ali_conv_fwd" : "ali_conv_bwd_data"); return ALI_ERR_BAD_ARG; }
+  GDesc d;
+  GPlan p;
+  const int rc = plan_conv(g, which, epilogue_or_none(ep), ws_bytes, ws != nullptr, job != nullptr, false, d, p);
+  if (rc != ALI_OK) return rc;
+  if (p.route == kRouteFirst) return conv_first_launch(g, a, w, out, ep, (hipStream_t)stream);
+  if (p.route == kRouteS2First) return conv_s2_first_launch(g, a, w, out, ep, (hipStream_t)stream);
+  d.in = a; d.w = w; d.out = out;
+  d.ctr = reinterpret_cast<int*>(ws);
+  d.ws = reinterpret_cast<float*>(ws_payload(ws));
+  return run_gemm(d, p, (hipStream_t)stream, job);
+}
+
+extern "C" int32_t ali_conv_plan(const AliConvGeom* g, int32_t which, const AliEpilogue* ep, size_t ws_bytes,
+                                 int32_t has_ws, int32_t as_job, AliConvPlan* out) {
+  if (!out || (which != 0 && which != 1)) { set_error("ali_conv_plan: bad argument"); return ALI_ERR_BAD_ARG; }
+  memset(out, 0, sizeof(*out));
+  GDesc d;
+  GPlan p;
+  const int rc = plan_conv(g, which, epilogue_or_none(ep), ws_bytes, has_ws != 0, as_job != 0, false, d, p);
+  if (rc == ALI_OK) memcpy(out, &p, sizeof(p));
+  return rc;
+}
+
+// The plan a table-building caller asks about (plan_conv: query): no operands, no twins, an ample workspace.
+static bool query_plan(const AliConvGeom* g, int32_t which, int32_t mfma_f16, GDesc& d, GPlan& p) {
+  if (which != 0 && which != 1) return false;
+  AliEpilogue ep = epilogue_or_none(nullptr);
+  ep.mfma_f16 = mfma_f16;
+  return plan_conv(g, which, ep, SIZE_MAX, true, false, true, d, p) == ALI_OK;
+}
+
 extern "C" int32_t ali_conv_mtiles(const AliConvGeom* g, int32_t which, int32_t mfma_f16, int32_t* tile_rows,
                                    int32_t* pixel_major) {
-  if (!geom_ok(g) || (which != 0 && which != 1)) return 0;
-  if (which == 0 && conv_first_ok(g, nullptr, mfma_f16 != 0)) {      // per-image kernel: one slot per image
-    if (tile_rows) *tile_rows = g->P * g->Q;
-    if (pixel_major) *pixel_major = 0;
-    return g->B;
-  }
   GDesc d;
-  memset(&d, 0, sizeof(d));
-  d.f16 = mfma_f16 != 0;
-  bool vec;
-  if (which == 0) { setup_fwd(g, d); vec = (g->C % 4) == 0; }
-  else { if (!setup_bwd_data(g, d)) return 0; vec = (g->K % 4) == 0; }
-  TileCfg tc;
-  int max_taps = 0;
-  const int tiles = plan_tiles(d, vec, tc, max_taps);
-  if (tiles < 0) return 0;
-  if (tile_rows) *tile_rows = tc.bm;
-  if (pixel_major) *pixel_major = d.ph[0].pixmajor;
-  return tiles;
+  GPlan p;
+  if (!query_plan(g, which, mfma_f16, d, p)) return 0;
+  if (tile_rows) *tile_rows = p.tile_rows;
+  if (pixel_major) *pixel_major = p.pixel_major;
+  return p.ntile_m;
 }
 
 extern "C" int32_t ali_conv_tile_order(const AliConvGeom* g, int32_t which, int32_t mfma_f16, int32_t* order,
                                        int32_t cap) {
-  if (!geom_ok(g) || (which != 0 && which != 1) || !order) return 0;
-  if (which == 0 && conv_first_ok(g, nullptr, mfma_f16 != 0)) return 0;
   GDesc d;
-  memset(&d, 0, sizeof(d));
-  d.f16 = mfma_f16 != 0;
-  bool vec;
-  if (which == 0) { setup_fwd(g, d); vec = (g->C % 4) == 0; }
-  else { if (!setup_bwd_data(g, d)) return 0; vec = (g->K % 4) == 0; }
-  if (!vec || (d.Cin % BK) != 0) return 0;          // only the uniform-tap loop skips dead taps tile-wide
-  TileCfg tc;
-  int max_taps = 0;
-  const int tiles = plan_tiles(d, vec, tc, max_taps);
+  GPlan p;
+  if (!order || !query_plan(g, which, mfma_f16, d, p)) return 0;
+  if (p.route != kRouteGemm || p.mode != 2) return 0;          // only the uniform-tap loop skips dead taps tile-wide
+  const int tiles = p.ntile_m, nt = p.ntile_n;
   if (tiles <= 0 || tiles > cap) return 0;
   std::vector<int> cost;
-  if (!tile_costs(d, tc.bm, cost) || (int)cost.size() != tiles) return 0;
+  if (!tile_costs(d, p.bm, cost) || (int)cost.size() != tiles) return 0;
   if (*std::max_element(cost.begin(), cost.end()) == *std::min_element(cost.begin(), cost.end())) return 0;
   std::vector<int> idx(tiles);
   for (int i = 0; i < tiles; ++i) idx[i] = i;
@@ -2001,16 +2105,8 @@ extern "C" int32_t ali_conv_tile_order(const AliConvGeom* g, int32_t which, int3
   // longest-processing-time-first onto the CUs -- each tile, heaviest first, goes to the free rank position whose
   // CUs carry the least so far.  Tiles beyond the resident window follow in sorted order (they are dispatched as
   // blocks retire).  Grids whose left-over tiles are split along K keep the plain order (their last slots are special).
-  const int nt = (d.Cout + tc.bn - 1) / tc.bn;
-  const long long blocks = (long long)tiles * nt;
-  bool tail_split = false;
-  if (blocks > kNumCU && blocks < 4 * kNumCU) {
-    const int R = (int)(blocks % kNumCU);
-    const int max_nkt = (max_taps * d.Cin + BK - 1) / BK;
-    tail_split = R > 0 && 2 * R <= kNumCU && max_nkt / 2 >= 4;
-  }
   const int W = std::min(tiles, 4 * kNumCU / nt);
-  if (tail_split || W < 2) {
+  if (p.tail_split > 1 || W < 2) {
     for (int i = 0; i < tiles; ++i) order[i] = idx[i];
     return tiles;
   }
@@ -2022,11 +2118,11 @@ extern "C" int32_t ali_conv_tile_order(const AliConvGeom* g, int32_t which, int3
     const int tile = idx[i];
     int best = -1;
     long long best_load = 0;
-    for (int p = 0; p < W; ++p) {
-      if (used[p]) continue;
+    for (int q = 0; q < W; ++q) {
+      if (used[q]) continue;
       long long l = 0;
-      for (int by = 0; by < nt; ++by) l = std::max(l, load[slot_of(p, by) % kNumCU]);
-      if (best < 0 || l < best_load) { best = p; best_load = l; }
+      for (int by = 0; by < nt; ++by) l = std::max(l, load[slot_of(q, by) % kNumCU]);
+      if (best < 0 || l < best_load) { best = q; best_load = l; }
     }
     used[best] = 1;
     order[best] = tile;
@@ -2037,72 +2133,44 @@ extern "C" int32_t ali_conv_tile_order(const AliConvGeom* g, int32_t which, int3
 }
 
 extern "C" int32_t ali_conv_writes_out16(const AliConvGeom* g, int32_t which) {
-  (void)which;
-  return geom_ok(g) ? 1 : 0;       // every mfma_f16 launch of the GEMM kernel does, whatever arithmetic its loop uses
+  GDesc d;
+  GPlan p;
+  AliEpilogue ep = epilogue_or_none(nullptr);
+  ep.mfma_f16 = 1;
+  plan_conv(g, which, ep, 0, false, false, false, d, p);
+  // every kernel but the per-image first conv leaves the twin, whatever arithmetic its loop uses -- and that one never
+  // serves an mfma_f16 launch (the route is decided before anything else can be rejected)
+  return (geom_ok(g) && p.route != kRouteFirst) ? 1 : 0;
 }
 
 extern "C" int32_t ali_conv_uses_f16(const AliConvGeom* g, int32_t which, const AliEpilogue* ep) {
   if (!geom_ok(g) || !ep || !ep->mfma_f16) return 0;
-  if (which == 0 && conv_s2_first_ok(g, ep)) return 1;          // row-walking first-layer kernel, fp16 variant
-  return ((which == 0 ? g->C : g->K) % 32) == 0 ? 1 : 0;        // uniform-tap GEMM loop
-}
-
-static int conv_fwd_impl(const AliConvGeom* g, const float* x, const float* w, float* y, const AliEpilogue* ep,
-                         void* ws, size_t ws_bytes, ali_stream_t stream, AliGemmJob* job) {
-  if (!geom_ok(g) || !x || !w || !y) { set_error("ali_conv_fwd: bad argument"); return ALI_ERR_BAD_ARG; }
-  if (conv_first_ok(g, nullptr, ep && ep->mfma_f16)) {
-    // (the slot count ali_conv_mtiles reports depends on the geometry alone: an epilogue the per-image kernel cannot
-    // serve is an error here rather than a silent change of the partial layout)
-    if (conv_first_ok(g, ep, false)) {
-      if (ep && ep->bn_part && ep->bn_slots > 0 && ep->bn_slots != g->B) {
-        set_error("ali_conv_fwd: bn_part was sized for %d slots, the per-image kernel leaves %d", ep->bn_slots, g->B);
-        return ALI_ERR_BAD_ARG;
-      }
-      return conv_first_launch(g, x, w, y, ep, (hipStream_t)stream);
-    }
-    if (ep && ep->bn_part) { set_error("ali_conv_fwd: epilogue not supported for this first-layer geometry"); return ALI_ERR_BAD_ARG; }
-    // (no partials requested: the GEMM kernel serves the epilogue the per-image kernel cannot)
-  }
-  if (conv_s2_first_ok(g, ep)) return conv_s2_first_launch(g, x, w, y, ep, (hipStream_t)stream);
   GDesc d;
-  memset(&d, 0, sizeof(d));
-  d.in = x; d.w = w; d.out = y;
-  fill_epilogue(d, ep);
-  setup_fwd(g, d);
-  return finalize_and_launch(d, ws, ws_bytes, (hipStream_t)stream, (g->C % 4) == 0, g->pad == 0, job);
-}
-
-static int conv_bwd_data_impl(const AliConvGeom* g, const float* dy, const float* w, float* dx, const AliEpilogue* ep,
-                              void* ws, size_t ws_bytes, ali_stream_t stream, AliGemmJob* job) {
-  if (!geom_ok(g) || !dy || !w || !dx) { set_error("ali_conv_bwd_data: bad argument"); return ALI_ERR_BAD_ARG; }
-  GDesc d;
-  memset(&d, 0, sizeof(d));
-  d.in = dy; d.w = w; d.out = dx;
-  fill_epilogue(d, ep);
-  if (!setup_bwd_data(g, d)) return ALI_ERR_BAD_ARG;
-  return finalize_and_launch(d, ws, ws_bytes, (hipStream_t)stream, (g->K % 4) == 0, false, job);
+  GPlan p;
+  plan_conv(g, which, *ep, 0, false, false, false, d, p);
+  return p.f16 != 0 ? 1 : 0;      // route and arithmetic are decided first: the answer stands whatever is rejected later
 }
 
 extern "C" int ali_conv_fwd(const AliConvGeom* g, const float* x, const float* w, float* y, const AliEpilogue* ep,
                             void* ws, size_t ws_bytes, ali_stream_t stream) {
-  return conv_fwd_impl(g, x, w, y, ep, ws, ws_bytes, stream, nullptr);
+  return conv_impl(0, g, x, w, y, ep, ws, ws_bytes, stream, nullptr);
 }
 extern "C" int ali_conv_bwd_data(const AliConvGeom* g, const float* dy, const float* w, float* dx,
                                  const AliEpilogue* ep, void* ws, size_t ws_bytes, ali_stream_t stream) {
-  return conv_bwd_data_impl(g, dy, w, dx, ep, ws, ws_bytes, stream, nullptr);
+  return conv_impl(1, g, dy, w, dx, ep, ws, ws_bytes, stream, nullptr);
 }
 extern "C" int ali_conv_fwd_job(const AliConvGeom* g, const float* x, const float* w, float* y, const AliEpilogue* ep,
                                 void* ws, size_t ws_bytes, AliGemmJob* job, ali_stream_t stream) {
   if (!job) { set_error("ali_conv_fwd_job: job is NULL"); return ALI_ERR_BAD_ARG; }
   job->opaque[0] = 0;
-  return conv_fwd_impl(g, x, w, y, ep, ws, ws_bytes, stream, job);
+  return conv_impl(0, g, x, w, y, ep, ws, ws_bytes, stream, job);
 }
 extern "C" int ali_conv_bwd_data_job(const AliConvGeom* g, const float* dy, const float* w, float* dx,
                                      const AliEpilogue* ep, void* ws, size_t ws_bytes, AliGemmJob* job,
                                      ali_stream_t stream) {
   if (!job) { set_error("ali_conv_bwd_data_job: job is NULL"); return ALI_ERR_BAD_ARG; }
   job->opaque[0] = 0;
-  return conv_bwd_data_impl(g, dy, w, dx, ep, ws, ws_bytes, stream, job);
+  return conv_impl(1, g, dy, w, dx, ep, ws, ws_bytes, stream, job);
 }
 
 extern "C" int ali_gemm_launch_multi(int32_t n, const AliGemmJob* jobs, ali_stream_t stream_) {
@@ -2117,18 +2185,15 @@ extern "C" int ali_gemm_launch_multi(int32_t n, const AliGemmJob* jobs, ali_stre
   }
   for (int v = 0; v < 2; ++v) {
     std::vector<GJobRec>& all = rec[v];
+    const int bm = v == 0 ? 64 : 128, bn = v == 0 ? 64 : 32;       // GPlan.job_variant
     // longest blocks first (the dispatcher hands blocks out in order: the short ones fill the tail)
     std::stable_sort(all.begin(), all.end(), [](const GJobRec& a, const GJobRec& b) { return a.cost > b.cost; });
     for (size_t j0 = 0; j0 < all.size(); j0 += kGJobs) {
       const size_t cnt = std::min(all.size() - j0, (size_t)kGJobs);
       if (cnt == 1) {
         const GJobRec& r = all[j0];
-        dim3 grid(r.gx, r.gy, r.gz);
-        if (r.d.no_uniform == 0) {
-          if (v == 0) hipLaunchKernelGGL((gconv_kernel<64, 64, 2, 2, 2, 0, true>), grid, dim3(256), 0, stream, r.d);
-          else hipLaunchKernelGGL((gconv_kernel<128, 32, 4, 1, 2, 0, true>), grid, dim3(256), 0, stream, r.d);
-        } else if (v == 0) hipLaunchKernelGGL((gconv_kernel<64, 64, 2, 2, 2>), grid, dim3(256), 0, stream, r.d);
-        else hipLaunchKernelGGL((gconv_kernel<128, 32, 4, 1, 2>), grid, dim3(256), 0, stream, r.d);
+        hipLaunchKernelGGL(gconv_instance(bm, bn, 2, 0, r.d.no_uniform == 0).one, dim3(r.gx, r.gy, r.gz), dim3(256), 0,
+                           stream, r.d);
       } else {
         GJobs gj;
         memset(&gj, 0, sizeof(gj));
@@ -2144,11 +2209,7 @@ extern "C" int ali_gemm_launch_multi(int32_t n, const AliGemmJob* jobs, ali_stre
         }
         gj.n = (int)cnt;
         if (blocks > (1LL << 30)) { set_error("ali_gemm_launch_multi: grid too large"); return ALI_ERR_BAD_ARG; }
-        if (any_uni) {
-          if (v == 0) hipLaunchKernelGGL((gconv_multi_kernel<64, 64, 2, 2, 2, 0, true>), dim3((unsigned)blocks), dim3(256), 0, stream, gj);
-          else hipLaunchKernelGGL((gconv_multi_kernel<128, 32, 4, 1, 2, 0, true>), dim3((unsigned)blocks), dim3(256), 0, stream, gj);
-        } else if (v == 0) hipLaunchKernelGGL((gconv_multi_kernel<64, 64, 2, 2, 2>), dim3((unsigned)blocks), dim3(256), 0, stream, gj);
-        else hipLaunchKernelGGL((gconv_multi_kernel<128, 32, 4, 1, 2>), dim3((unsigned)blocks), dim3(256), 0, stream, gj);
+        hipLaunchKernelGGL(gconv_instance(bm, bn, 2, 0, any_uni).multi, dim3((unsigned)blocks), dim3(256), 0, stream, gj);
       }
       int rc = check_launch("gconv_multi_kernel");
       if (rc) return rc;

@@ -188,6 +188,32 @@ int32_t ali_conv_writes_out16(const AliConvGeom* g, int32_t which);
  * channel count % 32 == 0) and the first Conv2d of the spectrogram stacks (4 / 8 -> 64 channels, 5x5, stride 2,
  * audio_mnist.py:186); every other launch keeps fp32 arithmetic.  What a checker has to know to emulate the launch. */
 int32_t ali_conv_uses_f16(const AliConvGeom* g, int32_t which, const AliEpilogue* ep);
+/* The launch plan: everything the host decides for one ali_conv_fwd / ali_conv_bwd_data call (DESIGN.md 3.1.1 has the
+ * order of the decisions).  The four queries above are views of it. */
+typedef struct {
+  int32_t route;        /* 0: implicit-GEMM kernel; 1: per-image first conv (8 -> 32 channels, stride 1); 2: row-walking
+                           first conv (4 / 8 -> 64 channels, 5x5, stride 2).  Routes 1 and 2 fill route, threads, grid_*
+                           (1: also ntile_m = images = bn_part slots, tile_rows = P*Q; 2: f16), the rest is 0 */
+  int32_t bm, bn;       /* tile */
+  int32_t mode;         /* gather loop: 0 scalar, 1 16-byte gathers, 2 uniform-tap loop, 3 channel stride 4 / 8 / 16 */
+  int32_t f16;          /* 0 fp32 MFMA; fp16 MFMA: 1 operands converted in flight, 2 fp16 twins read, 3 LDS-DMA kernel */
+  int32_t uni;          /* uniform-tile kernel instance */
+  int32_t threads;      /* 256 or 512 */
+  int32_t ntile_m, ntile_n, tile_rows, pixel_major;   /* as ali_conv_mtiles, which plans without twins */
+  int32_t splitk, kt_per_split;                       /* grid-wide split along K, k-tiles per share */
+  int32_t tail_split, tail_u0;    /* the blocks from tail_u0 on are cut tail_split ways along K (1: none) */
+  int32_t lin1d, xcd_chunk;       /* 1-D grid (tail split, dispatch order, XCD chunks); blocks per XCD chunk or 0 */
+  int32_t ordered;                /* AliEpilogue.tile_order is followed */
+  int32_t grid_x, grid_y, grid_z;
+  int32_t job_variant;  /* -1: launched at once; 0 / 1: recorded in the AliGemmJob (64x64 / 128x32 multi-job kernel) */
+  int32_t empty;        /* nothing to launch */
+} AliConvPlan;
+/* Host side only (no GPU needed, nothing launched, no operand touched): what ali_conv_fwd (which = 0) /
+ * ali_conv_bwd_data (which = 1) would do for g and ep (NULL = no epilogue; pointers are only compared with NULL) given
+ * a workspace of ws_bytes (has_ws = 0: a NULL workspace) -- as_job != 0: what ali_conv_fwd_job / ali_conv_bwd_data_job
+ * would.  Returns the status and leaves the error text the launch would. */
+int32_t ali_conv_plan(const AliConvGeom* g, int32_t which, const AliEpilogue* ep, size_t ws_bytes, int32_t has_ws,
+                      int32_t as_job, AliConvPlan* out);
 int ali_conv_fwd(const AliConvGeom* g, const float* x, const float* w_kxc, float* y,
                  const AliEpilogue* ep, void* ws, size_t ws_bytes, ali_stream_t stream);
 int ali_conv_bwd_data(const AliConvGeom* g, const float* dy, const float* w_cxk, float* dx,

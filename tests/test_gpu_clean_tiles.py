@@ -158,7 +158,7 @@ def test_1x1_gemm_split_k_uneven_k_ranges(S):
 
 
 def test_1x1_gemm_tail_split_launch():
-    """M = 19200 (300 M-tiles of 64), K = 128 (2 n-tiles): 600 blocks of 64 x 64.  By finalize_and_launch's rules: 600
+    """M = 19200 (300 M-tiles of 64), K = 128 (2 n-tiles): 600 blocks of 64 x 64.  By plan_conv's rules: 600
     blocks is not below 2 x 256 CUs, so no split-K search runs and S = 1; 256 < 600 < 1024 with 600 % 256 = 88 left-over
     tiles, and Sr = 2 is the largest power of two with Sr * 88 <= 256 (one piece per CU), so it is a tail split: 512 whole
     tiles, then 88 tiles cut two ways along K.  C = 288 = 9 k-tiles: the two pieces are 5 and 4 k-tiles long (odd and

@@ -107,8 +107,9 @@ CASES = [
          bwd_order=0, defer=1),
     # conv_first_kernel (one image per block; <25, 5> with the live-channel hint, <25> / <9> without),
     # conv_first_wgrad_kernel for the 5x5 ones (Cg_log = 5).  fwd = (images, pixels per image, ..) is ali_conv_mtiles
-    # speaking of conv_first_kernel; no host query names conv_first_wgrad_kernel -- only its predicate in
-    # ali_conv_bwd_weight (8 -> 32 channels, 5x5, stride 1, pad 0) selects it, which these shapes are chosen to meet
+    # speaking of conv_first_kernel (ali_conv_plan: route 1, asserted below); no host query names
+    # conv_first_wgrad_kernel -- only its predicate in ali_conv_bwd_weight (8 -> 32 channels, 5x5, stride 1, pad 0)
+    # selects it, which these shapes are chosen to meet
     Case("first-5x5", (64, 5, 12, 20, 32, 5, 5, 1, 0), cpad=8, fwd=(64, 128, False), bwd=(120, 128, True), fwd_order=0,
          bwd_order=120, defer=0),
     Case("first-3x3", (64, 5, 12, 20, 32, 3, 3, 1, 0), cpad=8, fwd=(64, 180, False), bwd=(120, 128, True), fwd_order=0,
@@ -120,9 +121,9 @@ CASES = [
     Case("first-narrow", (64, 5, 12, 7, 32, 5, 5, 1, 0), cpad=8, fwd=(64, 24, False), bwd=(42, 128, True), fwd_order=0,
          bwd_order=42, defer=0),
     # conv_s2_first_kernel (a wave walks one output row; Q >= 32, P != Q), 4- and 8-channel strides, pad 1 and 2.
-    # No host query reports this kernel: fwd = (21 / 55, 64, ..) below is what ali_conv_mtiles says of the general GEMM,
-    # which is NOT launched here -- the entries only keep the geometry from drifting; the kernel is selected by its
-    # predicate (4 / 8 -> 64 channels, 5x5, stride 2, Q >= 32), which the shapes meet
+    # ali_conv_plan reports this kernel as route 2 (asserted below).  fwd = (21 / 55, 64, ..) is what ali_conv_mtiles says
+    # of the general GEMM, which is NOT launched here (the row-walking kernel has no M-tiles) -- the entries only keep
+    # the geometry from drifting
     Case("s2first-c4", (2, 3, 40, 71, 64, 5, 5, 2, 1), cpad=4, fwd=(21, 64, False), bwd=(46, 128, False), fwd_order=0,
          bwd_order=0, defer=1),
     Case("s2first-c8", (3, 7, 69, 66, 64, 5, 5, 2, 2), cpad=8, fwd=(55, 64, False), bwd=(110, 128, False), fwd_order=0,
@@ -275,11 +276,24 @@ def assert_route(ops, c):
 @pytest.mark.parametrize("cid", [c.id for c in CASES])
 def test_case_takes_its_route(cid):
     """Host side only: tile count, tile height and row order of both GEMM launches, dispatch-order entries, deferrable
-    flag -- and the arithmetic that puts `tail` and `xcd` on their launch shapes (finalize_and_launch's rules)."""
+    flag -- and the arithmetic that puts `tail` and `xcd` on their launch shapes (plan_conv's rules), next to what the
+    library's own plan says (ops.conv_plan)."""
     ops = _ops()
     ops.reload_tuning()
     c = BY_ID[cid]
     assert_route(ops, c)
+    if c.kind == "conv":
+        plan = ops.conv_plan(c.geom(ops), 0)
+        assert plan.route == (1 if cid.startswith("first-") else 2 if cid.startswith("s2first-") else 0), (cid, plan)
+        if plan.route == 0:
+            assert (plan.ntile_m, plan.tile_rows, bool(plan.pixel_major)) == c.route["fwd"], (cid, plan)
+        if cid == "tail":       # the whole tiles first, the left-over tiles cut two ways (352 blocks of the data gradient: split-K)
+            assert (plan.bm, plan.bn, plan.splitk, plan.tail_split, plan.tail_u0, plan.grid_x) == (64, 64, 1, 2, 512, 512 + 2 * 88)
+            bwd = ops.conv_plan(c.geom(ops), 1)
+            assert bwd.splitk > 1 and bwd.tail_split == 1
+        if cid == "xcd":
+            assert (plan.xcd_chunk, plan.lin1d, plan.grid_x) == (263, 1, 8 * 263) and plan.tail_split == 1
+            assert ops.conv_plan(c.geom(ops), 1).tail_split > 1
     # ali_conv_mtiles reports the tile's height only.  The block counts below take the 64-wide N tile pick_tile pairs
     # with a 64-row tile for the fp32 path (64x64 while blocks(64, 64) <= 16 * 256 CUs; its other tiles are 64x128,
     # reached only beyond that, and 128 rows high): K = 128 makes 2 N-tiles.  Should pick_tile ever pair 64 rows with 128

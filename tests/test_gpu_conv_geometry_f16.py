@@ -70,7 +70,7 @@ CASES = [
     (Case("t-pix", (70, 64, 2, 3, 128, 3, 5, 1, 2)), dict(fwd=(14, 64, True), bwd=(7, 64, True), uses=(1, 1))),
     # --- the fp32 module's `tail` does NOT reach the tail split under f16: its forward takes 150 tiles of 128 x 128 under
     # the fp16 tile rule, its data gradient 352 of 64 x 64 -- both below 2 blocks per CU, so both launches split K over
-    # ALL their tiles (finalize_and_launch: the tail split needs S == 1).  Kept as the deep split-K case of the fp16 loops
+    # ALL their tiles (plan_conv: the tail split needs S == 1).  Kept as the deep split-K case of the fp16 loops
     (B32["tail"], dict(fwd=(150, 128, True), bwd=(352, 64, True), uses=(1, 1))),
     # --- tail split under f16: 64 output channels both ways keep pick_tile at 64 x 64 and one N-tile.  Forward: 64 * 19 *
     # 30 rows = 570 blocks, 512 run whole, 58 left over; data gradient: 64 * 18 * 30 rows = 540 blocks, 28 left over;
@@ -225,8 +225,18 @@ def assert_route(ops, c):
 CUS = 256        # kNumCU of csrc/ali_common.h
 
 
+def plan16(ops, c, stage, twins=False, **env):
+    """ops.conv_plan of the layer's forward (0) / data-gradient (1) launch under precision("f16"), with fp16 twins of
+    both operands or without (the plan only asks whether the pointers are null)"""
+    with ops.tuning(**env), ops.precision("f16"):
+        ep = ops.epilogue()
+        if twins:
+            ep.in16 = ep.w16 = ep.out16 = 0x1000
+        return ops.conv_plan(c.geom(ops), _which(c)[stage], ep)
+
+
 def tail_split_ways(blocks, max_nkt):
-    """Sr of finalize_and_launch (gconv.hip) for a uniform-tap launch with a workspace and no ALI_SPLITK: 1 = no tail
+    """Sr of plan_conv (gconv.hip) for a uniform-tap launch with a workspace and no ALI_SPLITK: 1 = no tail
     split.  The split needs S == 1, i.e. a grid the split-K rule leaves alone (at least two blocks per CU, or fewer than
     8 k-tiles), fewer than 4 blocks per CU, and R = blocks % CUs left-over tiles that fit the chip at least twice over
     with at least 4 k-tiles per piece."""
@@ -253,13 +263,32 @@ def test_f16_case_takes_its_route(cid):
     if cid == "tail":       # below 2 blocks per CU: split-K over every tile, no tail split
         assert tail_split_ways(ROUTE[cid]["fwd"][0] * 1, T * c.C // 32) == 1        # (128-wide tile: one N-tile)
         assert tail_split_ways(ROUTE[cid]["bwd"][0] * ((c.C + 63) // 64), T * c.K // 32) == 1
-    if cid == "tail16":     # 64 x 64 tiles, one N-tile each way; k-tiles of 32 over all R * S taps of the interior tiles
+        for stage in (0, 1):        # ... and the library's own plan says the same
+            plan = plan16(ops, c, stage)
+            assert plan.splitk > 1 and plan.tail_split == 1 and plan.f16 == 1, (stage, plan)
+    if cid in TWINS:        # the LDS-DMA kernel: twins, gathered channels % 64 == 0, a forced (or large enough) 256 x 256 tile
+        for stage in (0, 1):
+            plan = plan16(ops, c, stage, twins=True, ALI_BM=256, ALI_BN=256)
+            if gemm_cin(c)[stage] % 64 == 0:
+                assert (plan.f16, plan.threads, plan.bm, plan.bn, plan.splitk, plan.tail_split) == (3, 512, 256, 256, 1, 1), (stage, plan)
+            else:               # (t-s2's data gradient gathers 160 channels: converted in flight, pick_tile's tile)
+                assert plan.f16 == 1 and plan.threads == 256 and plan.bm <= 128, (stage, plan)
+            assert plan16(ops, c, stage, twins=True, ALI_NO_DMA16=1, ALI_SPLITK=1).f16 == (2 if gemm_cin(c)[stage] % 64 == 0 else 1)
+            assert plan16(ops, c, stage, twins=False, ALI_BM=256, ALI_BN=256).f16 == 1      # no twins: the forced tile is dropped
+    if cid == "tail16":
+        for stage in (0, 1):
+            for twins in (False, True):
+                plan = plan16(ops, c, stage, twins=twins)
+                assert (plan.bm, plan.bn, plan.splitk, plan.tail_split, plan.tail_u0) == (64, 64, 1, 2, 512), (stage, twins, plan)
+                assert plan.f16 == (2 if twins else 1)     # 64 x 64 tiles, one N-tile each way; k-tiles of 32 over all R * S taps of the interior tiles
         assert ROUTE[cid]["fwd"][1] == ROUTE[cid]["bwd"][1] == 64 and c.C == c.K == 64
         assert ROUTE[cid]["fwd"][0] == (c.B * c.P * c.Q + 63) // 64 == 570 and ROUTE[cid]["bwd"][0] == (c.B * c.H * c.W + 63) // 64 == 540
         assert tail_split_ways(570, T * c.C // 32) == 2 and tail_split_ways(540, T * c.K // 32) == 2
     if cid in S2FIRST:      # predicate of conv_s2_first_kernel
         assert c.cpad in (4, 8) and c.K == 64 and c.R == c.S == 5 and c.stride == 2 and c.pad <= 2 and c.Q >= 32
         assert c.P % 4 != 0
+        plan = plan16(ops, c, 0)
+        assert (plan.route, plan.f16, plan.grid_x, plan.grid_y) == (2, 1, (c.P + 3) // 4, c.B), plan
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -589,10 +618,10 @@ def test_f16_lds_dma_kernel(cid, leg):
     """gconv_kernel512<256, 256, .., 3> forced onto the rectangular twin cases (ragged M: t-img, t-ct; ragged N: all, K <
     256 or 160; pixel-major with tile-wide tap skipping: t-pix; sub-pixel phases with nr != ns: t-ct): against the
     reference, and EQUAL to the register-staged twin loop run with whole k-loops (ALI_NO_DMA16=1, ALI_SPLITK=1).
-    No host query reports this kernel (ali_conv_mtiles plans without the twins), and a forced 256 x 256 tile quietly
-    falls back to pick_tile's when the launch may not use it: the test asserts the preconditions of finalize_and_launch
-    that it can see (both twins, gathered channels % 64 == 0, no fused BatchNorm or in_ld, ALI_SPLITK / ALI_NO_DMA16
-    unset) but cannot observe which kernel ran."""
+    ali_conv_mtiles plans without the twins and never reports this kernel, and a forced 256 x 256 tile quietly falls back
+    to pick_tile's when the launch may not use it: the test asserts plan_conv's preconditions (both twins, gathered
+    channels % 64 == 0, no fused BatchNorm or in_ld, ALI_SPLITK / ALI_NO_DMA16 unset) and that ali_conv_plan, asked
+    with the epilogue of the launch itself, names the kernel (F16 = 3, 512 threads)."""
     import os
     ops = _ops()
     c = BY_ID[cid]
@@ -608,6 +637,9 @@ def test_f16_lds_dma_kernel(cid, leg):
             outs.append({})
             for name, stage, go in stages:
                 out = outs[-1][name] = go()
+                ep = ops.epilogue()
+                ops._f16_operands(L.geom, _which(c)[stage], *((L.x, L.wf) if stage == 0 else (L.gpre, L.wd)), out, ep)
+                assert ops.conv_plan(L.geom, _which(c)[stage], ep).f16 == (3 if "ALI_BM" in env else 2), (cid, name, tag)
                 verify(c, L.r, name, nchw(out), name + tag)
                 twin_is_rounded_output(ops, out)
     for name, _, _ in stages:
@@ -628,7 +660,7 @@ def test_f16_lds_dma_kernel(cid, leg):
 def test_f16_tail_split(cid, leg, twins):
     """`tail16` at the library's own tile (the block count is the route): forward 570 and data gradient 540 blocks of
     64 x 64, of which 512 run whole and the 58 / 28 left over are cut two ways along K and folded in the kernel
-    (finalize_and_launch: uniform-tap loops, fp32 and fp16 alike; test_f16_case_takes_its_route asserts the
+    (plan_conv: uniform-tap loops, fp32 and fp16 alike; test_f16_case_takes_its_route asserts the
     preconditions).  `tail`, the fp32 module's geometry, has too few blocks under the fp16 tile rule: plain split-K."""
     ops = _ops()
     c = BY_ID[cid]
