@@ -1,0 +1,184 @@
+"""Executor of the morphomnist family: the measurement loop of ``mnist_gan_measured_cf.py`` and
+``mnist_vae_measured_cf.py`` -- ``extract_observed_attributes`` for every generated image -- as one call per batch.
+
+  MorphoMeasure   ``measure(images)`` returns thickness, intensity and slant (the scripts' three columns) plus area,
+                  stroke length, the slant of the up-sampled image, the counts behind them and a status per image, as
+                  device tensors with no host read: four launches per chunk (csrc/morpho.hip: binarise, distance map,
+                  thinning, measures).  ``table()`` is the one host read.
+
+CPU tensors run the statement ``morphomnist.morpho`` row by row in the dtype of the tensor (float64: the tests'
+reference; float32: their yardstick).  What is measured is that statement, not scikit-image's pipeline.
+"""
+import numpy as np
+import torch
+
+from morphomnist import morpho as stmt
+
+from . import ops
+
+COLUMNS = ("thickness", "intensity", "slant", "area", "length", "slant_hires")
+WORKSPACE_BUDGET = 384 << 20     # bytes of scratch, distance maps and bitmaps one chunk may hold
+
+
+def pack_bits(images):
+    """boolean images [B, Hh, Wh] (numpy) -> the bitmap words int32 [B, Hh, ceil(Wh / 32)] (a CPU tensor)"""
+    images = np.asarray(images, dtype=bool)
+    B, Hh, Wh = images.shape
+    wpr = (Wh + 31) // 32
+    padded = np.zeros((B, Hh, wpr * 32), dtype=bool)
+    padded[:, :, :Wh] = images
+    return torch.from_numpy(np.packbits(padded, axis=2, bitorder="little").view(np.int32).reshape(B, Hh, wpr).copy())
+
+
+def unpack_bits(words, Wh):
+    """bitmap words [B, Hh, wpr] (a tensor on any device) -> boolean images [B, Hh, Wh] (numpy)"""
+    w = words.detach().cpu().numpy().view(np.uint8)
+    return np.unpackbits(w, axis=2, bitorder="little")[:, :, :Wh].astype(bool)
+
+
+def scratch_bytes(H, W, scale):
+    """the largest scratch per image of the three kernels that use one (binarise, edt, thin)"""
+    return max(4 * H * W * scale if scale > 1 else 0, 2 * H * W * scale * scale)
+
+
+def per_image_bytes(H, W, scale):
+    """what one image of a chunk holds on the device: scratch, the distance map and the two bitmaps"""
+    Hh, Wh = H * scale, W * scale
+    return scratch_bytes(H, W, scale) + 4 * Hh * Wh + 2 * 4 * Hh * ((Wh + 31) // 32)
+
+
+def as_images(images):
+    """[B, 1, H, W], [B, H, W] or [B, H * W] (square) -> [B, H, W]"""
+    if images.dim() == 4 and images.shape[1] == 1:
+        return images[:, 0]
+    if images.dim() == 3:
+        return images
+    if images.dim() == 2:
+        n = int(round(images.shape[1] ** 0.5))
+        if n * n == images.shape[1]:
+            return images.reshape(images.shape[0], n, n)
+    raise ValueError(f"MorphoMeasure: need [B, 1, H, W], [B, H, W] or square [B, H * W] images, got "
+                     f"{tuple(images.shape)}")
+
+
+def statement_row(image, scale=16, threshold=.5, seed=0, dtype=np.float64, binary=None):
+    """One image through the statement: (counts [4] int64, values [5], slant_hires, status), the floats in ``dtype``.
+    ``binary``: continue from this binary image instead of the statement's own."""
+    image = np.asarray(image, dtype=dtype)
+    m = stmt.ImageMorphology(image, threshold, scale, seed, dtype, binary=binary)
+    straight, diagonal = stmt.skeleton_pairs(m.skeleton)
+    counts = np.array([m.binary_image.sum(), m.skeleton.sum(), straight, diagonal], dtype=np.int64)
+    values = np.array([m.area, m.stroke_length, m.mean_thickness, stmt.intensity(image),
+                       -stmt.ImageMoments(image - image.min(), dtype).horizontal_shear], dtype=dtype)
+    slant_hires = np.arctan(-stmt.ImageMoments(m.hires_image - m.hires_image.min(), dtype).horizontal_shear)
+    return counts, values, dtype(slant_hires), m.status
+
+
+class MorphoMeasure:
+    """``extract_observed_attributes`` of the measured-counterfactual scripts for a batch.
+
+    ``measure(images)`` takes [B, 1, H, W], [B, H, W] or [B, H * W] (square) float tensors, in the Generator's range
+    (-1 .. 1) or in 0 .. 255.  Every measure but ``intensity`` is unchanged by a positive affine map of the pixel
+    values: the threshold is relative, and the moments behind the two slants are those of the image less its minimum
+    -- for the scripts' ``255 * (x + 1) / 2`` with a background of 0 exactly the moments ``ImageMoments(image)`` takes.
+    ``intensity`` is returned in the units of the input.
+
+    Returns {"thickness", "intensity", "slant" (the scripts' -u11 / u02), "area", "length", "slant_hires"
+    (atan of the same ratio on the up-sampled image): float32 [B]; "counts": int32 [B, 4] = foreground, skeleton,
+    straight pairs, diagonal pairs; "status": int32 [B], 0, or 1 for an image without background (NaN thickness, area,
+    length), or 2 if the thinning did not finish}.  Limit: H * scale and W * scale up to 512.
+
+    CUDA tensors: four launches per chunk of ``chunk`` images, no host read; the default chunk is what fits
+    ``WORKSPACE_BUDGET`` (306 images of 28 x 28 at scale 16, 1.25 MB each), so memory is bounded whatever B is.
+    ``table()`` returns every row measured so far as numpy columns with one host read; ``reset()`` forgets them."""
+
+    def __init__(self, scale=16, threshold=.5, seed=0, chunk=None):
+        self.scale, self.threshold, self.seed = int(scale), float(threshold), int(seed)
+        if self.scale < 1:
+            raise ValueError("MorphoMeasure: scale >= 1")
+        self.chunk = chunk
+        self._ops, self._ws, self._blocks = {}, {}, []
+        self._keep = stmt.keep_bits()
+
+    def chunk_for(self, H, W):
+        if self.chunk is not None:
+            return max(int(self.chunk), 1)
+        return max(WORKSPACE_BUDGET // per_image_bytes(H, W, self.scale), 1)
+
+    def operators(self, H, W, device):
+        """(AH, AW): the expand operators as fp32 device tensors, built once per size in fp64 on the host"""
+        key = (H, W, str(device))
+        if key not in self._ops:
+            self._ops[key] = tuple(torch.from_numpy(stmt.expand_operator(n, self.scale).astype(np.float32)).to(device)
+                                   for n in (H, W)) if self.scale > 1 else (None, None)
+        return self._ops[key]
+
+    def _workspace(self, n, H, W, device):
+        need = ops.WS_RESERVED + n * scratch_bytes(H, W, self.scale)
+        ws = self._ws.get(str(device))
+        if ws is None or ws.numel() < need:
+            ws = self._ws[str(device)] = torch.zeros(need, dtype=torch.uint8, device=device)
+        return ws
+
+    @torch.no_grad()
+    def measure(self, images):
+        x = as_images(images)
+        if not x.is_floating_point():
+            raise ValueError("MorphoMeasure: float images only")
+        B, H, W = x.shape
+        if H * self.scale > ops.MORPHO_MAX_SIDE or W * self.scale > ops.MORPHO_MAX_SIDE:
+            raise ValueError(f"MorphoMeasure: {H} x {W} images at scale {self.scale} exceed the limit of "
+                             f"{ops.MORPHO_MAX_SIDE} x {ops.MORPHO_MAX_SIDE} up-sampled pixels")
+        if not x.is_cuda:
+            return self._remember(*self._measure_cpu(x))
+        if x.dtype != torch.float32 or not x[0].is_contiguous():
+            x = x.float().contiguous()
+        dev = x.device
+        counts = torch.empty(B, 4, dtype=torch.int32, device=dev)
+        values = torch.empty(B, 5, dtype=torch.float32, device=dev)
+        slant = torch.empty(B, dtype=torch.float32, device=dev)
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+        AH, AW = self.operators(H, W, dev)
+        n = min(self.chunk_for(H, W), B)
+        ws = self._workspace(n, H, W, dev)
+        for lo in range(0, B, n):
+            hi = min(lo + n, B)
+            bits, fg, hstats = ops.morpho_binarise(x[lo:hi], self.scale, AH, AW, self.threshold, ws=ws)
+            d2, st = ops.morpho_edt(bits, W * self.scale, ws=ws)
+            skel = ops.morpho_thin(bits, d2, fg, st, self._keep, self.seed, ws=ws)
+            ops.morpho_measure(x[lo:hi], self.scale, skel, d2, fg, hstats, st,
+                               out=(counts[lo:hi], values[lo:hi], slant[lo:hi]))
+            status[lo:hi] = st
+        return self._remember(counts, values, slant, status)
+
+    def _measure_cpu(self, x):
+        dtype = np.float64 if x.dtype == torch.float64 else np.float32
+        rows = [statement_row(img.numpy(), self.scale, self.threshold, self.seed, dtype) for img in x]
+        return (torch.from_numpy(np.stack([r[0] for r in rows]).astype(np.int32)),
+                torch.from_numpy(np.stack([r[1] for r in rows])),
+                torch.from_numpy(np.array([r[2] for r in rows], dtype=dtype)),
+                torch.tensor([r[3] for r in rows], dtype=torch.int32))
+
+    def _remember(self, counts, values, slant, status):
+        out = {"area": values[:, 0], "length": values[:, 1], "thickness": values[:, 2], "intensity": values[:, 3],
+               "slant": values[:, 4], "slant_hires": slant, "counts": counts, "status": status}
+        # one block of float64 per call: the integers are exact in it, and ``table`` reads every block at once
+        self._blocks.append(torch.cat([values.double(), slant.double().reshape(-1, 1), counts.double(),
+                                       status.double().reshape(-1, 1)], dim=1))
+        return out
+
+    def table(self):
+        """{column: numpy array} of every row measured so far, in order (one host read): the float columns of
+        ``COLUMNS``, ``counts`` int64 [N, 4] and ``status`` int64 [N]"""
+        if not self._blocks:
+            host = np.zeros((0, 11))
+        else:
+            host = torch.cat(self._blocks).cpu().numpy()
+        out = {"area": host[:, 0], "length": host[:, 1], "thickness": host[:, 2], "intensity": host[:, 3],
+               "slant": host[:, 4], "slant_hires": host[:, 5]}
+        out["counts"] = host[:, 6:10].astype(np.int64)
+        out["status"] = host[:, 10].astype(np.int64)
+        return out
+
+    def reset(self):
+        self._blocks = []

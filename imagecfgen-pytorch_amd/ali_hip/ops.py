@@ -7,6 +7,7 @@ import collections
 import ctypes
 from ctypes import byref, c_void_p
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1785,3 +1786,111 @@ def manifold_err(cf, owner, cls, S, Q, TS, TQ, cnt, tcnt, out=None):
                                     _chk(out, "out"), c_void_p(ws.data_ptr()), ws.numel(), _stream()),
                "ali_manifold_err")
     return out
+
+
+# ---------------------------------------------------------------------- the morphomnist family (csrc/morpho.hip)
+MORPHO_MAX_SIDE = 512            # H * scale and W * scale of one launch
+WS_RESERVED = 4096               # ALI_WS_RESERVED: the head of every workspace, in front of the scratch
+
+
+def _i32s(t, shape, name):
+    if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
+        raise ValueError(f"{name}: need a contiguous int32 CUDA tensor of shape {tuple(shape)}, got {t.dtype} "
+                         f"{tuple(t.shape)}")
+    return c_void_p(t.data_ptr())
+
+
+def _morpho_images(x, scale):
+    """x [B, H, W] fp32 CUDA with contiguous images -> (pointer, image pitch, B, H, W, Hh, Wh)"""
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.numel() > 0 and x[0].is_contiguous()):
+        raise ValueError(f"morpho: need fp32 CUDA images [B, H, W] with contiguous images, got {x.dtype} "
+                         f"{tuple(x.shape)} strides {tuple(x.stride())}")
+    B, H, W = x.shape
+    scale = int(scale)
+    if scale < 1 or H * scale > MORPHO_MAX_SIDE or W * scale > MORPHO_MAX_SIDE:
+        raise ValueError(f"morpho: {H} x {W} images at scale {scale} exceed the limit of {MORPHO_MAX_SIDE} x "
+                         f"{MORPHO_MAX_SIDE} up-sampled pixels")
+    ld = x.stride(0) if B > 1 else max(x.stride(0), H * W)
+    if ld < H * W:
+        raise ValueError("morpho: images overlap")
+    return c_void_p(x.data_ptr()), ld, B, H, W, H * scale, W * scale
+
+
+def _morpho_ws(ws, device):
+    ws = workspace(device) if ws is None else ws
+    if not (ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous()):
+        raise ValueError("morpho: the workspace is a contiguous uint8 CUDA tensor")
+    return c_void_p(ws.data_ptr()), ws.numel()
+
+
+def morpho_binarise(x, scale, AH=None, AW=None, threshold=0.5, ws=None):
+    """Up-sample and binarise x [B, H, W] (include/ali_hip.h: ali_morpho_binarise); AH [H * scale, H], AW [W * scale, W]
+    fp32 on the device (not needed at scale 1).  Returns (bin int32 [B, Hh, ceil(Wh / 32)] bitmap words, fg int32 [B],
+    hstats float64 [B, 8] = min, max and the six raw moment sums of the up-sampled image)."""
+    lib = _lib.load()
+    ptr, ld, B, H, W, Hh, Wh = _morpho_images(x, scale)
+    if scale > 1:
+        for a, n in ((AH, H), (AW, W)):
+            if a is None or tuple(a.shape) != (n * scale, n):
+                raise ValueError(f"morpho_binarise: need an expand operator of shape {(n * scale, n)}")
+    dev = x.device
+    bits = torch.empty(B, Hh, (Wh + 31) // 32, dtype=torch.int32, device=dev)
+    fg = torch.empty(B, dtype=torch.int32, device=dev)
+    hstats = torch.empty(B, 8, dtype=torch.float64, device=dev)
+    wp, wn = _morpho_ws(ws, dev)
+    _lib.check(lib.ali_morpho_binarise(ptr, ld, B, H, W, int(scale), None if scale == 1 else _chk(AH, "AH"),
+                                       None if scale == 1 else _chk(AW, "AW"), float(threshold),
+                                       _i32(bits, "bin"), _i32(fg, "fg"), _f64(hstats, hstats.shape, "hstats"), wp, wn,
+                                       _stream()), "ali_morpho_binarise")
+    return bits, fg, hstats
+
+
+def morpho_edt(bits, Wh, ws=None):
+    """The exact squared distance map of the bitmaps bits [B, Hh, ceil(Wh / 32)] (include/ali_hip.h: ali_morpho_edt).
+    Returns (d2 int32 [B, Hh, Wh], status int32 [B]: 1 for an image without background, whose d2 is not written)."""
+    lib = _lib.load()
+    B, Hh, wpr = bits.shape
+    if wpr != (Wh + 31) // 32:
+        raise ValueError(f"morpho_edt: {wpr} words per row do not hold {Wh} pixels")
+    d2 = torch.empty(B, Hh, Wh, dtype=torch.int32, device=bits.device)
+    status = torch.empty(B, dtype=torch.int32, device=bits.device)
+    wp, wn = _morpho_ws(ws, bits.device)
+    _lib.check(lib.ali_morpho_edt(_i32(bits, "bin"), B, Hh, Wh, _i32(d2, "d2"), _i32(status, "status"), wp, wn,
+                                  _stream()), "ali_morpho_edt")
+    return d2, status
+
+
+def morpho_thin(bits, d2, fg, status, keep16, seed=0, ws=None):
+    """The ordered thinning (include/ali_hip.h: ali_morpho_thin) of the bitmaps under the keys of d2 and seed; keep16: the
+    512-bit keep table as a uint32 numpy array [16].  Returns the skeleton bitmaps; ``status`` is updated in place."""
+    lib = _lib.load()
+    B, Hh, Wh = d2.shape
+    keep16 = np.ascontiguousarray(keep16, dtype=np.uint32)
+    if keep16.shape != (16,):
+        raise ValueError("morpho_thin: keep16 holds 16 words")
+    skel = torch.empty_like(bits)
+    wp, wn = _morpho_ws(ws, bits.device)
+    _lib.check(lib.ali_morpho_thin(_i32s(bits, (B, Hh, (Wh + 31) // 32), "bin"), _i32(d2, "d2"), _i32(fg, "fg", B), B, Hh,
+                                   Wh, int(seed) & (2 ** 64 - 1), keep16.ctypes.data_as(c_void_p), _i32(skel, "skel"),
+                                   _i32(status, "status", B), wp, wn, _stream()), "ali_morpho_thin")
+    return skel
+
+
+def morpho_measure(x, scale, skel, d2, fg, hstats, status, out=None):
+    """The measures of x [B, H, W] (include/ali_hip.h: ali_morpho_measure).  Returns (counts int32 [B, 4] = foreground,
+    skeleton, straight pairs, diagonal pairs; values fp32 [B, 5] = area, length, thickness, intensity, shear;
+    slant_hires fp32 [B]); ``out``: three such tensors to write into."""
+    lib = _lib.load()
+    ptr, ld, B, H, W, Hh, Wh = _morpho_images(x, scale)
+    dev = x.device
+    if out is None:
+        out = (torch.empty(B, 4, dtype=torch.int32, device=dev), torch.empty(B, 5, dtype=torch.float32, device=dev),
+               torch.empty(B, dtype=torch.float32, device=dev))
+    counts, values, slant = out
+    if tuple(values.shape) != (B, 5) or tuple(slant.shape) != (B,):
+        raise ValueError("morpho_measure: out is (counts [B, 4], values [B, 5], slant_hires [B])")
+    _lib.check(lib.ali_morpho_measure(ptr, ld, B, H, W, int(scale), _i32s(skel, (B, Hh, (Wh + 31) // 32), "skel"),
+                                      _i32s(d2, (B, Hh, Wh), "d2"), _i32(fg, "fg", B), _f64(hstats, (B, 8), "hstats"),
+                                      _i32(status, "status", B), _i32s(counts, (B, 4), "counts"), _chk(values, "values"),
+                                      _chk(slant, "slant_hires"), _stream()), "ali_morpho_measure")
+    return counts, values, slant

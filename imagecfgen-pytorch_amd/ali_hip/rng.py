@@ -1,14 +1,16 @@
 """The counter RNG of the HIP path on the host: the key schedule of csrc/ali_rng.h (the table there is the statement)
 and the references that reproduce a run's draws from (seed, counter, index) -- Dropout2d masks, latents, the WGAN-GP
-``eps``, Gumbel noise and Griffin-Lim phases.  The integers are exact on both sides."""
+``eps``, Gumbel noise, Griffin-Lim phases and the tiebreak of the thinning order.  The integers are exact on both sides."""
 import numpy as np
 import torch
 
 DEFAULT_Z_SEED, COUNTER_MUL = 0x5EED, 0xD1B54A32D192ED03
 LATENT_STREAM, GP_STREAM = 0x4C4154454E545A31, 0x47504D4958455053
 GUMBEL_STREAM, PHASE_STREAM = 0x47554D42454C3031, 0x474C504841534531
+THIN_STREAM = 0x5448494E4B455931
 STREAMS = {"mask": (), "latent": (LATENT_STREAM,), "gp": (LATENT_STREAM, GP_STREAM),       # the tags mixed into the
-           "gumbel": (LATENT_STREAM, GUMBEL_STREAM), "phase": (PHASE_STREAM,)}              # base key, in order
+           "gumbel": (LATENT_STREAM, GUMBEL_STREAM), "phase": (PHASE_STREAM,),               # base key, in order
+           "thin": (THIN_STREAM,)}
 M64, TWO24 = (1 << 64) - 1, 16777216.0
 
 
@@ -98,3 +100,9 @@ def phase_reference(seed, counter, n, offset=0):
     + t of a [B,F,T] batch): hi24 / lo24 of hash e under the "phase" key over 2^24, exact in fp32, in [0, 1)."""
     r = hashes(key(seed, counter, "phase"), n, offset)
     return torch.from_numpy((np.stack([hi24(r), lo24(r)]) / TWO24).astype(np.float32))
+
+
+def thin_reference(seed, n):
+    """The tiebreaks of ``ali_morpho_thin(seed)`` for the pixels of linear index 0 .. n of an image: an int64 array [n],
+    hi24 of hash i under the "thin" key of ``seed`` (no counter).  The same for every image of a batch."""
+    return hi24(hashes(key(seed, None, "thin"), n))

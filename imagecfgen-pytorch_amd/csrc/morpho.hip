@@ -1,0 +1,584 @@
+// The morphomnist family (include/ali_hip.h: ali_morpho_binarise, ali_morpho_edt, ali_morpho_thin, ali_morpho_measure):
+// thickness, stroke length, area, intensity and slant of a batch of images, measured the way morphomnist/morpho.py
+// (the statement, numpy / scipy in fp64) measures one image -- up-sample, binarise, exact Euclidean distance map,
+// ordered thinning, sums over the skeleton -- without a host step in between.
+//
+// One workgroup owns one image in every kernel, so nothing crosses a block: no arrival counters, no atomics.
+//   binarise  T = X AWt goes to the workspace ([H][W s] floats, s times smaller than the up-sampled image); the
+//             up-sampled image itself is formed twice, 8 rows x 256 columns at a time, as 255 * AH T with explicit fmaf
+//             (both passes give the same bits), and never stored: pass 1 reduces min, max and six fp64 moment sums,
+//             pass 2 thresholds, packs 32 pixels to a word by wave ballot and counts.  The product is taken of the
+//             image less its minimum (the plate goes back on the sums in fp64), so that an image in -1 .. 1 and the
+//             same image in 0 .. 255 go through the same arithmetic.  A constant input is all foreground by definition.
+//   edt       a thread per column finds the distance g to the nearest background pixel of the column (down, then up),
+//             as uint16 in the workspace; then a thread per pixel takes min_j' (j - j')^2 + g(i, j')^2 over |j - j'| < g:
+//             a candidate farther along the row than the column distance cannot win.  Integers throughout: exact.
+//   thin      the statement visits the foreground in ascending key order and sets each pixel to keep[its current 3 x 3
+//             neighbourhood].  A visit reads only the eight neighbours, so a pixel may be visited as soon as every
+//             neighbour with a smaller key has been: by induction over the key order every pixel then sees exactly the
+//             neighbourhood the sequential walk shows it.  The kernel runs rounds: (A) every undecided pixel whose
+//             smaller-key neighbours are all decided is marked ready, barrier, (B) the ready pixels decide, barrier.
+//             Two adjacent pixels are never ready in the same round (the larger of the two waits for the smaller), so
+//             a ready pixel's neighbourhood does not change during (B).  Two bitmaps live in LDS, the current image
+//             and the decided pixels (which takes the place of the initial image once the keys have been compared):
+//             2 * 4 * H s * ceil(W s / 32) bytes, 64 KB at 512 x 512 and 49 KB at 448 x 448; the per-pixel
+//             "which neighbours are smaller" byte is computed once, from d2, the initial neighbourhoods and the hash,
+//             and kept in the workspace (each byte is written and read by one thread).  The undecided pixel with the
+//             smallest key is always ready, so <= (foreground count) rounds suffice; the loop is capped there, and
+//             also left when a round decides nothing: status 2.
+//   measure   skeleton pixels, straight and diagonal neighbour pairs, the fp64 sum of sqrt(d2); on the input image
+//             min, max, the median of the pixels >= the middle by radix selection on the ordered bit patterns (32
+//             counting passes per order statistic: exact, and linear in the pixel count), and fp64 moments.
+// Every sum runs in a fixed order (ali_reduce.h): the same inputs give the same bits on every run.
+#include "ali_reduce.h"
+
+namespace ali {
+
+constexpr int kMoMaxSide = 512;                                      // H * scale and W * scale
+constexpr int kMoBlock = 256;
+constexpr int kMoWaves = kMoBlock / 64;
+constexpr int kMoRows = 8;                                           // rows of the up-sampled image a thread forms at once
+constexpr int kThinBlock = 1024;
+constexpr int kThinWords = (kMoMaxSide * (kMoMaxSide / 32) + kThinBlock - 1) / kThinBlock;   // bitmap words per thread
+constexpr uint32_t kNoBg = 0xFFFFu;                                  // column distance: no background in the column
+
+struct KeepTable { uint32_t w[16]; };
+
+__device__ __forceinline__ int wave_isum(int v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+template <int WAVES>
+__device__ __forceinline__ int block_isum(int v, int* s) { return waves_sum<WAVES>(wave_isum(v), s); }
+
+// bits x-1, x, x+1 of row y of a bitmap (bits 0..2); outside the image: 0
+__device__ __forceinline__ uint32_t row3(const uint32_t* bm, int Hh, int wpr, int y, int x) {
+  if (y < 0 || y >= Hh) return 0u;
+  const uint32_t* r = bm + y * wpr;
+  const int w = x >> 5, b = x & 31;
+  uint64_t v = (uint64_t)r[w] << 1;
+  if (b == 0 && w > 0) v |= r[w - 1] >> 31;
+  if (b == 31 && w + 1 < wpr) v |= (uint64_t)(r[w + 1] & 1u) << 33;
+  return (uint32_t)(v >> b) & 7u;
+}
+// the 3 x 3 neighbourhood of (y, x): bit 3 * r + c, centre at bit 4
+__device__ __forceinline__ uint32_t nbhd(const uint32_t* bm, int Hh, int wpr, int y, int x) {
+  return row3(bm, Hh, wpr, y - 1, x) | (row3(bm, Hh, wpr, y, x) << 3) | (row3(bm, Hh, wpr, y + 1, x) << 6);
+}
+// the bits of the last word of a row that lie inside the image
+__device__ __forceinline__ uint32_t tail_mask(int w, int wpr, int Wh) {
+  return ((w % wpr) == wpr - 1 && (Wh & 31)) ? (1u << (Wh & 31)) - 1u : 0xFFFFFFFFu;
+}
+
+// ------------------------------------------------------------------------------------------------------- binarise
+template <bool EXPAND>
+__global__ void __launch_bounds__(kMoBlock)
+morpho_binarise_kernel(const float* __restrict__ x, long long ld, int H, int W, int s, const float* __restrict__ AH,
+                       const float* __restrict__ AW, float threshold, float* __restrict__ T, uint32_t* __restrict__ bin,
+                       int wpr, int* __restrict__ fg, double* __restrict__ hstats) {
+  __shared__ float s_f[kMoWaves];
+  __shared__ double s_d[kMoWaves];
+  __shared__ int s_i[kMoWaves];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int Hh = H * s, Wh = W * s;
+  const float* X = x + (long long)b * ld;
+  float* Tb = T + (long long)b * H * Wh;
+  // The input's minimum comes off before the product and goes back on, in fp64, when the sums are written (the
+  // operator's rows sum to 1: a plate stays a plate).  The background of an image in -1 .. 1 is then formed as 0, not as
+  // -255 through operators rounded to fp32 -- the same arithmetic as for the same image in 0 .. 255.  A constant input
+  // is all foreground: its up-sampled image is constant too, and what rounding leaves of it is not thresholded.
+  float xmn = INFINITY, xmx = -INFINITY;
+  for (int e = tid; e < H * W; e += kMoBlock) {
+    xmn = fminf(xmn, X[e]);
+    xmx = fmaxf(xmx, X[e]);
+  }
+  xmx = block_max<kMoWaves>(xmx, s_f);
+  xmn = -block_max<kMoWaves>(-xmn, s_f);
+  const bool flat = xmn == xmx;
+  if (EXPAND) {
+    for (int e = tid; e < H * Wh; e += kMoBlock) {
+      const int r = e / Wh, j = e % Wh;
+      float acc = 0.f;
+      for (int c = 0; c < W; ++c) acc = fmaf(X[r * W + c] - xmn, AW[j * W + c], acc);
+      Tb[e] = acc;
+    }
+    __syncthreads();                                                 // (the block reads what the block wrote)
+  }
+  // rows i0 .. i0 + 7 of column j of the up-sampled image
+  auto tile = [&](int i0, int j, float (&v)[kMoRows]) {
+    if (!EXPAND) {
+#pragma unroll
+      for (int k = 0; k < kMoRows; ++k) v[k] = i0 + k < Hh ? X[(i0 + k) * W + j] : 0.f;
+      return;
+    }
+    float acc[kMoRows];
+#pragma unroll
+    for (int k = 0; k < kMoRows; ++k) acc[k] = 0.f;
+    for (int r = 0; r < H; ++r) {
+      const float t = Tb[r * Wh + j];
+#pragma unroll
+      for (int k = 0; k < kMoRows; ++k) {
+        const int i = i0 + k < Hh ? i0 + k : Hh - 1;                 // (uniform in the block)
+        acc[k] = fmaf(AH[i * H + r], t, acc[k]);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < kMoRows; ++k) v[k] = 255.f * acc[k];
+  };
+
+  float mn = INFINITY, mx = -INFINITY;
+  double m[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int i0 = 0; i0 < Hh; i0 += kMoRows)
+    for (int j = tid; j < Wh; j += kMoBlock) {
+      float v[kMoRows];
+      tile(i0, j, v);
+#pragma unroll
+      for (int k = 0; k < kMoRows; ++k) {
+        if (i0 + k >= Hh) break;
+        mn = fminf(mn, v[k]);
+        mx = fmaxf(mx, v[k]);
+        const double d = (double)v[k], xx = (double)j, yy = (double)(i0 + k);
+        m[0] += d; m[1] += xx * d; m[2] += yy * d; m[3] += xx * xx * d; m[4] += xx * yy * d; m[5] += yy * yy * d;
+      }
+    }
+  mx = block_max<kMoWaves>(mx, s_f);
+  mn = -block_max<kMoWaves>(-mn, s_f);
+#pragma unroll
+  for (int q = 0; q < 6; ++q) m[q] = block_sum<kMoWaves>(m[q], s_d);
+  if (tid == 0) {
+    double* hs = hstats + (long long)b * 8;
+    const double plate = EXPAND ? 255.0 * (double)xmn : 0.0, Hn = (double)Hh, Wn = (double)Wh;
+    const double sx = Wn * (Wn - 1.0) / 2.0, sy = Hn * (Hn - 1.0) / 2.0;
+    const double sxx = (Wn - 1.0) * Wn * (2.0 * Wn - 1.0) / 6.0, syy = (Hn - 1.0) * Hn * (2.0 * Hn - 1.0) / 6.0;
+    const double grid[6] = {Hn * Wn, Hn * sx, Wn * sy, Hn * sxx, sx * sy, Wn * syy};   // the sums of a plate of 1
+    hs[0] = (double)mn + plate; hs[1] = (double)mx + plate;
+#pragma unroll
+    for (int q = 0; q < 6; ++q) hs[2 + q] = m[q] + plate * grid[q];
+  }
+  const float thr = mn + (mx - mn) * threshold;
+  uint32_t* out = bin + (long long)b * Hh * wpr;
+  int count = 0;                                                     // per wave: every lane holds the wave's count
+  for (int i0 = 0; i0 < Hh; i0 += kMoRows)
+    for (int j0 = 0; j0 < Wh; j0 += kMoBlock) {                      // (uniform trip count: every lane reaches the ballot)
+      const int j = j0 + tid;
+      float v[kMoRows];
+      if (j < Wh) tile(i0, j, v);
+      const int w0 = (j0 + (tid & ~63)) >> 5;
+#pragma unroll
+      for (int k = 0; k < kMoRows; ++k) {
+        if (i0 + k >= Hh) break;
+        const unsigned long long bits = __ballot(j < Wh && (flat || v[k] >= thr));
+        count += __popcll(bits);
+        uint32_t* row = out + (i0 + k) * wpr;
+        if ((tid & 63) == 0 && w0 < wpr) row[w0] = (uint32_t)bits;
+        if ((tid & 63) == 32 && w0 + 1 < wpr) row[w0 + 1] = (uint32_t)(bits >> 32);
+      }
+    }
+  count = waves_sum<kMoWaves>(count, s_i);
+  if (tid == 0) fg[b] = count;
+}
+
+// ------------------------------------------------------------------------------------------------------------ edt
+__global__ void __launch_bounds__(kMoBlock)
+morpho_edt_kernel(const uint32_t* __restrict__ bin, int Hh, int Wh, int wpr, uint16_t* __restrict__ G,
+                  int* __restrict__ d2, int* __restrict__ status) {
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const uint32_t* bm = bin + (long long)b * Hh * wpr;
+  uint16_t* g = G + (long long)b * Hh * Wh;
+  int* out = d2 + (long long)b * Hh * Wh;
+  int any_bg = 0;
+  for (int j = tid; j < Wh; j += kMoBlock) {
+    int last = -1;
+    for (int i = 0; i < Hh; ++i) {
+      if (!((bm[i * wpr + (j >> 5)] >> (j & 31)) & 1u)) last = i;
+      g[i * Wh + j] = (uint16_t)(last < 0 ? kNoBg : (uint32_t)(i - last));
+    }
+    any_bg |= last >= 0;
+    last = -1;
+    for (int i = Hh - 1; i >= 0; --i) {
+      if (!((bm[i * wpr + (j >> 5)] >> (j & 31)) & 1u)) last = i;
+      const uint32_t up = last < 0 ? kNoBg : (uint32_t)(last - i);
+      if (up < g[i * Wh + j]) g[i * Wh + j] = (uint16_t)up;
+    }
+  }
+  const int has_bg = __syncthreads_or(any_bg);                       // (and the column distances are the block's to read)
+  if (tid == 0) status[b] = has_bg ? 0 : 1;
+  if (!has_bg) return;                                               // no background anywhere: d2 stays undefined
+  for (int e = tid; e < Hh * Wh; e += kMoBlock) {
+    const int i = e / Wh, j = e % Wh;
+    const uint32_t gc = g[e];
+    int best = 0;
+    if (gc != 0) {
+      const bool open = gc == kNoBg;                                 // no background in this column: the whole row
+      best = open ? 0x7FFFFFFF : (int)(gc * gc);
+      const int reach = open ? Wh : (int)gc - 1;
+      const uint16_t* row = g + i * Wh;
+      for (int dj = 1; dj <= reach && dj * dj < best; ++dj) {
+        if (j - dj >= 0) {
+          const uint32_t q = row[j - dj];
+          if (q != kNoBg) best = min(best, (int)(q * q) + dj * dj);
+        }
+        if (j + dj < Wh) {
+          const uint32_t q = row[j + dj];
+          if (q != kNoBg) best = min(best, (int)(q * q) + dj * dj);
+        }
+      }
+    }
+    out[e] = best;
+  }
+}
+
+// ----------------------------------------------------------------------------------------------------------- thin
+__global__ void __launch_bounds__(kThinBlock)
+morpho_thin_kernel(const uint32_t* __restrict__ bin, const int* __restrict__ d2, int Hh, int Wh, int wpr, uint64_t seed,
+                   KeepTable keep, uint8_t* __restrict__ less_ws, const int* __restrict__ fg,
+                   uint32_t* __restrict__ skel, int* __restrict__ status) {
+  extern __shared__ uint32_t s_bm[];
+  __shared__ uint32_t s_keep[16];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int nw = Hh * wpr;                                           // <= kThinWords * kThinBlock
+  uint32_t* init = s_bm;                                             // the input, until the keys are compared; then
+  uint32_t* dec = s_bm;                                              // decided, or not foreground: ~init to begin with
+  uint32_t* cur = s_bm + nw;
+  const uint32_t* bm = bin + (long long)b * nw;
+  const int* D = d2 + (long long)b * Hh * Wh;
+  uint8_t* L = less_ws + (long long)b * Hh * Wh;
+  const int st = status[b];
+  if (tid < 16) s_keep[tid] = keep.w[tid];
+  for (int w = tid; w < nw; w += kThinBlock) {
+    const uint32_t v = st == 0 ? bm[w] & tail_mask(w, wpr, Wh) : 0u; // (an image without background has no skeleton)
+    init[w] = v;
+    cur[w] = v;
+  }
+  __syncthreads();
+  // which neighbours come before a pixel: the key (d2, corner, tiebreak, linear index), compared lazily
+  const uint64_t key = thin_key(rng_base_key(seed, nullptr));
+  for (int w = tid; w < nw; w += kThinBlock) {
+    uint32_t u = init[w];
+    const int y = w / wpr, x0 = (w % wpr) * 32;
+    while (u) {
+      const int bit = __ffs(u) - 1;
+      u &= u - 1;
+      const int x = x0 + bit, lin = y * Wh + x;
+      const uint32_t nb = nbhd(init, Hh, wpr, y, x);
+      const int d = D[lin], c = 9 - __popc(nb);
+      uint32_t less = 0;
+#pragma unroll
+      for (int n = 0; n < 9; ++n) {
+        if (n == 4 || !((nb >> n) & 1u)) continue;
+        const int qy = y + n / 3 - 1, qx = x + n % 3 - 1, ql = qy * Wh + qx;
+        const int qd = D[ql];
+        bool lt;
+        if (qd != d) {
+          lt = qd < d;
+        } else {
+          const int qc = 9 - __popc(nbhd(init, Hh, wpr, qy, qx));
+          if (qc != c) {
+            lt = qc < c;
+          } else {
+            const uint32_t qt = hi24(hash_at(key, (uint64_t)ql)), pt = hi24(hash_at(key, (uint64_t)lin));
+            lt = qt != pt ? qt < pt : ql < lin;
+          }
+        }
+        if (lt) less |= 1u << (n < 4 ? n : n - 1);
+      }
+      L[lin] = (uint8_t)less;
+    }
+  }
+  __syncthreads();                                                   // (every neighbourhood of `init` has been read)
+  for (int w = tid; w < nw; w += kThinBlock) dec[w] = ~init[w];
+  __syncthreads();
+  const int cap = fg[b];
+  int stuck = 0, left = 0;
+  for (int round = 0; round < cap; ++round) {
+    uint32_t ready[kThinWords];
+#pragma unroll
+    for (int k = 0; k < kThinWords; ++k) {
+      const int w = tid + k * kThinBlock;
+      ready[k] = 0u;
+      if (w >= nw) continue;
+      uint32_t u = ~dec[w];
+      const int y = w / wpr, x0 = (w % wpr) * 32;
+      while (u) {
+        const int bit = __ffs(u) - 1;
+        u &= u - 1;
+        const uint32_t dn = nbhd(dec, Hh, wpr, y, x0 + bit);
+        const uint32_t have = (dn & 15u) | ((dn >> 5) << 4);
+        if (!((uint32_t)L[y * Wh + x0 + bit] & ~have)) ready[k] |= 1u << bit;
+      }
+    }
+    __syncthreads();                                                 // (A) read `dec`; (B) writes it
+    int mine = 0;
+#pragma unroll
+    for (int k = 0; k < kThinWords; ++k) {
+      const int w = tid + k * kThinBlock;
+      if (w >= nw) continue;
+      uint32_t r = ready[k], clear = 0u;
+      const int y = w / wpr, x0 = (w % wpr) * 32;
+      while (r) {
+        const int bit = __ffs(r) - 1;
+        r &= r - 1;
+        const uint32_t idx = nbhd(cur, Hh, wpr, y, x0 + bit);
+        if (!((s_keep[idx >> 5] >> (idx & 31)) & 1u)) clear |= 1u << bit;
+      }
+      if (ready[k]) {
+        cur[w] &= ~clear;                                            // (this thread is the only writer of word w)
+        dec[w] |= ready[k];
+        mine |= 2;
+      }
+      if (~dec[w]) mine |= 1;
+    }
+    left = __syncthreads_or(mine & 1);                               // (a predicate: any thread, not a bitwise or)
+    const int moved = __syncthreads_or(mine & 2);
+    if (!left) break;
+    if (!moved) { stuck = 1; break; }                                // (cannot happen: the smallest key is always ready)
+  }
+  for (int w = tid; w < nw; w += kThinBlock) skel[(long long)b * nw + w] = cur[w];
+  if (tid == 0 && (stuck || left)) status[b] = 2;
+}
+
+// -------------------------------------------------------------------------------------------------------- measure
+// floats as unsigned integers in the same order
+__device__ __forceinline__ uint32_t ordered_bits(float v) {
+  const uint32_t u = __float_as_uint(v);
+  return (u & 0x80000000u) ? ~u : u | 0x80000000u;
+}
+__device__ __forceinline__ float from_ordered_bits(uint32_t k) {
+  return __uint_as_float((k & 0x80000000u) ? k & 0x7FFFFFFFu : ~k);
+}
+
+// the k-th smallest (from 0) of the pixels >= thr: one counting pass per bit, from the top
+__device__ float select_kth(const float* X, int N, double thr, int k, int* s_i) {
+  uint32_t prefix = 0u;
+  for (int bit = 31; bit >= 0; --bit) {
+    const uint32_t above = bit == 31 ? 0u : ~((2u << bit) - 1u);
+    int cnt = 0;
+    for (int e = threadIdx.x; e < N; e += kMoBlock) {
+      const float v = X[e];
+      const uint32_t kb = ordered_bits(v);
+      cnt += (double)v >= thr && (kb & above) == prefix && !((kb >> bit) & 1u);
+    }
+    cnt = block_isum<kMoWaves>(cnt, s_i);
+    if (k >= cnt) {
+      k -= cnt;
+      prefix |= 1u << bit;
+    }
+  }
+  return from_ordered_bits(prefix);
+}
+
+__global__ void __launch_bounds__(kMoBlock)
+morpho_measure_kernel(const float* __restrict__ x, long long ld, int H, int W, int s, const uint32_t* __restrict__ skel,
+                      const int* __restrict__ d2, int wpr, const int* __restrict__ fg, const double* __restrict__ hstats,
+                      const int* __restrict__ status, int* __restrict__ counts, float* __restrict__ values,
+                      float* __restrict__ slant) {
+  __shared__ float s_f[kMoWaves];
+  __shared__ double s_d[kMoWaves];
+  __shared__ int s_i[kMoWaves];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int Hh = H * s, Wh = W * s, nw = Hh * wpr;
+  const uint32_t* sk = skel + (long long)b * nw;
+  const int* D = d2 + (long long)b * Hh * Wh;
+  const int st = status[b];
+  int n_sk = 0, n_st = 0, n_dg = 0;
+  double sum_d = 0.0;
+  for (int w = tid; w < nw; w += kMoBlock) {
+    uint32_t u = sk[w] & tail_mask(w, wpr, Wh);
+    const int y = w / wpr, x0 = (w % wpr) * 32;
+    while (u) {
+      const int bit = __ffs(u) - 1;
+      u &= u - 1;
+      const int xx = x0 + bit;
+      const uint32_t here = row3(sk, Hh, wpr, y, xx), below = row3(sk, Hh, wpr, y + 1, xx);
+      n_sk += 1;
+      n_st += (int)((here >> 2) & 1u) + (int)((below >> 1) & 1u);    // right, below
+      n_dg += (int)(below & 1u) + (int)((below >> 2) & 1u);          // below-left, below-right
+      sum_d += sqrt((double)D[y * Wh + xx]);
+    }
+  }
+  n_sk = block_isum<kMoWaves>(n_sk, s_i);
+  n_st = block_isum<kMoWaves>(n_st, s_i);
+  n_dg = block_isum<kMoWaves>(n_dg, s_i);
+  sum_d = block_sum<kMoWaves>(sum_d, s_d);
+
+  // the input image: min, max, moments
+  const float* X = x + (long long)b * ld;
+  const int N = H * W;
+  float mn = INFINITY, mx = -INFINITY;
+  double m[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int e = tid; e < N; e += kMoBlock) {
+    const float v = X[e];
+    mn = fminf(mn, v);
+    mx = fmaxf(mx, v);
+    const double d = (double)v, xx = (double)(e % W), yy = (double)(e / W);
+    m[0] += d; m[1] += xx * d; m[2] += yy * d; m[3] += xx * xx * d; m[4] += xx * yy * d; m[5] += yy * yy * d;
+  }
+  mx = block_max<kMoWaves>(mx, s_f);
+  mn = -block_max<kMoWaves>(-mn, s_f);
+#pragma unroll
+  for (int q = 0; q < 6; ++q) m[q] = block_sum<kMoWaves>(m[q], s_d);
+  const double thr = (double)mn + ((double)mx - (double)mn) * 0.5;
+  int n_sel = 0;
+  for (int e = tid; e < N; e += kMoBlock) n_sel += (double)X[e] >= thr;
+  n_sel = block_isum<kMoWaves>(n_sel, s_i);
+  const float nan = __int_as_float(0x7fc00000);
+  float intensity = nan;                                             // (NaN pixels: nothing is >= the middle)
+  if (n_sel > 0) {                                                   // (uniform)
+    const float hi = select_kth(X, N, thr, n_sel / 2, s_i);
+    intensity = hi;
+    if (!(n_sel & 1)) {
+      const float lo = select_kth(X, N, thr, n_sel / 2 - 1, s_i);
+      intensity = (float)(((double)lo + (double)hi) * 0.5);
+    }
+  }
+  if (tid != 0) return;
+  // -u11 / u02 of an Hn x Wn image less its minimum, from the raw sums q = (1, x, y, xx, xy, yy) of the image: the
+  // sums of a constant plate are closed forms, exact in fp64
+  auto shear = [](const double* q, double lo, double Hn, double Wn) {
+    const double sx = Wn * (Wn - 1.0) / 2.0, sy = Hn * (Hn - 1.0) / 2.0;
+    const double syy = (Hn - 1.0) * Hn * (2.0 * Hn - 1.0) / 6.0;
+    const double m00 = q[0] - lo * Hn * Wn;
+    const double m10 = (q[1] - lo * Hn * sx) / m00, m01 = (q[2] - lo * Wn * sy) / m00;
+    const double u11 = (q[4] - lo * sx * sy) / m00 - m10 * m01, u02 = (q[5] - lo * Wn * syy) / m00 - m01 * m01;
+    return -u11 / u02;
+  };
+  const bool ok = st == 0;
+  const double ds = (double)s;
+  int* c = counts + (long long)b * 4;
+  c[0] = fg[b]; c[1] = n_sk; c[2] = n_st; c[3] = n_dg;
+  float* v = values + (long long)b * 5;
+  v[0] = ok ? (float)((double)fg[b] / (ds * ds)) : nan;
+  v[1] = ok ? (float)(((double)n_st + sqrt(2.0) * (double)n_dg) / ds) : nan;
+  v[2] = ok && n_sk > 0 ? (float)(2.0 * (sum_d / (double)n_sk) / ds) : nan;
+  v[3] = intensity;
+  v[4] = (float)shear(m, (double)mn, (double)H, (double)W);
+  const double* hs = hstats + (long long)b * 8;
+  slant[b] = (float)atan(shear(hs + 2, hs[0], (double)Hh, (double)Wh));
+}
+
+// the side limits every entry point shares
+static int morpho_check_dims(const char* who, int32_t B, int32_t Hh, int32_t Wh) {
+  if (B < 1 || Hh < 1 || Wh < 1 || Hh > kMoMaxSide || Wh > kMoMaxSide) {
+    set_error("%s: B = %d < 1 or an up-sampled image of %d x %d outside [1, %d] x [1, %d]", who, (int)B, (int)Hh,
+              (int)Wh, kMoMaxSide, kMoMaxSide);
+    return ALI_ERR_BAD_ARG;
+  }
+  return ALI_OK;
+}
+// n * scale, or one past the limit when it is larger (no overflow)
+static int32_t hires_side(int32_t n, int32_t scale) {
+  const int64_t v = (int64_t)n * scale;
+  return (int32_t)(v > kMoMaxSide ? kMoMaxSide + 1 : v);
+}
+static int morpho_scratch(const char* who, void* ws, size_t ws_bytes, size_t need, void** at) {
+  if (need && (!ws || ws_payload_bytes(ws_bytes) < need)) {
+    set_error("%s: workspace too small (%zu bytes behind the reserved head needed)", who, need);
+    return ALI_ERR_WORKSPACE;
+  }
+  *at = ws_payload(ws);
+  return ALI_OK;
+}
+
+}  // namespace ali
+
+using namespace ali;
+
+extern "C" int ali_morpho_binarise(const float* x, int64_t ld, int32_t B, int32_t H, int32_t W, int32_t scale,
+                                   const float* AH, const float* AW, float threshold, uint32_t* bin, int32_t* fg,
+                                   double* hstats, void* ws, size_t ws_bytes, ali_stream_t stream) {
+  if (!x || !bin || !fg || !hstats || (scale > 1 && (!AH || !AW))) {
+    set_error("ali_morpho_binarise: NULL argument");
+    return ALI_ERR_BAD_ARG;
+  }
+  if (H < 1 || W < 1 || scale < 1 || ld < (int64_t)H * W) {
+    set_error("ali_morpho_binarise: H = %d, W = %d or scale = %d < 1, or ld = %lld < H * W", (int)H, (int)W, (int)scale,
+              (long long)ld);
+    return ALI_ERR_BAD_ARG;
+  }
+  int rc = morpho_check_dims("ali_morpho_binarise", B, hires_side(H, scale), hires_side(W, scale));
+  if (rc != ALI_OK) return rc;
+  const int Wh = W * scale, wpr = (Wh + 31) / 32;
+  void* T = nullptr;
+  rc = morpho_scratch("ali_morpho_binarise", ws, ws_bytes, scale > 1 ? sizeof(float) * (size_t)B * H * Wh : 0, &T);
+  if (rc != ALI_OK) return rc;
+  if (scale > 1)
+    hipLaunchKernelGGL(morpho_binarise_kernel<true>, dim3((unsigned)B), dim3(kMoBlock), 0, ST(stream), x, (long long)ld,
+                       (int)H, (int)W, (int)scale, AH, AW, threshold, static_cast<float*>(T), bin, wpr,
+                       reinterpret_cast<int*>(fg), hstats);
+  else
+    hipLaunchKernelGGL(morpho_binarise_kernel<false>, dim3((unsigned)B), dim3(kMoBlock), 0, ST(stream), x, (long long)ld,
+                       (int)H, (int)W, 1, AH, AW, threshold, static_cast<float*>(T), bin, wpr,
+                       reinterpret_cast<int*>(fg), hstats);
+  return check_launch("morpho_binarise_kernel");
+}
+
+extern "C" int ali_morpho_edt(const uint32_t* bin, int32_t B, int32_t Hh, int32_t Wh, int32_t* d2, int32_t* status,
+                              void* ws, size_t ws_bytes, ali_stream_t stream) {
+  if (!bin || !d2 || !status) {
+    set_error("ali_morpho_edt: NULL argument");
+    return ALI_ERR_BAD_ARG;
+  }
+  int rc = morpho_check_dims("ali_morpho_edt", B, Hh, Wh);
+  if (rc != ALI_OK) return rc;
+  void* G = nullptr;
+  rc = morpho_scratch("ali_morpho_edt", ws, ws_bytes, sizeof(uint16_t) * (size_t)B * Hh * Wh, &G);
+  if (rc != ALI_OK) return rc;
+  hipLaunchKernelGGL(morpho_edt_kernel, dim3((unsigned)B), dim3(kMoBlock), 0, ST(stream), bin, (int)Hh, (int)Wh,
+                     (Wh + 31) / 32, static_cast<uint16_t*>(G), reinterpret_cast<int*>(d2),
+                     reinterpret_cast<int*>(status));
+  return check_launch("morpho_edt_kernel");
+}
+
+extern "C" int ali_morpho_thin(const uint32_t* bin, const int32_t* d2, const int32_t* fg, int32_t B, int32_t Hh,
+                               int32_t Wh, uint64_t seed, const uint32_t* keep16, uint32_t* skel, int32_t* status,
+                               void* ws, size_t ws_bytes, ali_stream_t stream) {
+  if (!bin || !d2 || !fg || !keep16 || !skel || !status) {
+    set_error("ali_morpho_thin: NULL argument");
+    return ALI_ERR_BAD_ARG;
+  }
+  int rc = morpho_check_dims("ali_morpho_thin", B, Hh, Wh);
+  if (rc != ALI_OK) return rc;
+  void* L = nullptr;
+  rc = morpho_scratch("ali_morpho_thin", ws, ws_bytes, (size_t)B * Hh * Wh, &L);
+  if (rc != ALI_OK) return rc;
+  KeepTable keep;
+  for (int i = 0; i < 16; ++i) keep.w[i] = keep16[i];
+  const int wpr = (Wh + 31) / 32;
+  const size_t lds = 2 * sizeof(uint32_t) * (size_t)Hh * wpr;        // <= 64 KB of the CU's 160
+  if (lds + 64 > 64 * 1024) {                                        // (512 x 512 alone: above a workgroup's default limit)
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(morpho_thin_kernel),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             2 * (int)sizeof(uint32_t) * kMoMaxSide * (kMoMaxSide / 32));
+    if (e != hipSuccess) {
+      set_error("ali_morpho_thin: cannot raise the kernel's LDS limit: %s", hipGetErrorString(e));
+      return ALI_ERR_LAUNCH;
+    }
+  }
+  hipLaunchKernelGGL(morpho_thin_kernel, dim3((unsigned)B), dim3(kThinBlock), lds, ST(stream), bin,
+                     reinterpret_cast<const int*>(d2), (int)Hh, (int)Wh, wpr, seed, keep, static_cast<uint8_t*>(L),
+                     reinterpret_cast<const int*>(fg), skel, reinterpret_cast<int*>(status));
+  return check_launch("morpho_thin_kernel");
+}
+
+extern "C" int ali_morpho_measure(const float* x, int64_t ld, int32_t B, int32_t H, int32_t W, int32_t scale,
+                                  const uint32_t* skel, const int32_t* d2, const int32_t* fg, const double* hstats,
+                                  const int32_t* status, int32_t* counts, float* values, float* slant_hires,
+                                  ali_stream_t stream) {
+  if (!x || !skel || !d2 || !fg || !hstats || !status || !counts || !values || !slant_hires) {
+    set_error("ali_morpho_measure: NULL argument");
+    return ALI_ERR_BAD_ARG;
+  }
+  if (H < 1 || W < 1 || scale < 1 || ld < (int64_t)H * W) {
+    set_error("ali_morpho_measure: H = %d, W = %d or scale = %d < 1, or ld = %lld < H * W", (int)H, (int)W, (int)scale,
+              (long long)ld);
+    return ALI_ERR_BAD_ARG;
+  }
+  const int rc = morpho_check_dims("ali_morpho_measure", B, hires_side(H, scale), hires_side(W, scale));
+  if (rc != ALI_OK) return rc;
+  hipLaunchKernelGGL(morpho_measure_kernel, dim3((unsigned)B), dim3(kMoBlock), 0, ST(stream), x, (long long)ld, (int)H,
+                     (int)W, (int)scale, skel, reinterpret_cast<const int*>(d2), (W * scale + 31) / 32,
+                     reinterpret_cast<const int*>(fg), hstats, reinterpret_cast<const int*>(status),
+                     reinterpret_cast<int*>(counts), values, slant_hires);
+  return check_launch("morpho_measure_kernel");
+}

@@ -666,6 +666,56 @@ int ali_manifold_err(const float* cf, int64_t ld, int32_t M, int32_t D, const in
                      const int32_t* tcnt, int32_t O, int32_t C, float* out3, void* ws, size_t ws_bytes,
                      ali_stream_t stream);
 
+/* The morphomnist family (morphomnist/morpho.py: ImageMorphology, ImageMoments, and extract_observed_attributes of
+ * mnist_gan_measured_cf.py / mnist_vae_measured_cf.py) for a batch; csrc/morpho.hip.  One workgroup per image in every
+ * kernel; integers and fixed-order fp64 sums: the same inputs give the same bits on every run.  No allocation, no host
+ * read, no synchronisation.  Limit: H * scale <= 512 and W * scale <= 512 (ALI_ERR_BAD_ARG above it).  Bitmaps are
+ * [B][H * scale][wpr] uint32 words, wpr = ceil(W * scale / 32), pixel x of a row at bit x & 31 of word x >> 5; the bits
+ * of a row's last word beyond the image are written as 0 and ignored when read.  Every workspace is the caller's: the
+ * scratch lies behind the ALI_WS_RESERVED head, which these kernels neither read nor write.
+ *
+ * ali_morpho_binarise: x [B] images of H x W fp32, image b at b * ld (ld >= H * W), rows contiguous.  scale > 1:
+ *   hires = 255 * AH x AWt with AH [H * scale][H], AW [W * scale][W] fp32 DEVICE row-major (the 1-D expand operator of
+ *   the statement, rounded from fp64 by the caller), all products in fp32 with fmaf, taken of x less its minimum (the
+ *   minimum's plate, 255 * min, is added back to min, max and the sums in fp64: the operators' rows sum to 1);
+ *   scale == 1: hires = x and AH, AW are not read.  hires is never stored.  hstats [B][8] double = { min, max, sum v, sum x v, sum y v, sum x^2 v,
+ *   sum x y v, sum y^2 v } of hires (x the column, y the row; fp64 sums of the fp32 pixels); bin = hires >= min +
+ *   (max - min) * threshold (fp32), and all ones for a constant x (whose hires is constant but for rounding); fg [B] =
+ *   the number of set pixels.  ws >= ALI_WS_RESERVED + 4 * B * H * W * scale
+ *   bytes when scale > 1.
+ * ali_morpho_edt: d2 [B][Hh][Wh] int32 = the exact squared Euclidean distance of every pixel to the nearest 0 pixel of
+ *   its image (0 on the background; the border is not background: scipy.ndimage.distance_transform_edt).  status [B]
+ *   = 0, or 1 for an image without a 0 pixel, whose d2 is left unwritten.  ws >= ALI_WS_RESERVED + 2 * B * Hh * Wh.
+ * ali_morpho_thin: the ordered thinning of the statement.  Every set pixel has the key (d2, corner, tiebreak, linear
+ *   index y * Wh + x), corner = 9 - the number of set pixels of its 3 x 3 neighbourhood in bin (zero padded), tiebreak =
+ *   hi24 of hash (linear index) under the "thin" key of seed (csrc/ali_rng.h; no counter); the pixels are visited in
+ *   ascending key order and each is set to bit (its current neighbourhood) of keep16, a HOST table of 512 bits (bit
+ *   3 * r + c of the index is the pixel at row r, column c of the neighbourhood, the centre is bit 4).  The kernel
+ *   decides a pixel as soon as all its neighbours with smaller keys are decided, which gives the sequential result
+ *   exactly.  fg [B]: the set pixels of bin, the cap of the round loop; an image whose loop ends with undecided pixels
+ *   gets status 2 (it cannot happen with consistent inputs).  Images with status != 0 on entry get an empty skeleton.
+ *   skel: a bitmap like bin.  ws >= ALI_WS_RESERVED + B * Hh * Wh bytes.  LDS: 8 * Hh * wpr bytes (at most 64 KB).
+ * ali_morpho_measure: counts [B][4] int32 = { fg, skeleton pixels, straight pairs (right, below), diagonal pairs
+ *   (below-left, below-right) }; values [B][5] fp32 = { area = fg / scale^2, length = (straight + sqrt 2 * diagonal) /
+ *   scale, thickness = 2 * mean of sqrt(d2) over the skeleton / scale, intensity, shear }; slant_hires [B] =
+ *   atan(shear of hires).  intensity = the median (the mean of the two middle values for an even count, formed in
+ *   fp64) of the pixels of x that are >= min + (max - min) / 2 (compared in fp64), in the units of x; shear =
+ *   -u11 / u02 of the central moments of (image - its minimum), which a positive affine map of the pixel values leaves
+ *   unchanged and which is the moment ratio of the image itself when its background is 0; the minimum's plate is taken
+ *   out of the raw fp64 sums in closed form.  Each is evaluated in fp64 and rounded once.  status != 0 gives NaN
+ *   for area, length and thickness, an empty skeleton NaN for thickness, a constant image NaN for both shears. */
+int ali_morpho_binarise(const float* x, int64_t ld, int32_t B, int32_t H, int32_t W, int32_t scale, const float* AH,
+                        const float* AW, float threshold, uint32_t* bin, int32_t* fg, double* hstats, void* ws,
+                        size_t ws_bytes, ali_stream_t stream);
+int ali_morpho_edt(const uint32_t* bin, int32_t B, int32_t Hh, int32_t Wh, int32_t* d2, int32_t* status, void* ws,
+                   size_t ws_bytes, ali_stream_t stream);
+int ali_morpho_thin(const uint32_t* bin, const int32_t* d2, const int32_t* fg, int32_t B, int32_t Hh, int32_t Wh,
+                    uint64_t seed, const uint32_t* keep16, uint32_t* skel, int32_t* status, void* ws, size_t ws_bytes,
+                    ali_stream_t stream);
+int ali_morpho_measure(const float* x, int64_t ld, int32_t B, int32_t H, int32_t W, int32_t scale, const uint32_t* skel,
+                       const int32_t* d2, const int32_t* fg, const double* hstats, const int32_t* status,
+                       int32_t* counts, float* values, float* slant_hires, ali_stream_t stream);
+
 /* Attribute plumbing of one batch (mnist.py:47-55, audio_mnist.py:203-210, whalecalls.py:455): idx[b*n_cat + j] =
  * argmax of categorical attribute j (one-hot rows of n_classes[j] floats, or int32 when cat_is_int[j]; first maximum
  * like torch.argmax); cont[b*n_cont + j] = cont_in[j][b]. */
