@@ -5,9 +5,14 @@
                   stroke length, the slant of the up-sampled image, the counts behind them and a status per image, as
                   device tensors with no host read: four launches per chunk (csrc/morpho.hip: binarise, distance map,
                   thinning, measures).  ``table()`` is the one host read.
+  MorphoPerturb   ``apply(images, thickness, slant, intensity)`` returns the ground-truth counterfactual images of
+                  ``mnist_vae_measured_cf.py`` and the data-set builders -- ``SetThickness``, ``SetSlant``, ``downscale``,
+                  the intensity rescale -- as device tensors with no host read: the four launches above and three more
+                  per chunk (reshape, shear_reduce, set_intensity).
 
 CPU tensors run the statement ``morphomnist.morpho`` row by row in the dtype of the tensor (float64: the tests'
-reference; float32: their yardstick).  What is measured is that statement, not scikit-image's pipeline.
+reference; float32: their yardstick), and ``morphomnist.perturb`` likewise.  What is measured and perturbed is that
+statement, not scikit-image's pipeline.
 """
 import numpy as np
 import torch
@@ -182,3 +187,140 @@ class MorphoMeasure:
 
     def reset(self):
         self._blocks = []
+
+
+def perturb_scratch_bytes(H, W, scale):
+    """the largest scratch per image of the seven launches: the four of ``scratch_bytes``, reshape's row distances
+    (uint16 per up-sampled pixel) and shear_reduce's T (float64 [H * scale, W])"""
+    return max(scratch_bytes(H, W, scale), 2 * H * W * scale * scale, 8 * H * W * scale if scale > 1 else 0)
+
+
+def perturb_image_bytes(H, W, scale):
+    """what one image of a ``MorphoPerturb`` chunk holds on the device: ``per_image_bytes`` with the scratch of all seven
+    launches, the reshaped bitmap, the quantised and the rescaled image and the moment sums"""
+    Hh, Wh = H * scale, W * scale
+    scratch = perturb_scratch_bytes(H, W, scale)
+    return (per_image_bytes(H, W, scale) - scratch_bytes(H, W, scale) + scratch + 4 * Hh * ((Wh + 31) // 32)
+            + 2 * 4 * H * W + 6 * 8)
+
+
+class MorphoPerturb:
+    """The ground-truth counterfactual image of ``mnist_vae_measured_cf.py`` / ``mnist_vae_counterfactuals.py`` and the
+    data-set builders for a batch: ``SetThickness``, ``SetSlant``, ``downscale`` and the intensity rescale of
+    ``morphomnist.perturb.counterfactual_image``.
+
+    ``apply(images, thickness=None, slant=None, intensity=None)`` takes images as ``MorphoMeasure.measure`` does (-1 .. 1
+    or 0 .. 255: the bitmap does not depend on it) and targets as [B] tensors on the images' device, or None (radius 0 /
+    no shear / no rescale).  Returns {"images": float [B, H, W] in 0 .. 255, "status": int32 [B] (0; 1, 2 as
+    ``MorphoMeasure``; 3: radius > max_radius; 4: nothing left to work with -- the image is 0 then), "radius": int32 [B]
+    (signed: dilate >= 0 > erode), "thickness_before": the measured thickness, "shear_before": float64 [B], u11 / u02 of
+    the reshaped bitmap, "intensity_before": the median of the quantised image}.
+
+    CUDA tensors: per chunk the four launches of ``MorphoMeasure`` and three more (csrc/morpho.hip: reshape,
+    shear_reduce, set_intensity) on the current stream, no host read; the chunk is what fits ``WORKSPACE_BUDGET`` by
+    ``perturb_image_bytes``.  The footprints up to ``max_radius`` are built on the host once (seconds at 64).  CPU
+    tensors run the statement row by row in the tensor's dtype."""
+
+    def __init__(self, scale=16, threshold=.5, seed=0, chunk=None, max_radius=64):
+        self.measure = MorphoMeasure(scale, threshold, seed, chunk)
+        self.scale, self.threshold, self.seed, self.chunk = self.measure.scale, float(threshold), int(seed), chunk
+        self.max_radius = int(max_radius)
+        if not 0 <= self.max_radius <= ops.MORPHO_MAX_RADIUS:
+            raise ValueError(f"MorphoPerturb: max_radius in 0 .. {ops.MORPHO_MAX_RADIUS}")
+        self._rops, self._half, self._ws = {}, {}, {}
+
+    def chunk_for(self, H, W):
+        if self.chunk is not None:
+            return max(int(self.chunk), 1)
+        return max(WORKSPACE_BUDGET // perturb_image_bytes(H, W, self.scale), 1)
+
+    def reduce_operators(self, H, W, device):
+        """(RH, RW): the reduce operators as float64 device tensors, built once per size on the host"""
+        key = (H, W, str(device))
+        if key not in self._rops:
+            self._rops[key] = tuple(torch.from_numpy(stmt.reduce_operator(n, self.scale).copy()).to(device)
+                                    for n in (H, W)) if self.scale > 1 else (None, None)
+        return self._rops[key]
+
+    def half_table(self, device):
+        from morphomnist import perturb
+        if str(device) not in self._half:
+            self._half[str(device)] = torch.from_numpy(perturb.half_width_table(self.max_radius)).to(device)
+        return self._half[str(device)]
+
+    def _workspace(self, n, H, W, device):
+        need = ops.WS_RESERVED + n * perturb_scratch_bytes(H, W, self.scale)
+        ws = self._ws.get(str(device))
+        if ws is None or ws.numel() < need:
+            ws = self._ws[str(device)] = torch.zeros(need, dtype=torch.uint8, device=device)
+        return ws
+
+    @staticmethod
+    def _target(t, B, device, dtype, name):
+        if t is None:
+            return None
+        t = torch.as_tensor(t)
+        if tuple(t.shape) != (B,) or t.device != device:
+            raise ValueError(f"MorphoPerturb: {name} is a [{B}] tensor on {device}, or None")
+        return t.to(dtype).contiguous()
+
+    @torch.no_grad()
+    def apply(self, images, thickness=None, slant=None, intensity=None):
+        x = as_images(images)
+        if not x.is_floating_point():
+            raise ValueError("MorphoPerturb: float images only")
+        B, H, W = x.shape
+        s = self.scale
+        if H * s > ops.MORPHO_MAX_SIDE or W * s > ops.MORPHO_MAX_SIDE:
+            raise ValueError(f"MorphoPerturb: {H} x {W} images at scale {s} exceed the limit of "
+                             f"{ops.MORPHO_MAX_SIDE} x {ops.MORPHO_MAX_SIDE} up-sampled pixels")
+        if not x.is_cuda:
+            return self._apply_cpu(x, thickness, slant, intensity)
+        if x.dtype != torch.float32 or not x[0].is_contiguous():
+            x = x.float().contiguous()
+        dev = x.device
+        t_t = self._target(thickness, B, dev, torch.float32, "thickness")
+        t_i = self._target(intensity, B, dev, torch.float32, "intensity")
+        t_s = self._target(slant, B, dev, torch.float64, "slant")
+        if t_s is not None:
+            t_s = -torch.tan(t_s)                                     # the target shear, fp64 on the device
+        out = {"images": torch.empty(B, H, W, dtype=torch.float32, device=dev),
+               "status": torch.empty(B, dtype=torch.int32, device=dev),
+               "radius": torch.empty(B, dtype=torch.int32, device=dev),
+               "thickness_before": torch.empty(B, dtype=torch.float32, device=dev),
+               "shear_before": torch.empty(B, dtype=torch.float64, device=dev),
+               "intensity_before": torch.empty(B, dtype=torch.float32, device=dev)}
+        mm = self.measure
+        AH, AW = mm.operators(H, W, dev)
+        RH, RW = self.reduce_operators(H, W, dev)
+        half = self.half_table(dev)
+        n = min(self.chunk_for(H, W), B)
+        ws = self._workspace(n, H, W, dev)
+        for lo in range(0, B, n):
+            hi = min(lo + n, B)
+            cut = lambda t: None if t is None else t[lo:hi]
+            bits, fg, hstats = ops.morpho_binarise(x[lo:hi], s, AH, AW, self.threshold, ws=ws)
+            d2, st = ops.morpho_edt(bits, W * s, ws=ws)
+            skel = ops.morpho_thin(bits, d2, fg, st, mm._keep, self.seed, ws=ws)
+            _, values, _ = ops.morpho_measure(x[lo:hi], s, skel, d2, fg, hstats, st)
+            shaped, radius, sums, st = ops.morpho_reshape(bits, W * s, values[:, 2], cut(t_t), st, half, s, ws=ws)
+            q, shear = ops.morpho_shear_reduce(shaped, H, W, s, sums, cut(t_s), st, RH, RW, ws=ws)
+            _, median, st = ops.morpho_set_intensity(q, cut(t_i), st, out=out["images"][lo:hi])
+            out["status"][lo:hi], out["radius"][lo:hi] = st, radius
+            out["thickness_before"][lo:hi], out["shear_before"][lo:hi] = values[:, 2], shear
+            out["intensity_before"][lo:hi] = median
+        return out
+
+    def _apply_cpu(self, x, thickness, slant, intensity):
+        from morphomnist import perturb
+        dtype = np.float64 if x.dtype == torch.float64 else np.float32
+        B = x.shape[0]
+        pick = lambda t, b: None if t is None else torch.as_tensor(t)[b].item()
+        rows = [perturb.counterfactual_image(x[b].numpy(), pick(thickness, b), pick(slant, b), pick(intensity, b),
+                                             self.scale, self.threshold, self.seed, dtype, self.max_radius)
+                for b in range(B)]
+        col = lambda k, dt: torch.from_numpy(np.array([r[k] for r in rows], dtype=dt))
+        return {"images": torch.from_numpy(np.stack([r["image"] for r in rows]).astype(dtype)),
+                "status": col("status", np.int32), "radius": col("radius", np.int32),
+                "thickness_before": col("thickness", dtype), "shear_before": col("shear", np.float64),
+                "intensity_before": col("median", dtype)}

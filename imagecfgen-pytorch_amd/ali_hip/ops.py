@@ -1894,3 +1894,108 @@ def morpho_measure(x, scale, skel, d2, fg, hstats, status, out=None):
                                       _i32(status, "status", B), _i32s(counts, (B, 4), "counts"), _chk(values, "values"),
                                       _chk(slant, "slant_hires"), _stream()), "ali_morpho_measure")
     return counts, values, slant
+
+
+MORPHO_MAX_RADIUS = 64           # the largest radius of ali_morpho_reshape's half-width table
+
+
+def _typed(t, dtype, shape, name):
+    if not (t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
+        raise ValueError(f"{name}: need a contiguous {dtype} CUDA tensor of shape {tuple(shape)}, got {t.dtype} "
+                         f"{tuple(t.shape)}")
+    return c_void_p(t.data_ptr())
+
+
+def morpho_reshape(bits, Wh, thickness, target, status, half, scale, ws=None):
+    """``SetThickness`` on the bitmaps bits [B, Hh, ceil(Wh / 32)] (include/ali_hip.h: ali_morpho_reshape).  thickness:
+    fp32 [B], any stride (a column of ``morpho_measure``'s values); target: fp32 [B] or None (radius 0); half: int16
+    [max_radius + 1, 2 * max_radius + 1] on the device (``morphomnist.perturb.half_width_table``).  Returns (the
+    dilated / eroded bitmaps, signed radius int32 [B], moment sums int64 [B, 6], status int32 [B])."""
+    lib = _lib.load()
+    if not (bits.is_cuda and bits.dtype == torch.int32 and bits.dim() == 3 and bits.is_contiguous()):
+        raise ValueError("morpho_reshape: bits is a contiguous int32 CUDA tensor [B, Hh, wpr]")
+    B, Hh, wpr = bits.shape
+    scale = int(scale)
+    if wpr != (Wh + 31) // 32:
+        raise ValueError(f"morpho_reshape: {wpr} words per row do not hold {Wh} pixels")
+    if scale < 1 or Hh > MORPHO_MAX_SIDE or Wh > MORPHO_MAX_SIDE:
+        raise ValueError(f"morpho: {Hh} x {Wh} bitmaps exceed the limit of {MORPHO_MAX_SIDE} x {MORPHO_MAX_SIDE} "
+                         f"up-sampled pixels, or scale {scale} < 1")
+    if not (thickness.is_cuda and thickness.dtype == torch.float32 and tuple(thickness.shape) == (B,)
+            and (B == 1 or thickness.stride(0) >= 1)):
+        raise ValueError(f"morpho_reshape: thickness is an fp32 CUDA tensor [{B}]")
+    max_radius = half.shape[0] - 1 if half.dim() == 2 else -1
+    if not 0 <= max_radius <= MORPHO_MAX_RADIUS:
+        raise ValueError(f"morpho_reshape: the half-width table holds radii 0 .. max_radius <= {MORPHO_MAX_RADIUS}")
+    dev = bits.device
+    out = torch.empty_like(bits)
+    radius = torch.empty(B, dtype=torch.int32, device=dev)
+    sums = torch.empty(B, 6, dtype=torch.int64, device=dev)
+    status_out = torch.empty(B, dtype=torch.int32, device=dev)
+    wp, wn = _morpho_ws(ws, dev)
+    _lib.check(lib.ali_morpho_reshape(c_void_p(bits.data_ptr()), c_void_p(thickness.data_ptr()),
+                                      max(thickness.stride(0), 1), None if target is None else
+                                      _typed(target, torch.float32, (B,), "target"), _i32(status, "status", B),
+                                      _typed(half, torch.int16, (max_radius + 1, 2 * max_radius + 1), "half"),
+                                      max_radius, B, Hh, Wh, scale, _i32(out, "out"), _i32(radius, "radius"),
+                                      c_void_p(sums.data_ptr()), _i32(status_out, "status_out"), wp, wn, _stream()),
+               "ali_morpho_reshape")
+    return out, radius, sums, status_out
+
+
+def morpho_shear_reduce(bits, H, W, scale, sums, target_shear, status, RH=None, RW=None, ws=None, debug=False):
+    """``SetSlant`` and ``downscale`` (include/ali_hip.h: ali_morpho_shear_reduce) of the bitmaps bits [B, H * scale,
+    ceil(W * scale / 32)] with moment sums int64 [B, 6]; target_shear: float64 [B] = -tan(slant), or None (no shear);
+    RH [H, H * scale], RW [W, W * scale] float64 on the device (not needed at scale 1).  Returns (q fp32 [B, H, W] grey
+    levels, shear float64 [B] = u11 / u02 of the bitmaps), and with ``debug`` also (raw fp32 [B, H, W], shifts int32
+    [B, H * scale])."""
+    lib = _lib.load()
+    scale = int(scale)
+    Hh, Wh = H * scale, W * scale
+    if H < 1 or W < 1 or scale < 1 or Hh > MORPHO_MAX_SIDE or Wh > MORPHO_MAX_SIDE:
+        raise ValueError(f"morpho: {H} x {W} images at scale {scale} exceed the limit of {MORPHO_MAX_SIDE} x "
+                         f"{MORPHO_MAX_SIDE} up-sampled pixels")
+    if not (bits.is_cuda and bits.dim() == 3 and tuple(bits.shape[1:]) == (Hh, (Wh + 31) // 32)):
+        raise ValueError(f"morpho_shear_reduce: bits is [B, {Hh}, {(Wh + 31) // 32}]")
+    B = bits.shape[0]
+    if scale > 1:
+        for a, n in ((RH, H), (RW, W)):
+            if a is None or tuple(a.shape) != (n, n * scale):
+                raise ValueError(f"morpho_shear_reduce: need a reduce operator of shape {(n, n * scale)}")
+    dev = bits.device
+    q = torch.empty(B, H, W, dtype=torch.float32, device=dev)
+    shear = torch.empty(B, dtype=torch.float64, device=dev)
+    raw = torch.empty(B, H, W, dtype=torch.float32, device=dev) if debug else None
+    shifts = torch.empty(B, Hh, dtype=torch.int32, device=dev) if debug else None
+    wp, wn = _morpho_ws(ws, dev)
+    _lib.check(lib.ali_morpho_shear_reduce(_i32s(bits, (B, Hh, (Wh + 31) // 32), "bin"),
+                                           _typed(sums, torch.int64, (B, 6), "sums"), None if target_shear is None else
+                                           _f64(target_shear, (B,), "target_shear"), _i32(status, "status", B), B, H, W,
+                                           scale, None if scale == 1 else _f64(RH, (H, Hh), "RH"),
+                                           None if scale == 1 else _f64(RW, (W, Wh), "RW"), _chk(q, "q"), _opt(raw, "raw"),
+                                           None if shifts is None else _i32(shifts, "shifts"),
+                                           c_void_p(shear.data_ptr()), wp, wn, _stream()), "ali_morpho_shear_reduce")
+    return (q, shear, raw, shifts) if debug else (q, shear)
+
+
+def morpho_set_intensity(q, target, status, out=None):
+    """``SetIntensity`` on grey-level images q [B, ...] (include/ali_hip.h: ali_morpho_set_intensity); target: fp32 [B]
+    or None (no rescale).  Returns (images like q in 0 .. 255, median fp32 [B], status int32 [B]); ``out``: the tensor
+    the images are written into."""
+    lib = _lib.load()
+    if q.dim() < 2 or q.numel() == 0:
+        raise ValueError("morpho_set_intensity: q is [B, ...]")
+    B = q.shape[0]
+    N = q.numel() // B
+    if N > MORPHO_MAX_SIDE * MORPHO_MAX_SIDE:
+        raise ValueError(f"morpho: images of {N} pixels exceed the limit of {MORPHO_MAX_SIDE} x {MORPHO_MAX_SIDE}")
+    out = torch.empty_like(q) if out is None else out
+    if tuple(out.shape) != tuple(q.shape) or out.data_ptr() == q.data_ptr():
+        raise ValueError("morpho_set_intensity: out is a tensor of q's shape, and not q")
+    median = torch.empty(B, dtype=torch.float32, device=q.device)
+    status_out = torch.empty(B, dtype=torch.int32, device=q.device)
+    _lib.check(lib.ali_morpho_set_intensity(_chk(q, "q"), None if target is None else
+                                            _typed(target, torch.float32, (B,), "target"), _i32(status, "status", B), B,
+                                            N, _chk(out, "out"), _chk(median, "median"),
+                                            _i32(status_out, "status_out"), _stream()), "ali_morpho_set_intensity")
+    return out, median, status_out

@@ -29,6 +29,13 @@
 //   measure   skeleton pixels, straight and diagonal neighbour pairs, the fp64 sum of sqrt(d2); on the input image
 //             min, max, the median of the pixels >= the middle by radix selection on the ordered bit patterns (32
 //             counting passes per order statistic: exact, and linear in the pixel count), and fp64 moments.
+// The perturbation half (ali_morpho_reshape, ali_morpho_shear_reduce, ali_morpho_set_intensity; the statement is
+// morphomnist/perturb.py) continues from the bitmap and the thickness these leave on the device:
+//   reshape   SetThickness: the radius from the measured and the target thickness, then dilation / erosion by the
+//             footprint's half widths through a per-row distance map (uint16 in the workspace, the bitmap in LDS).
+//   shear_reduce  SetSlant as an exact fp64 shift per row, then downscale: T = warped RWt and 255 RH T in fp64, rounded
+//             once, quantised with a guard of 1/128 grey level.
+//   set_intensity  the median of the bright pixels by `measure`'s selection, q * (target / median) clipped to 0 .. 255.
 // Every sum runs in a fixed order (ali_reduce.h): the same inputs give the same bits on every run.
 #include "ali_reduce.h"
 
@@ -457,6 +464,275 @@ morpho_measure_kernel(const float* __restrict__ x, long long ld, int H, int W, i
   slant[b] = (float)atan(shear(hs + 2, hs[0], (double)Hh, (double)Wh));
 }
 
+// -------------------------------------------------------------------------------------------------------- reshape
+constexpr int kMoMaxRadius = 64;
+constexpr int kMoStuck = 4;                                          // status: nothing left to work with
+constexpr int kMoTooFar = 3;                                         // status: radius > max_radius
+
+__device__ __forceinline__ long long wave_lsum(long long v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+
+// SetThickness on the bitmaps: flat dilation (erosion: of the complement, complemented) by the footprint of the radius
+// the kernel forms itself from the measured and the target thickness.  A footprint is its half widths (every row one
+// centred run), so out(y, x) = any_dy hd(y + dy, x) <= half[dy], hd the distance along the row to the nearest set
+// pixel: uint16 in the workspace (the bitmap is in LDS, the 2-byte map of 448 x 448 would not fit), one coalesced read
+// per (pixel, dy) whatever the half width is, where OR-ing shifted rows costs 2 half + 1 word shifts.  Distances are
+// looked for two words to either side: a pixel in the third word is 65 or more away, above every half width (<= 64).
+__global__ void __launch_bounds__(kMoBlock)
+morpho_reshape_kernel(const uint32_t* __restrict__ bin, const float* __restrict__ thickness, long long thick_ld,
+                      const float* __restrict__ target, const int* __restrict__ status_in,
+                      const int16_t* __restrict__ half, int max_radius, int Hh, int Wh, int wpr, int scale,
+                      uint16_t* __restrict__ HD, uint32_t* __restrict__ out, int* __restrict__ radius,
+                      long long* __restrict__ sums, int* __restrict__ status_out) {
+  __shared__ uint32_t s_bm[kMoMaxSide * (kMoMaxSide / 32)];
+  __shared__ int s_half[2 * kMoMaxRadius + 1];
+  __shared__ long long s_l[kMoWaves];
+  const int b = blockIdx.x, tid = threadIdx.x, nw = Hh * wpr;
+  const uint32_t* bm = bin + (long long)b * nw;
+  uint32_t* ob = out + (long long)b * nw;
+  uint16_t* hd = HD + (long long)b * Hh * Wh;
+  const float thick = thickness[(long long)b * thick_ld];
+  const double delta = (double)(target ? target[b] : thick) - (double)thick;
+  int st = status_in[b], r = 0;
+  if (st == 0) {
+    if (delta != delta) {
+      st = kMoStuck;                                                 // NaN thickness: no skeleton
+    } else {
+      r = (int)fmin((double)scale * fabs(delta) / 2.0, 1073741824.0);
+      if (r > max_radius) st = kMoTooFar;
+    }
+  }
+  const bool erode = delta < 0.0;
+  if (st != 0) {                                                     // (uniform)
+    for (int w = tid; w < nw; w += kMoBlock) ob[w] = 0u;
+    if (tid == 0) {
+      radius[b] = st == kMoTooFar ? (erode ? -r : r) : 0;
+      status_out[b] = st;
+      for (int q = 0; q < 6; ++q) sums[(long long)b * 6 + q] = 0;
+    }
+    return;
+  }
+  for (int w = tid; w < nw; w += kMoBlock) s_bm[w] = (erode ? ~bm[w] : bm[w]) & tail_mask(w, wpr, Wh);
+  const int16_t* hrow = half + (long long)r * (2 * max_radius + 1);
+  for (int k = tid; k <= 2 * r; k += kMoBlock) s_half[k] = hrow[k];
+  __syncthreads();
+  for (int e = tid; e < Hh * Wh; e += kMoBlock) {
+    const int y = e / Wh, x = e % Wh, w = x >> 5, bit = x & 31;
+    const uint32_t* row = s_bm + y * wpr;
+    uint32_t d = kNoBg;
+    uint32_t v = row[w] & (0xFFFFFFFFu >> (31 - bit));               // the bits at or left of x
+    if (v) {
+      d = (uint32_t)(bit - (31 - __clz(v)));
+    } else {
+      for (int k = 1; k <= 2 && w - k >= 0; ++k)
+        if ((v = row[w - k]) != 0u) {
+          d = (uint32_t)(x - ((w - k) * 32 + 31 - __clz(v)));
+          break;
+        }
+    }
+    v = row[w] & (0xFFFFFFFFu << bit);                               // at or right of x
+    if (v) {
+      d = min(d, (uint32_t)(__ffs(v) - 1 - bit));
+    } else {
+      for (int k = 1; k <= 2 && w + k < wpr; ++k)
+        if ((v = row[w + k]) != 0u) {
+          d = min(d, (uint32_t)((w + k) * 32 + __ffs(v) - 1 - x));
+          break;
+        }
+    }
+    hd[e] = (uint16_t)d;
+  }
+  __syncthreads();                                                   // (the block reads what the block wrote)
+  long long m[6] = {0, 0, 0, 0, 0, 0};
+  for (int y = 0; y < Hh; ++y) {
+    const int lo = max(-r, -y), hi = min(r, Hh - 1 - y);
+    for (int j0 = 0; j0 < Wh; j0 += kMoBlock) {                      // (uniform trip count: every lane reaches the ballot)
+      const int j = j0 + tid;
+      bool hit = false;
+      if (j < Wh)
+        for (int dy = lo; dy <= hi && !hit; ++dy) hit = (int)hd[(y + dy) * Wh + j] <= s_half[dy + r];
+      const bool set = j < Wh && (hit != erode);
+      const unsigned long long bits = __ballot(set);
+      const int w0 = (j0 + (tid & ~63)) >> 5;
+      if ((tid & 63) == 0 && w0 < wpr) ob[y * wpr + w0] = (uint32_t)bits;
+      if ((tid & 63) == 32 && w0 + 1 < wpr) ob[y * wpr + w0 + 1] = (uint32_t)(bits >> 32);
+      if (set) {
+        const long long xx = j, yy = y;
+        m[0] += 1; m[1] += xx; m[2] += yy; m[3] += xx * xx; m[4] += xx * yy; m[5] += yy * yy;
+      }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 6; ++q) m[q] = waves_sum<kMoWaves>(wave_lsum(m[q]), s_l);
+  if (m[0] == 0 || m[0] * m[5] == m[2] * m[2]) {                     // nothing left, or one row (u02 == 0): uniform
+    for (int w = tid; w < nw; w += kMoBlock) ob[w] = 0u;             // (behind the barriers of the sums)
+#pragma unroll
+    for (int q = 0; q < 6; ++q) m[q] = 0;
+    st = kMoStuck;
+  }
+  if (tid == 0) {
+    radius[b] = erode ? -r : r;
+    status_out[b] = st;
+    for (int q = 0; q < 6; ++q) sums[(long long)b * 6 + q] = m[q];
+  }
+}
+
+// --------------------------------------------------------------------------------------------------- shear, reduce
+// u11 / u02 and the centroid row of a bitmap from its integer sums, and a row's shift, in fp64 with every operation
+// rounded on its own (no contraction): the bits numpy forms
+__device__ void shear_of_sums(const long long* q, double* shear, double* cy) {
+#pragma clang fp contract(off)
+  const double n = (double)q[0], sx = (double)q[1], sy = (double)q[2], sxy = (double)q[4], syy = (double)q[5];
+  const double m10 = sx / n, m01 = sy / n;
+  const double a = sxy / n, bb = m10 * m01, c = syy / n, d = m01 * m01;
+  const double u11 = a - bb, u02 = c - d;
+  *shear = u11 / u02;
+  *cy = m01;
+}
+__device__ int row_shift(double delta, double cy, int y, int Wh) {
+#pragma clang fp contract(off)
+  const double dy = (double)y - cy;
+  const double t = delta * dy;
+  const double f = floor(0.5 - t);
+  return (int)fmin(fmax(f, -(double)Wh), (double)Wh);
+}
+
+// SetSlant and downscale: the bitmap sheared row by row (nearest neighbour, 0 outside) into LDS, T = warped RWt into
+// the workspace (a sum over the set pixels of a row, ascending), raw = 255 * RH T rounded to fp32 once, q =
+// floor(clip(raw, 0, 255) + 2^-7) in fp32.  Operators, T and both sums are fp64: the rows of the reduce operator have
+// lobes of both signs, and where they cancel an operator rounded to fp32 alone leaves an error of thousands of ulps
+// of the pixel -- as large as the fp32 statement's whole error, which is the yardstick the tests hold this kernel to.
+__global__ void __launch_bounds__(kMoBlock)
+morpho_shear_reduce_kernel(const uint32_t* __restrict__ bin, const long long* __restrict__ sums,
+                           const double* __restrict__ target_shear, const int* __restrict__ status, int H, int W, int s,
+                           int wpr, const double* __restrict__ RH, const double* __restrict__ RW, double* __restrict__ T,
+                           float* __restrict__ qout, float* __restrict__ raw, int* __restrict__ shifts,
+                           double* __restrict__ shear_out) {
+  __shared__ uint32_t s_w[kMoMaxSide * (kMoMaxSide / 32)];
+  __shared__ int s_shift[kMoMaxSide];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int Hh = H * s, Wh = W * s, nw = Hh * wpr, N = H * W;
+  float* Q = qout + (long long)b * N;
+  if (status[b] != 0) {                                              // (uniform)
+    for (int e = tid; e < N; e += kMoBlock) {
+      Q[e] = 0.f;
+      if (raw) raw[(long long)b * N + e] = 0.f;
+    }
+    if (shifts)
+      for (int y = tid; y < Hh; y += kMoBlock) shifts[(long long)b * Hh + y] = 0;
+    if (tid == 0) shear_out[b] = __longlong_as_double(0x7ff8000000000000LL);
+    return;
+  }
+  double shear, cy;
+  shear_of_sums(sums + (long long)b * 6, &shear, &cy);
+  const double delta = target_shear ? __dsub_rn(target_shear[b], shear) : 0.0;
+  if (tid == 0) shear_out[b] = shear;
+  for (int y = tid; y < Hh; y += kMoBlock) {
+    const int sh = row_shift(delta, cy, y, Wh);
+    s_shift[y] = sh;
+    if (shifts) shifts[(long long)b * Hh + y] = sh;
+  }
+  __syncthreads();
+  const uint32_t* bm = bin + (long long)b * nw;
+  for (int e = tid; e < nw; e += kMoBlock) {
+    const int y = e / wpr, w = e % wpr;
+    const int p = 32 * w + s_shift[y];                               // the source column of bit 0
+    const int k = p >> 5, off = p & 31;                              // (floor: p may be negative)
+    const uint32_t* row = bm + y * wpr;
+    const uint64_t lo = k >= 0 && k < wpr ? row[k] & tail_mask(k, wpr, Wh) : 0u;
+    const uint64_t hi = k + 1 >= 0 && k + 1 < wpr ? row[k + 1] & tail_mask(k + 1, wpr, Wh) : 0u;
+    s_w[e] = (uint32_t)(((hi << 32) | lo) >> off) & tail_mask(w, wpr, Wh);
+  }
+  __syncthreads();
+  double* Tb = T + (long long)b * Hh * W;
+  if (s > 1) {
+    for (int e = tid; e < Hh * W; e += kMoBlock) {
+      const int y = e / W, c = e % W;
+      const double* rw = RW + (long long)c * Wh;
+      double acc = 0.0;
+      for (int w = 0; w < wpr; ++w) {
+        uint32_t u = s_w[y * wpr + w];
+        while (u) {
+          const int bit = __ffs(u) - 1;
+          u &= u - 1;
+          acc += rw[32 * w + bit];
+        }
+      }
+      Tb[e] = acc;
+    }
+    __syncthreads();                                                 // (the block reads what the block wrote)
+  }
+  for (int e = tid; e < N; e += kMoBlock) {
+    const int i = e / W, c = e % W;
+    double acc;
+    if (s > 1) {
+      acc = 0.0;
+      const double* rh = RH + (long long)i * Hh;
+      for (int y = 0; y < Hh; ++y) acc = fma(rh[y], Tb[y * W + c], acc);
+    } else {
+      acc = (double)((s_w[i * wpr + (c >> 5)] >> (c & 31)) & 1u);
+    }
+    const float v = (float)(255.0 * acc);
+    if (raw) raw[(long long)b * N + e] = v;
+    Q[e] = floorf(fminf(fmaxf(v, 0.f), 255.f) + 0.0078125f);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------ intensity
+// SetIntensity on the quantised image: the median of the pixels in the upper half of its range (the selection of
+// `measure`), factor = target / median and the product in fp32, clipped to 0 .. 255.  An image that is 0 everywhere
+// gets status 4; an image with a status is written as 0.
+__global__ void __launch_bounds__(kMoBlock)
+morpho_set_intensity_kernel(const float* __restrict__ q, const float* __restrict__ target,
+                            const int* __restrict__ status_in, int N, float* __restrict__ out,
+                            float* __restrict__ median, int* __restrict__ status_out) {
+  __shared__ float s_f[kMoWaves];
+  __shared__ int s_i[kMoWaves];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const float* X = q + (long long)b * N;
+  float* O = out + (long long)b * N;
+  float mn = INFINITY, mx = -INFINITY;
+  for (int e = tid; e < N; e += kMoBlock) {
+    mn = fminf(mn, X[e]);
+    mx = fmaxf(mx, X[e]);
+  }
+  mx = block_max<kMoWaves>(mx, s_f);
+  mn = -block_max<kMoWaves>(-mn, s_f);
+  int st = status_in[b];
+  if (st == 0 && !(mx > 0.f)) st = kMoStuck;
+  const float nan = __int_as_float(0x7fc00000);
+  if (st != 0) {                                                     // (uniform)
+    for (int e = tid; e < N; e += kMoBlock) O[e] = 0.f;
+    if (tid == 0) {
+      median[b] = nan;
+      status_out[b] = st;
+    }
+    return;
+  }
+  const double thr = (double)mn + ((double)mx - (double)mn) * 0.5;
+  int n_sel = 0;
+  for (int e = tid; e < N; e += kMoBlock) n_sel += (double)X[e] >= thr;
+  n_sel = block_isum<kMoWaves>(n_sel, s_i);                          // (>= 1: the maximum is selected)
+  float med = select_kth(X, N, thr, n_sel / 2, s_i);
+  if (!(n_sel & 1)) {
+    const float lo = select_kth(X, N, thr, n_sel / 2 - 1, s_i);
+    med = (float)(((double)lo + (double)med) * 0.5);
+  }
+  if (target) {
+    const float mult = target[b] / med;
+    for (int e = tid; e < N; e += kMoBlock) O[e] = fminf(fmaxf(X[e] * mult, 0.f), 255.f);
+  } else {
+    for (int e = tid; e < N; e += kMoBlock) O[e] = X[e];
+  }
+  if (tid == 0) {
+    median[b] = med;
+    status_out[b] = 0;
+  }
+}
+
 // the side limits every entry point shares
 static int morpho_check_dims(const char* who, int32_t B, int32_t Hh, int32_t Wh) {
   if (B < 1 || Hh < 1 || Wh < 1 || Hh > kMoMaxSide || Wh > kMoMaxSide) {
@@ -581,4 +857,72 @@ extern "C" int ali_morpho_measure(const float* x, int64_t ld, int32_t B, int32_t
                      reinterpret_cast<const int*>(fg), hstats, reinterpret_cast<const int*>(status),
                      reinterpret_cast<int*>(counts), values, slant_hires);
   return check_launch("morpho_measure_kernel");
+}
+
+extern "C" int ali_morpho_reshape(const uint32_t* bin, const float* thickness, int64_t thickness_ld, const float* target,
+                                  const int32_t* status_in, const int16_t* half, int32_t max_radius, int32_t B,
+                                  int32_t Hh, int32_t Wh, int32_t scale, uint32_t* out, int32_t* radius, int64_t* sums,
+                                  int32_t* status_out, void* ws, size_t ws_bytes, ali_stream_t stream) {
+  if (!bin || !thickness || !status_in || !half || !out || !radius || !sums || !status_out) {
+    set_error("ali_morpho_reshape: NULL argument");
+    return ALI_ERR_BAD_ARG;
+  }
+  if (max_radius < 0 || max_radius > kMoMaxRadius || scale < 1 || thickness_ld < 1) {
+    set_error("ali_morpho_reshape: max_radius = %d outside [0, %d], scale = %d < 1 or thickness_ld = %lld < 1",
+              (int)max_radius, kMoMaxRadius, (int)scale, (long long)thickness_ld);
+    return ALI_ERR_BAD_ARG;
+  }
+  int rc = morpho_check_dims("ali_morpho_reshape", B, Hh, Wh);
+  if (rc != ALI_OK) return rc;
+  void* HD = nullptr;
+  rc = morpho_scratch("ali_morpho_reshape", ws, ws_bytes, sizeof(uint16_t) * (size_t)B * Hh * Wh, &HD);
+  if (rc != ALI_OK) return rc;
+  hipLaunchKernelGGL(morpho_reshape_kernel, dim3((unsigned)B), dim3(kMoBlock), 0, ST(stream), bin, thickness,
+                     (long long)thickness_ld, target, reinterpret_cast<const int*>(status_in), half, (int)max_radius,
+                     (int)Hh, (int)Wh, (Wh + 31) / 32, (int)scale, static_cast<uint16_t*>(HD), out,
+                     reinterpret_cast<int*>(radius), reinterpret_cast<long long*>(sums),
+                     reinterpret_cast<int*>(status_out));
+  return check_launch("morpho_reshape_kernel");
+}
+
+extern "C" int ali_morpho_shear_reduce(const uint32_t* bin, const int64_t* sums, const double* target_shear,
+                                       const int32_t* status, int32_t B, int32_t H, int32_t W, int32_t scale,
+                                       const double* RH, const double* RW, float* q, float* raw, int32_t* shifts,
+                                       double* shear, void* ws, size_t ws_bytes, ali_stream_t stream) {
+  if (!bin || !sums || !status || !q || !shear || (scale > 1 && (!RH || !RW))) {
+    set_error("ali_morpho_shear_reduce: NULL argument");
+    return ALI_ERR_BAD_ARG;
+  }
+  if (H < 1 || W < 1 || scale < 1) {
+    set_error("ali_morpho_shear_reduce: H = %d, W = %d or scale = %d < 1", (int)H, (int)W, (int)scale);
+    return ALI_ERR_BAD_ARG;
+  }
+  int rc = morpho_check_dims("ali_morpho_shear_reduce", B, hires_side(H, scale), hires_side(W, scale));
+  if (rc != ALI_OK) return rc;
+  void* T = nullptr;
+  rc = morpho_scratch("ali_morpho_shear_reduce", ws, ws_bytes,
+                      scale > 1 ? sizeof(double) * (size_t)B * H * scale * W : 0, &T);
+  if (rc != ALI_OK) return rc;
+  hipLaunchKernelGGL(morpho_shear_reduce_kernel, dim3((unsigned)B), dim3(kMoBlock), 0, ST(stream), bin,
+                     reinterpret_cast<const long long*>(sums), target_shear, reinterpret_cast<const int*>(status),
+                     (int)H, (int)W, (int)scale, (W * scale + 31) / 32, RH, RW, static_cast<double*>(T), q, raw,
+                     reinterpret_cast<int*>(shifts), shear);
+  return check_launch("morpho_shear_reduce_kernel");
+}
+
+extern "C" int ali_morpho_set_intensity(const float* q, const float* target, const int32_t* status_in, int32_t B,
+                                        int32_t N, float* out, float* median, int32_t* status_out,
+                                        ali_stream_t stream) {
+  if (!q || !status_in || !out || !median || !status_out) {
+    set_error("ali_morpho_set_intensity: NULL argument");
+    return ALI_ERR_BAD_ARG;
+  }
+  if (B < 1 || N < 1 || N > kMoMaxSide * kMoMaxSide) {
+    set_error("ali_morpho_set_intensity: B = %d < 1 or N = %d outside [1, %d]", (int)B, (int)N,
+              kMoMaxSide * kMoMaxSide);
+    return ALI_ERR_BAD_ARG;
+  }
+  hipLaunchKernelGGL(morpho_set_intensity_kernel, dim3((unsigned)B), dim3(kMoBlock), 0, ST(stream), q, target,
+                     reinterpret_cast<const int*>(status_in), (int)N, out, median, reinterpret_cast<int*>(status_out));
+  return check_launch("morpho_set_intensity_kernel");
 }

@@ -14,6 +14,9 @@ checked (DESIGN 3.16 says why).
              pixels are visited once each, in ascending key order, and set to KEEP[current neighbourhood].
   measures   area = foreground / s^2; stroke_length = (straight + sqrt 2 * diagonal neighbour pairs of the skeleton) / s;
              mean_thickness = 2 * mean of sqrt(d2) over the skeleton / s.
+  reduce     low = R(H, s) hires R(W, s)^T, R(n, s) the [n, n s] matrix whose column k is the cubic-spline zoom by 1 / s
+             (mirror boundary, grid mode) of the unit vector e_k smoothed by the same Gaussian: the transpose-shaped
+             twin of A.  ``downscale`` = ``quantise`` of it (the perturbation half, morphomnist/perturb.py).
 """
 import functools
 
@@ -79,6 +82,50 @@ def expand(image, scale, dtype=np.float64):
     H, W = image.shape
     AH, AW = expand_operator(H, scale).astype(dtype), expand_operator(W, scale).astype(dtype)
     return dtype(255) * (AH @ (image @ AW.T))
+
+
+@functools.lru_cache(maxsize=None)
+def reduce_operator(n, scale, order=3):
+    """R(n, scale): float64 [n, n * scale], read-only; the identity at scale 1.  Its rows sum to 1 (5e-16 at (28, 16))."""
+    if scale == 1:
+        R = np.eye(n)
+    else:
+        sigma = 2 * scale / 6.0
+        cols = [ndimage.zoom(ndimage.gaussian_filter1d(e, sigma, mode="reflect"), n / (n * scale), order=order,
+                             mode="mirror", grid_mode=True) for e in np.eye(n * scale)]
+        R = np.stack(cols, axis=1)
+    R.setflags(write=False)
+    return R
+
+
+def reduce(image, scale, dtype=np.float64):
+    """``image`` [H s, W s] brought down to [H, W]: RH image RW^T, the operators rounded to ``dtype`` and the products
+    taken in it (the image's own units: no factor of 255)"""
+    image = np.asarray(image, dtype=dtype)
+    if scale == 1:
+        return image
+    Hh, Wh = image.shape
+    RH, RW = reduce_operator(Hh // scale, scale).astype(dtype), reduce_operator(Wh // scale, scale).astype(dtype)
+    return RH @ (image @ RW.T)
+
+
+QUANTISE_GUARD = 2.0 ** -7       # of a grey level
+
+
+def quantise_levels(levels):
+    """floor(clip(levels, 0, 255) + 2^-7) in the dtype of ``levels`` (grey levels, 0 .. 255): float-valued integers"""
+    levels = np.asarray(levels)
+    return np.floor(np.clip(levels, 0, 255) + levels.dtype.type(QUANTISE_GUARD))
+
+
+def quantise(v):
+    """floor(clip(255 v, 0, 255) + 2^-7).  The reference writes ``(255. * v).astype(np.uint8)``, which wraps above 255
+    and makes a plate of ones 254 or 255 by the last bit of a sum (the fp32 rows of R times 255 sum to 254.99998 .. 255);
+    the clamp replaces the wrap and the guard of 1 / 128 grey level makes plate and background deterministic."""
+    v = np.asarray(v)
+    if not np.issubdtype(v.dtype, np.floating):
+        v = v.astype(np.float64)
+    return quantise_levels(v.dtype.type(255) * v)
 
 
 def binarise(hires, threshold=.5):
@@ -201,6 +248,11 @@ class ImageMorphology:
         if self.status or not self.skeleton.any():
             return float("nan")
         return self.dtype(2) * np.mean(self.distance_map[self.skeleton]) / self.dtype(self.scale)
+
+    def downscale(self, image):
+        """``image`` [H s, W s] in the units of a bitmap (0 .. 1) -> [H, W] grey levels, float-valued integers in
+        ``dtype``: ``quantise(reduce(image))``"""
+        return quantise(reduce(np.asarray(image, dtype=self.dtype), self.scale, self.dtype))
 
 
 class ImageMoments:

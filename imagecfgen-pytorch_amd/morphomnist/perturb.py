@@ -1,0 +1,309 @@
+"""The perturbations the measured-counterfactual scripts and the data-set builders use -- ``SetThickness``, ``SetSlant``,
+``SetIntensity`` (and ``Thinning`` / ``Thickening``) -- written on numpy and scipy alone, and the scripts' five-line chain
+for one image, ``counterfactual_image``.  This module is the *statement* the kernels ``ali_morpho_reshape``,
+``ali_morpho_shear_reduce`` and ``ali_morpho_set_intensity`` (csrc/morpho.hip) are tested against; agreement with
+scikit-image's ``dilation`` / ``pyramid_reduce`` / ``warp`` has not been checked (DESIGN 3.17 says why, and lists the
+deviations).  ``Swelling``, ``Fracture`` and ``SetWidth`` are not built.
+
+  footprint  ``SetThickness`` dilates / erodes by a disk of 16 r made small again: the support of zoom(gaussian(disk(16 r),
+             16 / 3), (2 r + 1) / (32 r + 1), order 1).  The 16 is the reference's constant in ``_get_disk``, not the
+             image scale.  Every row of it is one centred run, so a footprint is its half widths.
+  reshape    flat dilation by the footprint (outside the image is background), or erosion, its dual on the image's own
+             pixels (outside the image does not constrain it).
+  shear      row y of the bitmap read at column x + floor(0.5 - delta (y - cy)): nearest neighbour, constant 0.
+  reduce     ``ImageMorphology.downscale``: quantise(RH bitmap RW^T) (morphomnist/morpho.py).
+  intensity  clip(q * (target / median), 0, 255), the median of the pixels of q in the upper half of its range.
+"""
+import functools
+
+import numpy as np
+from scipy import ndimage
+
+from .morpho import ImageMoments, ImageMorphology, intensity, quantise_levels, reduce, squared_distance
+
+DISK_SCALE = 16                  # the reference's ``_get_disk(radius, scale=16)``
+MAX_RADIUS = 64                  # the largest radius the kernels take (a 2049 x 2049 disk on the host, once)
+RADIUS_CAP = 2.0 ** 30           # a radius is reported up to here (status 3 long before)
+
+OK, NO_BACKGROUND, THIN_STUCK, RADIUS_TOO_LARGE, NOTHING_LEFT = 0, 1, 2, 3, 4
+
+
+def disk(k):
+    """x^2 + y^2 <= k^2: bool [2 k + 1, 2 k + 1]"""
+    y, x = np.mgrid[-k:k + 1, -k:k + 1]
+    return x * x + y * y <= k * k
+
+
+@functools.lru_cache(maxsize=None)
+def footprint(r):
+    """the structuring element of ``SetThickness`` for radius r: bool [2 r + 1, 2 r + 1], read-only.  scikit-image hands
+    the float disk to ``ndi.grey_dilation``, which casts it to bool: the support is the footprint."""
+    r = int(r)
+    if r == 0:
+        f = np.ones((1, 1), dtype=bool)
+    else:
+        big = ndimage.gaussian_filter(disk(DISK_SCALE * r).astype(np.float64), DISK_SCALE / 3, mode="reflect")
+        z = ndimage.zoom(big, (2 * r + 1) / (2 * DISK_SCALE * r + 1), order=1, mode="mirror", grid_mode=True)
+        f = z > 0
+    assert f.shape == (2 * r + 1, 2 * r + 1)
+    f.setflags(write=False)
+    return f
+
+
+@functools.lru_cache(maxsize=None)
+def half_widths(r):
+    """int64 [2 r + 1]: row dy of ``footprint(r)`` is the run of columns -h .. h around the centre, h = half_widths[dy]"""
+    f = footprint(r)
+    n = f.sum(1)
+    h = (n - 1) // 2
+    cols = np.arange(-int(r), int(r) + 1)
+    assert (n % 2 == 1).all() and (f == (np.abs(cols)[None, :] <= h[:, None])).all(), r   # one centred run, none empty
+    h.setflags(write=False)
+    return h
+
+
+def half_width_table(max_radius=MAX_RADIUS):
+    """int16 [max_radius + 1, 2 * max_radius + 1]: row r holds ``half_widths(r)`` in its first 2 r + 1 entries, -1 behind
+    them (what ``ali_morpho_reshape`` takes)"""
+    table = np.full((max_radius + 1, 2 * max_radius + 1), -1, dtype=np.int16)
+    for r in range(max_radius + 1):
+        table[r, :2 * r + 1] = half_widths(r)
+    return table
+
+
+def _row_dilate(bitmap, h):
+    """out(y, x) = any of bitmap(y, x - h .. x + h) inside the image"""
+    H, W = bitmap.shape
+    c = np.concatenate([np.zeros((H, 1), dtype=np.int64), np.cumsum(bitmap, axis=1, dtype=np.int64)], axis=1)
+    x = np.arange(W)
+    return c[:, np.minimum(x + h + 1, W)] - c[:, np.maximum(x - h, 0)] > 0
+
+
+def dilate(bitmap, r):
+    """flat dilation of a boolean image by ``footprint(r)``; outside the image is background"""
+    bitmap = np.asarray(bitmap, dtype=bool)
+    H, W = bitmap.shape
+    out = np.zeros((H, W), dtype=bool)
+    rows = {}
+    for k, h in enumerate(half_widths(r).tolist()):
+        dy = k - int(r)
+        if h not in rows:
+            rows[h] = _row_dilate(bitmap, h)
+        lo, hi = max(0, -dy), min(H, H - dy)                         # out rows y with 0 <= y + dy < H
+        if lo < hi:
+            out[lo:hi] |= rows[h][lo + dy:hi + dy]
+    return out
+
+
+def erode(bitmap, r):
+    """flat erosion by ``footprint(r)``; outside the image does not constrain it: ~dilate(~bitmap)"""
+    return ~dilate(~np.asarray(bitmap, dtype=bool), r)
+
+
+def signed_radius(thickness, target, scale):
+    """``SetThickness``'s radius with the sign of delta (dilate >= 0 > erode), formed in fp64 from the two values as
+    given: int(scale * |target - thickness| / 2), reported up to 2^30.  None for a NaN."""
+    delta = np.float64(target) - np.float64(thickness)
+    if np.isnan(delta):
+        return None
+    r = int(min(np.float64(scale) * abs(delta) / 2.0, RADIUS_CAP))
+    return r if delta >= 0 else -r
+
+
+def reshape(bitmap, radius):
+    """``dilate`` for radius >= 0, ``erode`` by -radius below"""
+    return dilate(bitmap, radius) if radius >= 0 else erode(bitmap, -radius)
+
+
+def moment_sums(bitmap):
+    """the six integer sums of a boolean image: count, sum x, sum y, sum x^2, sum x y, sum y^2 (int64 [6])"""
+    ys, xs = np.nonzero(bitmap)
+    return np.array([len(ys), xs.sum(), ys.sum(), (xs * xs).sum(), (xs * ys).sum(), (ys * ys).sum()], dtype=np.int64)
+
+
+def one_row(sums):
+    """u02 == 0: every set pixel lies in one row (count * sum y^2 == (sum y)^2, in integers)"""
+    n, _, sy, _, _, syy = (int(v) for v in sums)
+    return n * syy == sy * sy
+
+
+def horizontal_shear(sums):
+    """u11 / u02 of a bitmap from its integer sums, in fp64: bit for bit what ``ImageMoments(bitmap).horizontal_shear``
+    gives (its sums are integers below 2^53).  Returns (shear, cy)."""
+    n, sx, sy, _, sxy, syy = (np.float64(v) for v in sums)
+    m10, m01 = sx / n, sy / n
+    u11, u02 = sxy / n - m10 * m01, syy / n - m01 * m01
+    return u11 / u02, m01
+
+
+def shear_shifts(delta, cy, Hh, Wh):
+    """int64 [Hh]: floor(0.5 - delta * (y - cy)) in fp64 -- one subtraction, one product, one subtraction, one floor,
+    none fused -- held to -Wh .. Wh (a shift of Wh already reads outside the image everywhere)"""
+    y = np.arange(Hh, dtype=np.float64)
+    return np.clip(np.floor(np.float64(0.5) - np.float64(delta) * (y - np.float64(cy))), -Wh, Wh).astype(np.int64)
+
+
+def shift_rows(bitmap, shifts):
+    """out(y, x) = bitmap(y, x + shifts[y]), 0 outside the image"""
+    bitmap = np.asarray(bitmap, dtype=bool)
+    H, W = bitmap.shape
+    src = np.arange(W)[None, :] + np.asarray(shifts, dtype=np.int64)[:, None]
+    inside = (src >= 0) & (src < W)
+    return inside & bitmap[np.arange(H)[:, None], np.clip(src, 0, W - 1)]
+
+
+def set_intensity(q, target, dtype=np.float64):
+    """(clip(q * (target / median), 0, 255), median): the median of the pixels of q in the upper half of its range, the
+    factor and the product in ``dtype``"""
+    q = np.asarray(q, dtype=dtype)
+    median = dtype(intensity(q))
+    if target is None:
+        return q, median
+    return np.clip(q * (dtype(target) / median), 0, 255), median
+
+
+class Perturbation:
+    def __call__(self, morph):
+        """the perturbed hi-res image [H s, W s] of ``morph``; ``morph.downscale`` brings it back"""
+        raise NotImplementedError
+
+
+def _disk_erode(bitmap, radius):
+    """erosion by the exact ``disk(radius)``: d2 > r^2 (outside the image does not constrain it)"""
+    if bitmap.all():
+        return bitmap.copy()
+    return squared_distance(bitmap) > radius * radius
+
+
+class Thinning(Perturbation):
+    """thin a digit by ``amount`` of its thickness: erosion by the exact disk (host only)"""
+
+    def __init__(self, amount=.7):
+        self.amount = amount
+
+    def __call__(self, morph):
+        radius = int(self.amount * morph.scale * morph.mean_thickness / 2.)
+        return _disk_erode(morph.binary_image, radius)
+
+
+class Thickening(Perturbation):
+    """thicken a digit by ``amount`` of its thickness: dilation by the exact disk (host only)"""
+
+    def __init__(self, amount=1):
+        self.amount = amount
+
+    def __call__(self, morph):
+        radius = int(self.amount * morph.scale * morph.mean_thickness / 2.)
+        return ~_disk_erode(~morph.binary_image, radius)
+
+
+class SetThickness(Perturbation):
+    def __init__(self, target_thickness):
+        self.target_thickness = target_thickness
+
+    def __call__(self, morph):
+        radius = signed_radius(morph.mean_thickness, self.target_thickness, morph.scale)
+        if radius is None:
+            raise ValueError("SetThickness: the image has no thickness (no skeleton, or no background)")
+        return reshape(morph.binary_image, radius)
+
+
+class SetSlant(Perturbation):
+    """``transform.warp`` of the boolean image under the shear that brings its slant to the target: nearest neighbour,
+    constant 0, so a horizontal shift per row.  (scikit-image before 0.17 interpolated a bool image linearly: not
+    built.)"""
+
+    def __init__(self, target_slant_rad):
+        self.target_shear = -np.tan(np.float64(target_slant_rad))
+
+    def __call__(self, morph):
+        binary = morph.binary_image
+        delta = self.target_shear - ImageMoments(binary).horizontal_shear
+        return shift_rows(binary, shear_shifts(delta, ImageMoments(binary).m01, *binary.shape))
+
+
+class SetIntensity(Perturbation):
+    """as the reference has it, on top of ``downscale``: the median is the hi-res image's, the product the low-res one's"""
+
+    def __init__(self, target_intensity):
+        self.target_intensity = target_intensity
+
+    def __call__(self, morph):
+        mult = self.target_intensity / intensity(morph.hires_image)
+        return np.clip(morph.downscale(morph.hires_image) * mult, 0, 255)
+
+
+def reshape_stage(binary, thickness, target_thickness, scale, status=OK, max_radius=MAX_RADIUS):
+    """``SetThickness`` with its corners, as ``ali_morpho_reshape`` has it: (bitmap, signed radius, moment sums,
+    status); with a status the bitmap and the sums are 0, and the radius too unless the status is 3"""
+    zero, none = np.zeros(np.shape(binary), dtype=bool), np.zeros(6, dtype=np.int64)
+    if status:
+        return zero, 0, none, int(status)
+    radius = signed_radius(thickness, thickness if target_thickness is None else target_thickness, scale)
+    if radius is None:
+        return zero, 0, none, NOTHING_LEFT
+    if abs(radius) > max_radius:
+        return zero, radius, none, RADIUS_TOO_LARGE
+    reshaped = reshape(binary, radius)
+    sums = moment_sums(reshaped)
+    if sums[0] == 0 or one_row(sums):
+        return zero, radius, none, NOTHING_LEFT
+    return reshaped, radius, sums, OK
+
+
+def shear_stage(reshaped, sums, target_shear, scale, dtype=np.float64):
+    """``SetSlant`` and the reduce of a bitmap with status 0, as ``ali_morpho_shear_reduce`` has them: (u11 / u02,
+    shifts, warped bitmap, raw = 255 * reduce in ``dtype``, quantised).  ``target_shear`` = -tan(slant), or None."""
+    Hh, Wh = reshaped.shape
+    shear, cy = horizontal_shear(sums)
+    delta = np.float64(0) if target_shear is None else np.float64(target_shear) - shear
+    shifts = shear_shifts(delta, cy, Hh, Wh)
+    warped = shift_rows(reshaped, shifts)
+    raw = dtype(255) * reduce(warped, scale, dtype)
+    return shear, shifts, warped, raw, quantise_levels(raw)
+
+
+def continue_from(binary, thickness, H, W, target_thickness=None, target_shear=None, target_intensity=None, scale=16,
+                  status=OK, dtype=np.float64, max_radius=MAX_RADIUS):
+    """The chain from a binary image [H s, W s] and its measured thickness on (the tests hand it the device's own):
+    the dict of ``counterfactual_image``.  ``target_shear`` = -tan(slant)."""
+    Hh, Wh = H * scale, W * scale
+    out = dict(thickness=thickness, shear=np.float64("nan"), shifts=np.zeros(Hh, dtype=np.int64),
+               warped=np.zeros((Hh, Wh), dtype=bool), raw=np.zeros((H, W), dtype=dtype),
+               quantised=np.zeros((H, W), dtype=dtype), median=dtype("nan"), image=np.zeros((H, W), dtype=dtype))
+    out["reshaped"], out["radius"], out["sums"], out["status"] = reshape_stage(binary, thickness, target_thickness, scale,
+                                                                               status, max_radius)
+    if out["status"]:
+        return out
+    out["shear"], out["shifts"], out["warped"], out["raw"], q = shear_stage(out["reshaped"], out["sums"], target_shear,
+                                                                            scale, dtype)
+    if q.max() == 0:
+        out["status"] = NOTHING_LEFT
+        return out
+    out["quantised"] = q
+    out["image"], out["median"] = set_intensity(q, target_intensity, dtype)
+    return out
+
+
+def counterfactual_image(image, thickness=None, slant=None, intensity=None, scale=16, threshold=.5, seed=0,
+                         dtype=np.float64, max_radius=MAX_RADIUS):
+    """The scripts' chain for one image [H, W]:
+
+        morph   = ImageMorphology(im, scale=16)
+        new_img = np.float32(SetThickness(th)(morph))
+        new_img = morph.downscale(np.float32(SetSlant(sl)(ImageMorphology(new_img))))
+        cur     = np.median(new_img[new_img >= mn + (mx - mn) * .5])
+        new_img = np.clip(new_img * (in_ / cur), 0, 255)
+
+    ``thickness`` / ``slant`` / ``intensity`` of None: radius 0 / delta 0 / no rescale.  Returns a dict: ``image`` [H, W]
+    in 0 .. 255 and the intermediates -- ``thickness`` (measured), ``radius`` (signed), ``reshaped`` (the bitmap before
+    the shear), ``sums`` (its six integer moment sums), ``shear`` (its u11 / u02), ``shifts`` [H s], ``warped``, ``raw``
+    (255 * reduce), ``quantised``, ``median``, ``status``: 0, or 1 (no background) / 2 (thinning) as ``ImageMorphology``
+    has them, 3 for a radius above ``max_radius``, 4 when nothing is left to work with (no skeleton, erosion removed
+    every pixel, every pixel in one row, or the quantised image is 0 everywhere).  A non-zero status: ``image`` is 0."""
+    image = np.asarray(image, dtype=dtype)
+    H, W = image.shape
+    morph = ImageMorphology(image, threshold, scale, seed, dtype)
+    return continue_from(morph.binary_image, morph.mean_thickness, H, W, thickness,
+                         None if slant is None else -np.tan(np.float64(slant)), intensity, scale, morph.status, dtype,
+                         max_radius)

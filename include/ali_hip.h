@@ -716,6 +716,51 @@ int ali_morpho_measure(const float* x, int64_t ld, int32_t B, int32_t H, int32_t
                        const int32_t* d2, const int32_t* fg, const double* hstats, const int32_t* status,
                        int32_t* counts, float* values, float* slant_hires, ali_stream_t stream);
 
+/* The perturbation half of the family (morphomnist/perturb.py: SetThickness, SetSlant, ImageMorphology.downscale,
+ * SetIntensity -- the ground-truth counterfactual image of mnist_vae_measured_cf.py and the data-set builders), on the
+ * bitmaps and measures the four kernels above leave on the device.  Same layout, limits and workspace convention; one
+ * workgroup per image, integers and fixed-order fp64 sums, no atomics: the same inputs give the same bits on every run.
+ * Status values: 0; 1 and 2 as above; 3: the radius exceeds max_radius; 4: nothing left to work with (NaN thickness,
+ * no pixel left, every pixel in one row so that u02 == 0, or a quantised image that is 0 everywhere).  An image with a
+ * status != 0 passes through every later kernel as zeros, and keeps its status.
+ *
+ * ali_morpho_reshape: thickness: the measured thickness of image b at thickness[b * thickness_ld] (fp32, as
+ *   ali_morpho_measure wrote it: values + 2 with thickness_ld = 5); target [B] fp32 or NULL (radius 0).  delta =
+ *   (double)target - (double)thickness; radius = (int)min(scale * |delta| / 2, 2^30) in fp64, formed on the device;
+ *   radius[b] carries the sign of delta (written as 0 unless the status is 0 or 3).  half: DEVICE int16
+ *   [max_radius + 1][2 * max_radius + 1], row r = the half widths of the 2 r + 1 rows of the footprint of radius r
+ *   (every row one centred run of 2 h + 1 pixels); max_radius <= 64.  delta >= 0: out(y, x) = any pixel of bin within
+ *   the footprint around (y, x), outside the image being background; delta < 0: the same of the complement inside the
+ *   image, complemented (outside the image does not constrain the erosion).  Exact: the distance along the row to the
+ *   nearest set pixel goes to the workspace as uint16 and out(y, x) = any_dy hd(y + dy, x) <= half[dy].  sums [B][6]
+ *   int64 = { count, sum x, sum y, sum x^2, sum x y, sum y^2 } of out.  status_out = status_in, else 4 / 3 as above
+ *   (out and sums are then 0).  ws >= ALI_WS_RESERVED + 2 * B * Hh * Wh bytes.  LDS: 4 * 512 * 16 bytes.
+ * ali_morpho_shear_reduce: shear = u11 / u02 and cy = sum y / count from sums, in fp64 with every operation rounded on
+ *   its own; delta = target_shear[b] - shear (target_shear [B] fp64 = -tan(slant), or NULL: delta = 0); row y of bin is
+ *   read at column x + shift(y), shift(y) = floor(0.5 - delta * (y - cy)) held to -Wh .. Wh, 0 outside the image (the
+ *   shifts equal numpy's fp64 bit for bit).  T = warped RWt (fp64 sums over a row's set pixels in ascending x) goes to
+ *   the workspace, raw = 255 * RH T (fp64 sums in ascending y, rounded to fp32 once), q = floor(clip(raw, 0, 255) +
+ *   2^-7) in fp32.  RH [H][H * scale], RW [W][W * scale] DOUBLE, DEVICE row-major: the 1-D reduce operator of the
+ *   statement as it is (its rows have lobes of both signs; rounded to fp32 they would leave, where the lobes cancel,
+ *   the whole error of an fp32 product); scale == 1: they are not read and raw = 255 * warped.  q [B][H][W]; raw
+ *   [B][H][W] and shifts [B][H * scale] int32 are written when non-NULL; shear [B] fp64 (NaN with a status).  ws >=
+ *   ALI_WS_RESERVED + 8 * B * H * scale * W bytes when scale > 1.  LDS: 4 * 512 * 16 + 4 * 512 bytes.
+ * ali_morpho_set_intensity (a third launch: it is testable alone and takes any image, not only shear_reduce's): q [B][N]
+ *   fp32; median [B] = the median of the pixels of q that are >= min + (max - min) / 2, as ali_morpho_measure forms it;
+ *   out = clip(q * (target[b] / median), 0, 255), factor and product in fp32; target NULL: out = q.  An image whose
+ *   maximum is not above 0 gets status 4; with a status out is 0 and median NaN.  out must not overlap q (the median
+ *   is selected from q while other threads write out), nor may any output of the three overlap one of its inputs. */
+int ali_morpho_reshape(const uint32_t* bin, const float* thickness, int64_t thickness_ld, const float* target,
+                       const int32_t* status_in, const int16_t* half, int32_t max_radius, int32_t B, int32_t Hh,
+                       int32_t Wh, int32_t scale, uint32_t* out, int32_t* radius, int64_t* sums, int32_t* status_out,
+                       void* ws, size_t ws_bytes, ali_stream_t stream);
+int ali_morpho_shear_reduce(const uint32_t* bin, const int64_t* sums, const double* target_shear, const int32_t* status,
+                            int32_t B, int32_t H, int32_t W, int32_t scale, const double* RH, const double* RW,
+                            float* q, float* raw, int32_t* shifts, double* shear, void* ws, size_t ws_bytes,
+                            ali_stream_t stream);
+int ali_morpho_set_intensity(const float* q, const float* target, const int32_t* status_in, int32_t B, int32_t N,
+                             float* out, float* median, int32_t* status_out, ali_stream_t stream);
+
 /* Attribute plumbing of one batch (mnist.py:47-55, audio_mnist.py:203-210, whalecalls.py:455): idx[b*n_cat + j] =
  * argmax of categorical attribute j (one-hot rows of n_classes[j] floats, or int32 when cat_is_int[j]; first maximum
  * like torch.argmax); cont[b*n_cont + j] = cont_in[j][b]. */
