@@ -87,6 +87,40 @@ class PackCache:
                 self.store[key] = (self._tag(param), val, builder, param)
 
 
+def _refuse(i: int, m, why: str):
+    raise NotImplementedError(f"ali_hip.chain: layer {i} ({m.__class__.__name__}): {why}")
+
+
+def _check_layer(i: int, m):
+    """Refuses, at plan construction, every setting of layer ``i`` that the stages cannot represent: they carry one
+    stride / padding / output padding per convolution (``stride[0]`` ...), dense undilated zero-padded kernels, an
+    affine BatchNorm with a fixed momentum, an Unflatten of dim 1 and a Dropout2d that keeps something."""
+    if isinstance(m, (nn.Conv2d, nn.ConvTranspose2d)):
+        if isinstance(m.padding, str):
+            _refuse(i, m, f"padding={m.padding!r} (only explicit integer padding)")
+        for name in ("stride", "padding") + (("output_padding",) if isinstance(m, nn.ConvTranspose2d) else ()):
+            v = tuple(getattr(m, name))
+            if len(set(v)) != 1:
+                _refuse(i, m, f"{name}={v} (both entries must be equal)")
+        if tuple(m.dilation) != (1, 1):
+            _refuse(i, m, f"dilation={tuple(m.dilation)} (only 1)")
+        if m.groups != 1:
+            _refuse(i, m, f"groups={m.groups} (only 1)")
+        if m.padding_mode != "zeros":
+            _refuse(i, m, f"padding_mode={m.padding_mode!r} (only 'zeros')")
+    elif isinstance(m, nn.BatchNorm2d):
+        if m.momentum is None:
+            _refuse(i, m, "momentum=None (the cumulative moving average is not implemented)")
+        if not m.affine:
+            _refuse(i, m, "affine=False (the kernels read a weight and a bias)")
+    elif isinstance(m, nn.Unflatten):
+        if m.dim != 1:
+            _refuse(i, m, f"dim={m.dim} (only dim=1)")
+    elif isinstance(m, nn.Dropout2d) or m.__class__.__name__ in ("Dropout2d", "TapedDropout2d"):
+        if not 0.0 <= float(m.p) < 1.0:
+            _refuse(i, m, f"p={m.p} (outside [0, 1))")
+
+
 class ChainPlan:
     def __init__(self, seq: nn.Sequential):
         self.seq = weakref.ref(seq)          # the plan lives in a WeakKeyDictionary keyed by seq: no strong cycle
@@ -94,6 +128,8 @@ class ChainPlan:
         self.cache = PackCache()
         pre = []
         mods = list(seq)
+        for i, m in enumerate(mods):
+            _check_layer(i, m)
         i = 0
         flat = False          # an nn.Flatten() was seen: the Linear behind it is a "flat" stage
         while i < len(mods):
@@ -584,7 +620,7 @@ def _pre_ops(st: Stage, sv, bn_part, mask_applied: bool, groups: int):
     mask_in = mask if st.pattern == ["drop", "bn"] else None
     mask_post = mask if st.pattern == ["bn", "drop"] else None
     use_batch = sv.training or bn.running_mean is None
-    momentum = bn.momentum if bn.momentum is not None else 0.1
+    momentum = bn.momentum          # (never None: ChainPlan refuses the cumulative average)
     if bn_part is not None:
         stg = ops.bn_stats_from_partials(bn_part[0], bn_part[1], groups, Cp, (B // groups) * rows, bn.weight.detach(),
                                          bn.bias.detach(), bn.running_mean, bn.running_var, momentum, bn.eps)

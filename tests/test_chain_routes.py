@@ -10,7 +10,11 @@ and the ``if`` ladders of the two generators) -- not by running ``route``.
 A row is (kind, pre-op pattern, fwd, wgrad, wgrad_fold, dgrad, planes, fold_ok, bn_leave, bn_reduce): the stage's kind
 and the fields of its ``Route`` (``planes``: the form a single requested plane takes).  The second list of a chain is
 ``wgrad_geoms``: the (B,H,W,C,P,Q,K,R,S,stride,pad) that size the split of every deferred weight gradient -- the
-summation order, hence the bits, of the weight gradients depend on it."""
+summation order, hence the bits, of the weight gradients depend on it.
+
+This file only names routes.  The synthetic stacks -- ``SYNTHETIC`` here and ``chain_stacks.NEW_STACKS``, whose rows and
+stage shapes ``NEW_EXPECTED`` pins -- are RUN in tests/test_gpu_chain_stacks.py: ``run_chain`` on the device against
+fp64 autograd, forward, input gradient, parameter gradients and BatchNorm buffers."""
 import importlib
 
 import pytest
@@ -365,6 +369,40 @@ SYNTHETIC_EXPECTED = {
 }
 
 
+def _pre(row, pattern, **fields):
+    """``row`` with another pre-op pattern / other Route fields"""
+    from ali_hip.chain import Route
+    return (row[0], pattern) + tuple(Route(*row[2:])._replace(**fields))
+
+
+FIRST = _pre(CONV, [], planes='scatter')        # a first Conv2d with 4-aligned output channels and no BatchNorm in front
+
+# chain_stacks.NEW_STACKS: name -> (rows, [input shape, output shape of every stage]); derived by reading ``route``
+NEW_EXPECTED = {
+    "tanh_drop": ([_pre(FIRST, [], fold_ok=False), _pre(CONV, ['drop'])],
+                  [(3, 7, 6, 4), (3, 5, 4, 16), (3, 3, 3, 8)]),
+    "convT_bn_drop": ([CONVT, _pre(CONVT, ['bn', 'drop'], fold_ok=False)],
+                      [(3, 3, 4, 16), (3, 8, 10, 8), (3, 10, 12, 4)]),
+    "convT_drop_bn": ([CONVT, _pre(CONV, ['drop', 'bn'])],
+                      [(3, 3, 4, 16), (3, 8, 10, 8), (3, 6, 8, 12)]),
+    "bn_flat": ([FIRST, ('flat', ['bn'], 'conv', ('conv', 'fused'), ('conv', 'fused'), 'conv', None, True, False, True)],
+                [(5, 6, 5, 4), (5, 4, 3, 8), (5, 1, 1, 5)]),
+    "relu": ([FIRST, CONV, CONV],
+             [(3, 9, 8, 4), (3, 7, 6, 12), (3, 3, 2, 8), (3, 3, 2, 4)]),
+    "scatter_drop": ([('convT', [], 'scatter_gemm', ('convT', 'colsum'), ('convT', 'colsum'), 'convT', None, True, False, True),
+                      _pre(CONV, ['drop'])],
+                     [(3, 4, 5, 32), (3, 11, 13, 2), (3, 9, 11, 8)]),
+    "head_after_bn_drop": ([FIRST, ('conv', ['bn', 'drop'], 'head', ('head', 'fused'), ('head', 'fused'), 'conv', None,
+                                    True, True, True)],
+                           [(6, 1, 1, 8), (6, 1, 1, 16), (6, 1, 1, 1)]),
+    "bn_norun": ([FIRST, _pre(CONV, ['bn'])],
+                 [(3, 6, 5, 4), (3, 4, 3, 8), (3, 3, 2, 4)]),
+    "linear_unflat_bn": ([('linear', [], 'conv', ('linear_repack', 'unflat'), ('linear_repack', 'unflat'), 'conv', None,
+                           False, False, False), _pre(CONVT, ['bn'])],
+                         [(4, 1, 1, 12), (4, 2, 2, 12), (4, 5, 5, 4)]),
+}
+
+
 def _walk(seq, shape, c_log):
     """(rows, wgrad_geoms) of ``seq`` for an input of ``shape`` with ``c_log`` real channels, without running it"""
     from ali_hip import chain
@@ -406,6 +444,22 @@ def test_synthetic_stacks_reach_the_other_routes(name):
         seq = make()
     _, rows, geoms = _walk(seq, shape, c_log)
     assert (rows, geoms) == SYNTHETIC_EXPECTED[name]
+
+
+def test_new_stacks_keep_their_routes_and_shapes():
+    """the stacks test_gpu_chain_stacks.py adds to SYNTHETIC: Route rows (``_walk``) and stage shapes (``chain.trace``)"""
+    from ali_hip import chain
+    from chain_stacks import NEW_STACKS
+    assert sorted(NEW_STACKS) == sorted(NEW_EXPECTED)
+    for name, (make, shape, c_log) in NEW_STACKS.items():
+        with torch.device("meta"):
+            seq = make()
+        plan, rows, _ = _walk(seq, shape, c_log)
+        want_rows, want_shapes = NEW_EXPECTED[name]
+        assert rows == want_rows, name
+        traced = chain.trace(plan, shape, c_log)
+        assert [traced[0][0]] + [t[1] for t in traced] == want_shapes, name
+        assert [(st.kind, st.pattern) + tuple(t[2]) for st, t in zip(plan.stages, traced)] == want_rows, name
 
 
 def test_every_route_value_is_pinned_somewhere():
