@@ -135,6 +135,12 @@ SIGNATURES = {
                                    c_void_p, c_double, c_double, c_double, c_double, c_void_p, c_void_p]),
     "ali_cf_select": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                c_void_p]),
+    "ali_eg_input": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_uint64,
+                              POINTER(AliCfSegment), c_int32, POINTER(c_void_p), c_int32] + [c_int32] * 8
+                     + [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ali_eg_seed": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_double, c_void_p, c_void_p, c_void_p]),
+    "ali_eg_reduce": (c_int32, [c_void_p, c_int32, c_void_p, POINTER(AliCfSegment), c_int32, POINTER(c_void_p), c_int32]
+                      + [c_int32] * 6 + [c_void_p, c_void_p, c_size_t, c_void_p]),
     "ali_bce_logits_pair": (c_int32, [c_void_p, c_int32, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     "ali_gp_mix": (c_int32, [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_int32, c_int64, c_void_p,
                             c_void_p, c_void_p]),

@@ -1676,6 +1676,76 @@ def cf_select(logit, metric, target, pred=None, order=None, n_hit=None):
     return pred, order, n_hit
 
 
+# ---------------------------------------------------------------------- expected gradients (csrc/attrib.hip)
+def _eg_layout(lay: CfLayout, A, name):
+    if lay.attrs_ld > A or any(s[0] != CF_COPY for s in lay.segments):
+        raise ValueError(f"{name}: the layout must copy the columns of a [., {A}] attribute row (ALI_CF_COPY segments)")
+
+
+def eg_input(lay: CfLayout, latent, x, bg, S, n_draws, idx=None, t=None, z=None, seed=0, dev_counter=None, offset=0,
+             want_draws=False):
+    """Explained rows x [R, A] and background bg [Nb, A] -> (generator input rows [R*S*n_draws, ld], delta [R, S, A],
+    idx used [R, S] int32 or None, t used [R, S] or None) in one launch (include/ali_hip.h: ali_eg_input).  ``lay``: COPY
+    segments from attribute columns (src_off) to row columns (dst_off), z in the row's first ``latent`` columns.  idx
+    [R, S] int32, t [R, S], z [R, S, n_draws, latent]: given, or None: drawn under (seed, *dev_counter), ``offset``
+    explained rows in (``ali_hip.rng.eg_index_reference`` / ``eg_t_reference`` / ``normal_reference``)."""
+    lib = _lib.load()
+    if x.dim() != 2 or bg.dim() != 2 or bg.shape[1] != x.shape[1]:
+        raise ValueError(f"eg_input: need x [R, A] and bg [Nb, A], got {tuple(x.shape)} and {tuple(bg.shape)}")
+    R, A = x.shape
+    _eg_layout(lay, A, "eg_input")
+    S, n_draws, latent = int(S), int(n_draws), int(latent)
+    if idx is not None and tuple(idx.shape) != (R, S):
+        raise ValueError(f"eg_input: idx must be [{R}, {S}], got {tuple(idx.shape)}")
+    if t is not None and tuple(t.shape) != (R, S):
+        raise ValueError(f"eg_input: t must be [{R}, {S}], got {tuple(t.shape)}")
+    if z is not None and z.numel() != R * S * n_draws * latent:
+        raise ValueError(f"eg_input: z must hold [{R}, {S}, {n_draws}, {latent}] values, got {tuple(z.shape)}")
+    dev = x.device
+    rows = torch.empty(R * S * n_draws, lay.ld, dtype=torch.float32, device=dev)
+    delta = torch.empty(R, S, A, dtype=torch.float32, device=dev)
+    idx_out = torch.empty(R, S, dtype=torch.int32, device=dev) if want_draws else None
+    t_out = torch.empty(R, S, dtype=torch.float32, device=dev) if want_draws else None
+    _lib.check(lib.ali_eg_input(_chk(x, "x"), _chk(bg, "bg"), None if idx is None else _i32(idx, "idx", R * S),
+                                _opt(t, "t"), _opt(z, "z"), *_rng_args(seed, dev_counter, offset), lay._segs,
+                                len(lay.segments), lay._tabs, len(lay.tables), R, S, n_draws, bg.shape[0], A, latent,
+                                lay.n_log, lay.ld, _chk(rows), _chk(delta),
+                                None if idx_out is None else c_void_p(idx_out.data_ptr()), _opt(t_out), _stream()),
+               "ali_eg_input")
+    return rows, delta, idx_out, t_out
+
+
+def eg_seed(logit, c, scale, want_p=False, glogit=None):
+    """glogit [N, K] = scale * p_c * ((k == c) - p_k) of the rows' softmax p, and p itself when asked (include/ali_hip.h:
+    ali_eg_seed).  Returns (glogit, p or None)."""
+    lib = _lib.load()
+    if logit.dim() != 2:
+        raise ValueError(f"eg_seed: need [N, K] logits, got {tuple(logit.shape)}")
+    N, K = logit.shape
+    if glogit is None:
+        glogit = torch.empty_like(logit)
+    p = torch.empty_like(logit) if want_p else None
+    _lib.check(lib.ali_eg_seed(_chk(logit, "logit"), N, K, int(c), float(scale), _chk(glogit, "glogit"), _opt(p),
+                               _stream()), "ali_eg_seed")
+    return glogit, p
+
+
+def eg_reduce(lay: CfLayout, g_rows, delta, n_draws, phi, c):
+    """phi[:, c, :] ([R, C, A]) <- sum over (sample, draw) of delta [R, S, A] times the attribute gradient of the input
+    rows' gradient g_rows [R*S*n_draws, ld] (include/ali_hip.h: ali_eg_reduce); the other classes stay as they are."""
+    lib = _lib.load()
+    R, S, A = delta.shape
+    _eg_layout(lay, A, "eg_reduce")
+    if phi.dim() != 3 or phi.shape[0] != R or phi.shape[2] != A:
+        raise ValueError(f"eg_reduce: phi must be [{R}, C, {A}], got {tuple(phi.shape)}")
+    ws = workspace(delta.device)
+    _lib.check(lib.ali_eg_reduce(_rows(g_rows, lay.ld, "g_rows", R * S * int(n_draws)), lay.ld, _chk(delta, "delta"),
+                                 lay._segs, len(lay.segments), lay._tabs, len(lay.tables), R, S, int(n_draws), A,
+                                 phi.shape[1], int(c), _chk(phi, "phi"), c_void_p(ws.data_ptr()), ws.numel(), _stream()),
+               "ali_eg_reduce")
+    return phi
+
+
 # ---------------------------------------------------------------------- the counterfactual metrics (csrc/cfmetrics.hip)
 def mse(y, x, gscale=1.0, want_grad=True, tanh_out=False):
     """``mean((y - x)^2)`` over all elements as a 0-d device tensor, and its gradient with respect to ``y`` times

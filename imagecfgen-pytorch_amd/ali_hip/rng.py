@@ -1,6 +1,7 @@
 """The counter RNG of the HIP path on the host: the key schedule of csrc/ali_rng.h (the table there is the statement)
 and the references that reproduce a run's draws from (seed, counter, index) -- Dropout2d masks, latents, the WGAN-GP
-``eps``, Gumbel noise, Griffin-Lim phases and the tiebreak of the thinning order.  The integers are exact on both sides."""
+``eps``, Gumbel noise, Griffin-Lim phases, the tiebreak of the thinning order and the background rows and mixing weights
+of the expected-gradients estimator.  The integers are exact on both sides."""
 import numpy as np
 import torch
 
@@ -8,9 +9,10 @@ DEFAULT_Z_SEED, COUNTER_MUL = 0x5EED, 0xD1B54A32D192ED03
 LATENT_STREAM, GP_STREAM = 0x4C4154454E545A31, 0x47504D4958455053
 GUMBEL_STREAM, PHASE_STREAM = 0x47554D42454C3031, 0x474C504841534531
 THIN_STREAM = 0x5448494E4B455931
+EG_STREAM = 0x4547425249445831
 STREAMS = {"mask": (), "latent": (LATENT_STREAM,), "gp": (LATENT_STREAM, GP_STREAM),       # the tags mixed into the
            "gumbel": (LATENT_STREAM, GUMBEL_STREAM), "phase": (PHASE_STREAM,),               # base key, in order
-           "thin": (THIN_STREAM,)}
+           "thin": (THIN_STREAM,), "eg": (EG_STREAM,)}
 M64, TWO24 = (1 << 64) - 1, 16777216.0
 
 
@@ -106,3 +108,15 @@ def thin_reference(seed, n):
     """The tiebreaks of ``ali_morpho_thin(seed)`` for the pixels of linear index 0 .. n of an image: an int64 array [n],
     hi24 of hash i under the "thin" key of ``seed`` (no counter).  The same for every image of a batch."""
     return hi24(hashes(key(seed, None, "thin"), n))
+
+
+def eg_index_reference(seed, counter, n, n_background, offset=0):
+    """The background rows ``ali_eg_input(idx=NULL, seed, &counter, offset, ...)`` draws for (explained row, sample)
+    pairs ``offset .. offset + n`` (pair e = row * S + sample; the launcher's ``offset`` counts rows: pass ``offset *
+    S``): an int64 array [n] in [0, n_background), ``(hi24 * n_background) >> 24`` of hash e under the "eg" key.  Exact."""
+    return (hi24(hashes(key(seed, counter, "eg"), n, offset)) * int(n_background)) >> 24
+
+
+def eg_t_reference(seed, counter, n, offset=0):
+    """The mixing weights of the same pairs: a float32 CPU tensor [n] in [0, 1), lo24 / 2^24 of the same hash.  Exact."""
+    return torch.from_numpy((lo24(hashes(key(seed, counter, "eg"), n, offset)) / TWO24).astype(np.float32))

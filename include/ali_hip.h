@@ -486,6 +486,46 @@ int ali_cf_input_step(const float* g_rows, int32_t ld, const float* rows, const 
 int ali_cf_select(const float* logit, const float* metric, const int32_t* target, int32_t S, int32_t C, int32_t* pred,
                   int32_t* order, int32_t* n_hit, ali_stream_t stream);
 
+/* Expected gradients (Erion et al.) around the two conv chains: what shap.GradientExplainer(...).shap_values(a) does
+ * to f(a) = mean_z softmax(clf(decoder(z, a))) in morphomnist_attribute_shap.py (csrc/attrib.hip).  R explained rows
+ * x [R][A], background bg [Nb][A], S interpolated samples per row, n_draws latents per sample, C classes:
+ *   a[r,k] = t[r,k] x[r] + (1 - t[r,k]) bg[idx[r,k]],   delta[r,k] = x[r] - bg[idx[r,k]]
+ *   phi[r,c,:] = sum_k delta[r,k] * d/da[r,k] ( scale * sum_s softmax(clf(decoder(z[r,k,s], a[r,k])))_c ),
+ *   scale = 1 / (S * n_draws).
+ * ali_eg_input: (x, bg, idx, t, z) -> the generator's input rows and delta, one launch, one block per (r, k)
+ *   (morphomnist_attribute_shap.py:74-79,113-114: the repeat of the attribute columns, randn, and shap's interpolation).
+ *   rows [R*S*n_draws][ld] = [z | mixed categorical @ table | mixed continuous | 0], row ((r*S + k)*n_draws + s);
+ *   delta [R][S][A] = x - bg[idx], one fp32 subtraction.  The mix is the fp32 rounding of the fp64 expression above;
+ *   t == 0 gives bg[idx] and t == 1 gives x, bit for bit.  The segments are AliCfSegment entries (kind ALI_CF_COPY):
+ *   `width` attribute columns at src_off go to the row's columns dst_off.. (table < 0) or, times tables[table]
+ *   ([width][256], summed over the classes in ascending order), to its 256 columns at dst_off; attr_off is not read.
+ *   They must lie in [latent, n_log) and fill it.  A <= 1024.  idx [R][S] int32 (values are clamped into [0, Nb)),
+ *   t [R][S] and z [R][S][n_draws][latent] may each be NULL and are then drawn from the counter RNG under (seed,
+ *   *dev_counter), `offset` counting the explained rows in front of row 0 (so a call split into row ranges draws what
+ *   the whole call draws): idx = (hi24 * Nb) >> 24 and t = lo24 / 2^24 of hash (offset + r) * S + k under the "eg" key
+ *   (csrc/ali_rng.h), z element (((offset + r) * S + k) * n_draws + s) * latent + l of ali_normal_fill's stream.
+ *   idx_out / t_out (optional, [R][S]) receive the values used.
+ * ali_eg_seed: logits [N][K] and a class c -> glogit[n][k] = scale * p_c * ((k == c) - p_k), p the max-subtracted
+ *   softmax of the row, evaluated in fp64 and rounded once (the gradient of scale * softmax(.)_c that autograd seeds
+ *   through `.softmax(1)` and the mean, :81); p_out [N][K] (optional) receives p.  One thread per row: 1 <= K <= 1024.
+ * ali_eg_reduce: g_rows [R*S*n_draws][ld] (the gradient of the generator's input rows at class c) and delta ->
+ *   phi[r][c][:] ([R][C][A]; the other classes are not touched): the mean of (x - b) * grad over the samples behind
+ *   `vae_explainer.shap_values(a_expl)` (:124,126).  Attribute gradient of a row: g_rows[dst_off + i], or
+ *   <g_rows[dst_off .. dst_off + 256), tables[table][i]>; times delta[r][k][i], summed over (k, s) in fp64 in a fixed
+ *   order: rows of a 64-row chunk by wave (w, w + 4, ...), waves 0..3, chunks in order by the block that arrives last.
+ *   No float atomics: the same inputs give the same bits.  A <= 256; ws >= ALI_WS_RESERVED + 8 * R * A *
+ *   ceil(S * n_draws / 64) bytes; the arrival counter is the last int of the reserved head and is left at zero. */
+int ali_eg_input(const float* x, const float* bg, const int32_t* idx, const float* t, const float* z, uint64_t seed,
+                 const int64_t* dev_counter, uint64_t offset, const AliCfSegment* segs, int32_t n_seg,
+                 const float* const* tables, int32_t n_tables, int32_t R, int32_t S, int32_t n_draws, int32_t Nb,
+                 int32_t A, int32_t latent, int32_t n_log, int32_t ld, float* rows, float* delta, int32_t* idx_out,
+                 float* t_out, ali_stream_t stream);
+int ali_eg_seed(const float* logit, int64_t N, int32_t K, int32_t c, double scale, float* glogit, float* p_out,
+                ali_stream_t stream);
+int ali_eg_reduce(const float* g_rows, int32_t ld, const float* delta, const AliCfSegment* segs, int32_t n_seg,
+                  const float* const* tables, int32_t n_tables, int32_t R, int32_t S, int32_t n_draws, int32_t A,
+                  int32_t C, int32_t c, float* phi, void* ws, size_t ws_bytes, ali_stream_t stream);
+
 /* torch.optim.Adam step (mnist.py:176-179,230,236,241), no amsgrad / decay.
  * One launch over a flat parameter segment.  The 1-based step count is `step`, or *dev_step when
  * dev_step != NULL (graph replays); the gradient is read as grad_scale * g (1/world for DP).
