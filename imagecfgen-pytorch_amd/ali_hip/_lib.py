@@ -141,6 +141,13 @@ SIGNATURES = {
     "ali_eg_seed": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_double, c_void_p, c_void_p, c_void_p]),
     "ali_eg_reduce": (c_int32, [c_void_p, c_int32, c_void_p, POINTER(AliCfSegment), c_int32, POINTER(c_void_p), c_int32]
                       + [c_int32] * 6 + [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "ali_ct_attack": (c_int32, [c_void_p] + [c_int32] * 5 + [c_void_p, c_void_p, c_double, c_void_p, c_int32, c_void_p,
+                                                             c_void_p, c_void_p, c_void_p]),
+    "ali_ct_book": (c_int32, [c_void_p] * 5 + [c_int32, c_int32, c_int64] + [c_void_p] * 10),
+    "ali_ct_cem_update": (c_int32, [c_void_p, c_int32] + [c_void_p] * 7 + [c_int32, c_double, c_double, c_double, c_int32,
+                                                                          c_int64] + [c_void_p] * 5),
+    "ali_ct_ce_update": (c_int32, [c_void_p, c_int32] + [c_void_p] * 8 + [c_int32] + [c_double] * 6
+                         + [c_int32, c_int64, c_void_p, c_void_p, c_void_p]),
     "ali_bce_logits_pair": (c_int32, [c_void_p, c_int32, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     "ali_gp_mix": (c_int32, [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_int32, c_int64, c_void_p,
                             c_void_p, c_void_p]),

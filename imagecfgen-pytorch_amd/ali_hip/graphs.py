@@ -36,11 +36,16 @@ class _Graphed:
         ops.copy_multi([p for st, v in zip(self.inputs, inputs)
                         for p in ([(st[k], x) for k, x in v.items()] if isinstance(v, dict) else [(st, v)])])
 
+    def replay(self, n=1):
+        """``n`` more runs on the inputs as they stand (a caller whose state lives in the tensors the graph updates)"""
+        for _ in range(n):
+            for g in self.graphs:
+                g.replay()
+        return self.out
+
     def __call__(self, *inputs):
         self.load(inputs)
-        for g in self.graphs:
-            g.replay()
-        return self.out
+        return self.replay()
 
 
 def sig(v):
@@ -119,3 +124,7 @@ class GraphCache:
             ent.out = ent.capture(run, *ent.inputs)
             self.entries[key] = ent
         return ent(*present)
+
+    def replay(self, args, extra=(), n=1):
+        """``n`` more runs of the graph ``__call__`` recorded for ``(args' signatures, extra)``, on the inputs it holds"""
+        return self.entries[graph_key(args, extra)].replay(n)

@@ -1746,6 +1746,91 @@ def eg_reduce(lay: CfLayout, g_rows, delta, n_draws, phi, c):
     return phi
 
 
+# ---------------------------------------------------------------------- the contrastive family (csrc/contrast.hip)
+def _ct_f32(t, n, name):
+    if t.numel() != n:
+        raise ValueError(f"{name}: need {n} elements, got {tuple(t.shape)}")
+    return _chk(t, name)
+
+
+def ct_attack(logit, B, t0=None, c=None, kappa=0.0, eval_off=0, grad_off=0, seed_ld=None):
+    """Evaluation and attack seed of B search rows (include/ali_hip.h: ali_ct_attack): logit [R, C]; row eval_off + b is
+    evaluated (first arg-max, success against t0 [B] int32), row grad_off + b attacked under c [B] and ``kappa``.
+    Returns (seed [B, seed_ld], A [B], pred [B] int32, succ [B] int32); ``t0`` None: (None, None, pred, None)."""
+    lib = _lib.load()
+    if logit.dim() != 2:
+        raise ValueError(f"ct_attack: need [R, C] logits, got {tuple(logit.shape)}")
+    R, C = logit.shape
+    B = int(B)
+    dev = logit.device
+    pred = torch.empty(B, dtype=torch.int32, device=dev)
+    seed = A = succ = None
+    ld = C if seed_ld is None else int(seed_ld)
+    if t0 is not None:
+        seed = torch.empty(B, ld, dtype=torch.float32, device=dev)
+        A = torch.empty(B, dtype=torch.float32, device=dev)
+        succ = torch.empty(B, dtype=torch.int32, device=dev)
+    _lib.check(lib.ali_ct_attack(_chk(logit, "logit"), R, C, B, int(eval_off), int(grad_off),
+                                 None if t0 is None else _i32(t0, "t0", B), None if t0 is None else _ct_f32(c, B, "c"),
+                                 float(kappa), _opt(seed), ld, _opt(A), _i32(pred, "pred"),
+                                 None if succ is None else _i32(succ, "succ"), _stream()), "ali_ct_attack")
+    return seed, A, pred, succ
+
+
+def ct_book(v, dist, succ, pred, it, K, best, best_dist, best_label, found, round_succ, ctab, copied=None):
+    """Best-so-far and, at it == K, the binary search on c (include/ali_hip.h: ali_ct_book): v, best [B, N]; ctab
+    [3, B] = (c, c_lo, c_hi).  Returns copied [B] int32: the rows whose v went into best in this launch."""
+    lib = _lib.load()
+    B = v.shape[0]
+    N = v.numel() // B
+    if tuple(ctab.shape) != (3, B) or best.shape != v.shape:
+        raise ValueError(f"ct_book: v {tuple(v.shape)}, best {tuple(best.shape)} and ctab {tuple(ctab.shape)} (need "
+                         f"[3, {B}]) do not belong together")
+    if copied is None:
+        copied = torch.empty(B, dtype=torch.int32, device=v.device)
+    _lib.check(lib.ali_ct_book(_chk(v, "v"), _ct_f32(dist, B, "dist"), _i32(succ, "succ", B), _i32(pred, "pred", B),
+                               _i32(it, "it", B), int(K), B, N, _chk(best, "best"), _ct_f32(best_dist, B, "best_dist"),
+                               _i32(best_label, "best_label", B), _i32(found, "found", B),
+                               _i32(round_succ, "round_succ", B), _chk(ctab[0], "c"), _chk(ctab[1], "c_lo"),
+                               _chk(ctab[2], "c_hi"), _i32(copied, "copied", B), _stream()), "ali_ct_book")
+    return copied
+
+
+def _ct_gx(gx, B, N, name):
+    if gx.numel() % (B * N):
+        raise ValueError(f"{name}: gx {tuple(gx.shape)} is no [B, N, channels] gradient of {B} rows of {N} pixels")
+    return _chk(gx, "gx"), gx.numel() // (B * N)
+
+
+def ct_cem_update(gx, v, y, x0, lo, hi, it, rnd, K, lr, beta, clip, l1, l2, dist, gnorm):
+    """One FISTA step of the pertinent-negative search on every row, or the start of the next round where it == K
+    (include/ali_hip.h: ali_ct_cem_update): gx the classifier's input gradient at y ([B, N] or NHWC [B, H, W, Cpad],
+    plane 0), v / y / x0 [B, N], everything else [B].  In place."""
+    lib = _lib.load()
+    B = v.shape[0]
+    N = v.numel() // B
+    g, gs = _ct_gx(gx, B, N, "ct_cem_update")
+    _lib.check(lib.ali_ct_cem_update(g, gs, _chk(v, "v"), _ct_f32(y, B * N, "y"), _ct_f32(x0, B * N, "x0"),
+                                     _ct_f32(lo, B, "lo"), _ct_f32(hi, B, "hi"), _i32(it, "it", B), _i32(rnd, "rnd", B),
+                                     int(K), float(lr), float(beta), float(clip), B, N, _ct_f32(l1, B, "l1"),
+                                     _ct_f32(l2, B, "l2"), _ct_f32(dist, B, "dist"), _ct_f32(gnorm, B, "gnorm"),
+                                     _stream()), "ali_ct_cem_update")
+
+
+def ct_ce_update(gx, v, x0, lo, hi, m, v2, it, rnd, K, lr, gamma, clip, l1, gnorm, betas=(0.9, 0.999), eps=1e-8):
+    """One Adam step of the counterfactual search on every row, or the start of the next round where it == K
+    (include/ali_hip.h: ali_ct_ce_update): gx the classifier's input gradient at v, v / x0 / m / v2 [B, N].  In place."""
+    lib = _lib.load()
+    B = v.shape[0]
+    N = v.numel() // B
+    g, gs = _ct_gx(gx, B, N, "ct_ce_update")
+    _lib.check(lib.ali_ct_ce_update(g, gs, _chk(v, "v"), _ct_f32(x0, B * N, "x0"), _ct_f32(lo, B, "lo"),
+                                    _ct_f32(hi, B, "hi"), _ct_f32(m, B * N, "m"), _ct_f32(v2, B * N, "v2"),
+                                    _i32(it, "it", B), _i32(rnd, "rnd", B), int(K), float(lr), float(gamma), float(clip),
+                                    float(betas[0]), float(betas[1]), float(eps), B, N, _ct_f32(l1, B, "l1"),
+                                    _ct_f32(gnorm, B, "gnorm"), _stream()), "ali_ct_ce_update")
+
+
 # ---------------------------------------------------------------------- the counterfactual metrics (csrc/cfmetrics.hip)
 def mse(y, x, gscale=1.0, want_grad=True, tanh_out=False):
     """``mean((y - x)^2)`` over all elements as a 0-d device tensor, and its gradient with respect to ``y`` times

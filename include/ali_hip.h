@@ -526,6 +526,48 @@ int ali_eg_reduce(const float* g_rows, int32_t ld, const float* delta, const Ali
                   const float* const* tables, int32_t n_tables, int32_t R, int32_t S, int32_t n_draws, int32_t A,
                   int32_t C, int32_t c, float* phi, void* ws, size_t ws_bytes, ali_stream_t stream);
 
+/* The contrastive family (csrc/contrast.hip): the pertinent-negative search of the contrastive explanation method
+ * (Dhurandhar et al. 2018) and the counterfactual search of Wachter et al. 2017, B rows as B independent searches around
+ * the classifier's chain (DESIGN 3.19 has the statement).  Per row b: the image x0 [N], its label t0, the bounds lo / hi,
+ * the iterate v (and the slack y, or Adam's m / v2), the search constants c / c_lo / c_hi, the counters it (iteration
+ * of the round, 0..K) and rnd, the best so far.  Everything a launch branches on is read from device memory, so one
+ * recorded graph serves every iteration of every round; all four write with ordinary vector stores, reduce in a fixed
+ * order in fp64 (no float atomics: the same inputs give the same bits) and need no workspace.
+ * ali_ct_attack: logit [R][C], 2 <= C <= 1024, one thread per search row b < B.  Row eval_off + b is evaluated:
+ *   pred[b] = its first arg-max (ties to the first index, as ali_softmax_xent), succ[b] = pred[b] != t0[b].  Row
+ *   grad_off + b is attacked: own = s[t0], other = the largest s[j], j != t0 (first on ties), A[b] = max(0, own - other
+ *   + kappa) and seed[b][:] = c[b] * (e_t0 - e_other) where own - other + kappa > 0 (evaluated in fp64), else 0;
+ *   the columns [C, seed_ld) are 0: the gradient of the last stage's output as chain_backward takes it.
+ *   t0 == NULL: only pred is written (the labels of x0 themselves).
+ * ali_ct_book: one block per row, k = it[b].  k >= 1 and succ[b]: the round has a success; with dist[b] < best_dist[b]
+ *   the row v[b] is copied into best[b] (otherwise best is not written), best_dist / best_label (= pred[b]) follow and
+ *   found[b] = 1; copied[b] says whether that happened in this launch.  k == K closes the round: after a success
+ *   c_hi = min(c_hi, c), c = (c_lo + c_hi) / 2; otherwise c_lo = max(c_lo, c) and c = (c_lo + c_hi) / 2 if c_hi < 1e9
+ *   else 10 c; round_succ[b] = 0.  it is not written: the update that follows in the stream sees the same k.
+ * ali_ct_cem_update: one block per row.  k == K: v = y = x0, it = 0, rnd += 1, the distances 0.  k < K, with gx the
+ *   classifier's input gradient at y (element i of row b at gx[(b * N + i) * gx_stride]):
+ *     g = gx + 2 (y - x0);  norm = |g|_2 -> gnorm;  g *= clip / norm if norm > clip;  u = y - lr sqrt(1 - k / K) g
+ *     w = min(u - beta, hi) if u - x0 > beta, max(u + beta, lo) if u - x0 < -beta, else x0;  v' = w if w > x0 else x0
+ *     y' = v' + k / (k + 3) (v' - v), then x0 where y' <= x0;  l1 = |v' - x0|_1, l2 = |v' - x0|_2^2 of v' as stored,
+ *     dist = l2 + beta l1;  it = k + 1.  Pixels that fall back to x0, lo or hi receive those floats themselves.
+ * ali_ct_ce_update: one block per row.  k == K: v = x0, m = v2 = 0, it = 0, rnd += 1, l1 = 0.  k < K:
+ *     g = gx + gamma sign(v - x0) (sign(0) = 0), the same clip, Adam (torch.optim.Adam's formula) at step k + 1,
+ *     v' clamped to [lo, hi], l1 = |v' - x0|_1 of v' as stored, it = k + 1.
+ *   Rows of N % 4 == 0 floats in 16-byte aligned buffers move as 16-byte accesses.  N < 2^31, gx_stride in [1, 64]. */
+int ali_ct_attack(const float* logit, int32_t R, int32_t C, int32_t B, int32_t eval_off, int32_t grad_off,
+                  const int32_t* t0, const float* c, double kappa, float* seed, int32_t seed_ld, float* A, int32_t* pred,
+                  int32_t* succ, ali_stream_t stream);
+int ali_ct_book(const float* v, const float* dist, const int32_t* succ, const int32_t* pred, const int32_t* it,
+                int32_t K, int32_t B, int64_t N, float* best, float* best_dist, int32_t* best_label, int32_t* found,
+                int32_t* round_succ, float* c, float* c_lo, float* c_hi, int32_t* copied, ali_stream_t stream);
+int ali_ct_cem_update(const float* gx, int32_t gx_stride, float* v, float* y, const float* x0, const float* lo,
+                      const float* hi, int32_t* it, int32_t* rnd, int32_t K, double lr, double beta, double clip,
+                      int32_t B, int64_t N, float* l1, float* l2, float* dist, float* gnorm, ali_stream_t stream);
+int ali_ct_ce_update(const float* gx, int32_t gx_stride, float* v, const float* x0, const float* lo, const float* hi,
+                     float* m, float* v2, int32_t* it, int32_t* rnd, int32_t K, double lr, double gamma, double clip,
+                     double beta1, double beta2, double eps, int32_t B, int64_t N, float* l1, float* gnorm,
+                     ali_stream_t stream);
+
 /* torch.optim.Adam step (mnist.py:176-179,230,236,241), no amsgrad / decay.
  * One launch over a flat parameter segment.  The 1-based step count is `step`, or *dev_step when
  * dev_step != NULL (graph replays); the gradient is read as grad_scale * g (1/world for DP).
