@@ -28,10 +28,8 @@ decoder must be ``image_scms.mnist.Generator`` or derive from it (``deepscm_vae.
 import torch
 
 from . import ops, rng
-from .chain import chain_backward, chain_forward, get_plan, trace
-from .classify import nhwc_input
-from .explain import _check_classifier, _Decoder, _row_width
 from .graphs import GraphCache
+from .pipeline import DecodeClassify, LayoutCache, require_eval
 
 MNIST_SLICES = {"digit": (0, 10), "thickness": (10, 1), "intensity": (11, 1), "slant": (12, 1)}
 SAVED_BYTES_BUDGET = 8 << 30        # device memory one launch may hold: what the default ``rows_per_launch`` is sized by
@@ -110,10 +108,10 @@ class ExpectedGradients:
 
     def __init__(self, decoder, classifier, background, n_draws=4, nsamples=200, seed=0, capture=True,
                  rows_per_launch=None, attr_slices=None):
-        self.dec = _Decoder(decoder)
+        self.pipe = DecodeClassify(classifier, decoder)
+        self.dec = self.pipe.dec
         if self.dec.spect:
             raise TypeError("ExpectedGradients: SpectGenerator decoders are not supported")
-        _check_classifier(classifier)
         self.decoder, self.classifier = decoder, classifier
         self._check_eval()
         if attr_slices is None:
@@ -126,7 +124,7 @@ class ExpectedGradients:
                 attr_slices = dict(MNIST_SLICES)
         self.slices = {k: (int(o), int(w)) for k, (o, w) in attr_slices.items()}
         self.cat, self.cont = self.dec.keys(self.slices)
-        n_log, want = _row_width(self.dec, self.cat, self.cont)[0], self.dec.layers[0].in_channels
+        n_log, want = self.dec.row_width(self.cat, self.cont)[0], self.dec.layers[0].in_channels
         if n_log != want:
             raise ValueError(f"ExpectedGradients: the decoder takes the attributes of a {want}-column input row, "
                              f"{list(self.slices)} make {n_log}")
@@ -141,17 +139,14 @@ class ExpectedGradients:
         self.capture, self.rows_per_launch = capture, rows_per_launch
         self._graphs = GraphCache(modules=[decoder, classifier])
         self._value_graphs = GraphCache(modules=[decoder, classifier])
-        self._layout = None
+        self._layouts = LayoutCache(self.dec, self._forget)
         self._calls = 0             # calls that drew: the counter of the RNG key (on the device: ``_ctr``)
         self._ctr = None
         self._shape = None
 
     # ---- checks and input forms
     def _check_eval(self):
-        for name, m in (("decoder", self.decoder), ("classifier", self.classifier)):
-            if m.training:
-                raise ValueError(f"ExpectedGradients: the {name} is in training mode; the attributions are defined in "
-                                 "eval mode only (call .eval())")
+        require_eval("ExpectedGradients", decoder=self.decoder, classifier=self.classifier)
 
     def _rows(self, a):
         if isinstance(a, dict):
@@ -192,34 +187,30 @@ class ExpectedGradients:
         return idx, t, z
 
     # ---- the device path
+    def _forget(self):
+        """the embedding table moved: the recorded launches name the old layout's"""
+        self._graphs.clear()
+        self._value_graphs.clear()
+
     def _device_layout(self, device):
-        tables = self.dec.tables(self.cat)
-        lay = self._layout
-        if lay is not None and all(a.data_ptr() == b.data_ptr() for a, b in zip(lay.tables, tables)):
-            return lay
+        return self._layouts.get(None, self._build_layout)
+
+    def _build_layout(self):
         L = self.dec.latent()
-        n_log, ld = _row_width(self.dec, self.cat, self.cont)
         segs = []
         for k, (o, w) in self.slices.items():
             if k in self.cat:
                 segs.append((ops.CF_COPY, w, o, L + ops.CF_EMB * self.cat.index(k), self.cat.index(k), o))
             else:
                 segs.append((ops.CF_COPY, w, o, L + ops.CF_EMB * len(self.cat) + self.cont.index(k), -1, o))
-        self._graphs.clear()        # (recorded launches name the old layout's tables)
-        self._value_graphs.clear()
-        self._layout = ops.CfLayout(segs, tables, n_log, ld)
-        return self._layout
+        lay = ops.CfLayout(segs, self.dec.tables(self.cat), *self.dec.row_width(self.cat, self.cont))
+        lay.cat = self.cat
+        return lay
 
     def _shapes(self, lay):
         """(classes C, bytes of saved activations per generator-input row): from the two plans, no launch"""
         if self._shape is None:
-            H, W = self.dec.image_hw()
-            tG = trace(get_plan(self.dec.layers), (1, 1, 1, lay.ld), lay.n_log)
-            tC = trace(get_plan(self.classifier), (1, H, W, 4), 1)
-            numel = lambda s: s[0] * s[1] * s[2] * s[3]  # noqa: E731
-            # every stage keeps its input and its output; a stage's input is the output of the one before
-            saved = sum(numel(t[0][0]) + sum(numel(o) for _, o, _ in t) for t in (tG, tC))
-            self._shape = (tC[-1][1][3], 4 * saved)
+            self._shape = self.pipe.shapes(lay.n_log, lay.ld)
         return self._shape
 
     def default_rows_per_launch(self, lay):
@@ -236,23 +227,14 @@ class ExpectedGradients:
         R, N = x.shape[0], S * nd
         C = self._shapes(lay)[0]
         rows, delta, _, _ = ops.eg_input(lay, self.dec.latent(), x, self.bg, S, nd, idx, t, z, self.seed, self._ctr, r0)
-        pG, pC = get_plan(self.dec.layers), get_plan(self.classifier)
-        H, W = self.dec.image_hw()
         phi = torch.zeros(R, C, self.A, dtype=torch.float32, device=x.device)
         # The chains take one explained row (its S * n_draws input rows) per pass: the GEMMs pick their tiles and their
         # split by the batch, so a row's bits would otherwise depend on the rows it shares a launch with
         for r in range(R):
-            xg, sG = chain_forward(pG, rows[r * N:(r + 1) * N].reshape(N, 1, 1, lay.ld), False, lay.n_log, True)
-            logits, sC = chain_forward(pC, nhwc_input(xg.reshape(N, 1, H, W)), False, 1, True)
-            lg, xc = logits.reshape(N, -1), xg.reshape(N, -1)
-            for c in classes:
-                glogit, _ = ops.eg_seed(lg, c, 1.0 / N)
-                gx, _ = chain_backward(pC, sC, glogit.reshape(logits.shape), 1, True, need_params=False)
-                # plane 0 of the classifier's NHWC input gradient: ali_cf_join with x = x_cf, whose distance term is
-                # sign(0) = 0
-                gy = ops.cf_join(gx.contiguous(), xc, xc)
-                g_rows, _ = chain_backward(pG, sG, gy.reshape(xg.shape), lay.n_log, True, need_params=False)
-                ops.eg_reduce(lay, g_rows.reshape(N, lay.ld), delta[r:r + 1], nd, phi[r:r + 1], c)
+            x_cf, logits, saved = self.pipe.forward(rows[r * N:(r + 1) * N], lay.n_log, True)
+            for c in classes:                   # (each from the one saved state; no distance term in the row gradient)
+                glogit, _ = ops.eg_seed(logits, c, 1.0 / N)
+                ops.eg_reduce(lay, self.pipe.row_grad(saved, glogit, x_cf), delta[r:r + 1], nd, phi[r:r + 1], c)
         return phi
 
     def _advance(self):
@@ -301,12 +283,8 @@ class ExpectedGradients:
         ones = torch.ones(R, 1, dtype=torch.float32, device=x.device)
         # t = 1 against the rows themselves as background: the attribute part is x, bit for bit
         rows, _, _, _ = ops.eg_input(lay, self.dec.latent(), x, x, 1, nd, rows_idx, ones, z, self.seed, self._ctr, 0)
-        N = rows.shape[0]
-        pG, pC = get_plan(self.dec.layers), get_plan(self.classifier)
-        xg, _ = chain_forward(pG, rows.reshape(N, 1, 1, lay.ld), False, lay.n_log, False)
-        H, W = self.dec.image_hw()
-        logits, _ = chain_forward(pC, nhwc_input(xg.reshape(N, 1, H, W)), False, 1, False)
-        _, p = ops.eg_seed(logits.reshape(N, -1), 0, 1.0, want_p=True)
+        _, logits, _ = self.pipe.forward(rows, lay.n_log)
+        _, p = ops.eg_seed(logits, 0, 1.0, want_p=True)
         return p.reshape(R, nd, -1).mean(dim=1)
 
     @torch.no_grad()

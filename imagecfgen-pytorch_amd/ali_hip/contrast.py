@@ -32,10 +32,8 @@ import math
 import torch
 
 from . import ops
-from .chain import chain_backward, chain_forward, get_plan, saved_rows
-from .classify import nhwc_input
-from .explain import _check_classifier
 from .graphs import GraphCache
+from .pipeline import DecodeClassify, require_eval
 
 PN_DEFAULTS = dict(c0=10.0, beta=0.1, kappa=10.0, binary_search_steps=5, learning_rate=1e-2, num_iterations=1000,
                    grad_clip=1e3)
@@ -209,7 +207,7 @@ class ContrastiveSearch:
     use (2B rows for "pn", B for "ce").  ``start`` / ``advance`` / ``result`` are ``run`` in pieces (tests, inspection)."""
 
     def __init__(self, classifier, mode="pn", capture=True, bounds=None, **hyper):
-        _check_classifier(classifier)
+        self.pipe = DecodeClassify(classifier)
         self.classifier, self.mode, self.capture = classifier, mode, capture
         self.hp = hyper_parameters(mode, hyper)
         self.bounds = None if bounds is None else (float(bounds[0]), float(bounds[1]))
@@ -222,9 +220,7 @@ class ContrastiveSearch:
         self._cur = None
 
     def _check_eval(self):
-        if self.classifier.training:
-            raise ValueError("ContrastiveSearch: the classifier is in training mode; the search is defined in eval "
-                             "mode only (call .eval())")
+        require_eval("ContrastiveSearch", classifier=self.classifier)
 
     @property
     def replays_per_search(self):
@@ -259,19 +255,15 @@ class ContrastiveSearch:
         B, N, hp, pn = st["B"], st["N"], self.hp, self.mode == "pn"
         rows = st["rows"]
         R = rows.shape[0]
-        plan = get_plan(self.classifier)
-        logits, saved = chain_forward(plan, nhwc_input(rows), False, 1, True)
-        lg = logits.reshape(R, -1)
+        lg, saved = self.pipe.classify(rows, save=True)
         flat = rows.reshape(R, N)
         v = flat[:B]
         seed, A, pred, succ = ops.ct_attack(lg, B, t0, st["ctab"][0], hp["kappa"], 0, B if pn else 0)
         dist = st["dist"] if pn else st["l1"]
         ops.ct_book(v, dist, succ, pred, st["it"], hp["num_iterations"], st["best"], st["best_dist"], st["best_label"],
                     st["found"], st["round_succ"], st["ctab"], st["copied"])
-        if pn:          # the slack rows alone: rows of a stack without BatchNorm are independent
-            saved = saved_rows(saved, B, 2 * B)
-        gx, _ = chain_backward(plan, saved, seed.reshape((B,) + tuple(logits.shape[1:])), 1, True, need_params=False)
-        gx = gx.contiguous()
+        # "pn": the slack rows alone -- rows of a stack without BatchNorm are independent
+        gx = self.pipe.image_grad(saved, seed, rows=(B, 2 * B) if pn else None)
         if pn:
             ops.ct_cem_update(gx, v, flat[B:], x0, lo, hi, st["it"], st["rnd"], hp["num_iterations"],
                               hp["learning_rate"], hp["beta"], hp["grad_clip"], st["l1"], st["l2"], st["dist"],
@@ -304,8 +296,8 @@ class ContrastiveSearch:
         rows.copy_(x0.reshape(B, 1, H, W).repeat(R // B, 1, 1, 1))
         # t0 from a pass of the batch shape the replays evaluate their iterates in: a row's logits depend on the
         # batch size in the last bits, and an iterate still at x0 must not count as a success by rounding alone
-        logits, _ = chain_forward(get_plan(self.classifier), nhwc_input(rows), False, 1, True)   # (as a replay's)
-        _, _, t0, _ = ops.ct_attack(logits.reshape(R, -1), B)
+        logits, _ = self.pipe.classify(rows, save=True)                                          # (as a replay's)
+        _, _, t0, _ = ops.ct_attack(logits, B)
         st["t0"].copy_(t0)
         st["ctab"][0].fill_(self.hp["c0"])
         st["ctab"][1].zero_()

@@ -17,66 +17,8 @@ construction (``explain/cf_example.py`` then runs the torch statement of the loo
 import torch
 
 from . import ops, ssim as _ssim
-from .chain import chain_backward, chain_forward, get_plan
-from .classify import nhwc_input
-from .graphs import GraphCache, graph_key
-
-
-class _Decoder:
-    """What the executors need of a generator stack: its layers' plan, the embedding tables, and which attribute goes
-    where in the input row ``[z | attribute @ table ... | continuous ... | 0]``."""
-
-    def __init__(self, G):
-        from image_scms._spect import SpectGenerator
-        from image_scms.mnist import Generator
-        self.G = G
-        if isinstance(G, Generator):
-            self.spect = False
-        elif isinstance(G, SpectGenerator):
-            self.spect = True
-        else:
-            raise TypeError(f"explain: {type(G).__name__} is not one of this package's generator stacks")
-        self.layers = G.layers
-
-    def keys(self, attrs):
-        """(table keys, continuous keys) in the order of the input row"""
-        if self.spect:
-            cat = list(self.G.cat_keys)
-            cont = [self.G.cont_key] if self.G.cont_key is not None else []
-        else:
-            from image_scms.mnist import _cont_keys
-            cat, cont = ["digit"], list(_cont_keys(attrs))
-        if set(cat + cont) != set(attrs):
-            raise ValueError(f"explain: the decoder takes the attributes {cat + cont}, got {list(attrs)}")
-        return cat, cont
-
-    def tables(self, cat):
-        if self.spect:
-            return [self.G.table(k).weight.detach() for k in cat]
-        return [self.G.digit_embedding.weight.detach()]
-
-    def latent(self):
-        if self.spect:
-            from image_scms._spect import LATENT_DIM
-        else:
-            from image_scms.mnist import LATENT_DIM
-        return LATENT_DIM
-
-    def image_hw(self):
-        if self.spect:
-            return tuple(self.G.image_hw)
-        return (28, 28)
-
-
-def _check_classifier(clf):
-    from classifiers._stack import ClassifierStack
-    if not isinstance(clf, ClassifierStack):
-        raise TypeError(f"explain: {type(clf).__name__} is not a ClassifierStack")
-
-
-def _row_width(dec, cat, cont):
-    n_log = dec.latent() + ops.CF_EMB * len(cat) + len(cont)
-    return n_log, n_log + (-n_log) % 32
+from .graphs import GraphCache
+from .pipeline import DecodeClassify, LayoutCache
 
 
 class HingeCFStepper:
@@ -94,8 +36,8 @@ class HingeCFStepper:
 
     def __init__(self, decoder, classifier, target_feature, categorical_features=None, features_to_ignore=None, c=10.0,
                  capture=True, betas=(0.9, 0.999), eps=1e-8):
-        self.dec = _Decoder(decoder)
-        _check_classifier(classifier)
+        self.pipe = DecodeClassify(classifier, decoder)
+        self.dec = self.pipe.dec
         self.decoder, self.classifier = decoder, classifier
         self.target_feature = target_feature
         self.categorical = list(categorical_features or [])
@@ -103,21 +45,23 @@ class HingeCFStepper:
         self.c, self.capture, self.betas, self.eps = float(c), capture, betas, eps
         self._graphs = GraphCache(modules=[decoder, classifier])           # the step: one graph per input signature
         self._final_graphs = GraphCache(modules=[decoder, classifier])     # the closing forward
-        self._layouts = {}
-        self._retired = []          # layouts of replaced tables: their ids stay taken while graphs may name them
         self._state = {}
+        self._layouts = LayoutCache(self.dec, self._forget)
+
+    def _forget(self):
+        """the embedding tables moved: nothing recorded or keyed under a layout's id is valid any more"""
+        self._graphs.clear()
+        self._final_graphs.clear()
+        self._state.clear()
 
     # ---- the segment table of one attribute signature
     def layout(self, attrs, trained_z):
         key = (tuple((k, v.shape[1]) for k, v in attrs.items()), trained_z)
-        lay = self._layouts.get(key)
-        if lay is not None and all(a.data_ptr() == b.data_ptr() for a, b in zip(lay.tables, self.dec.tables(lay.cat))):
-            return lay
-        if lay is not None:
-            self._retired.append(lay)
+        return self._layouts.get(key, lambda: self._build_layout(attrs, trained_z))
+
+    def _build_layout(self, attrs, trained_z):
         dec = self.dec
         cat, cont = dec.keys(attrs)
-        n_log, ld = _row_width(dec, cat, cont)
         L = dec.latent()
         segs, raw_off, given_off, attr_off = [], 0, 0, 0
         where = {"raw": {}, "given": {}, "attr": {}}
@@ -146,11 +90,10 @@ class HingeCFStepper:
         else:
             segs.append((ops.CF_COPY, L, given_off, 0, -1, -1))
             where["given"]["z"] = (given_off, L)
-        lay = ops.CfLayout(segs, dec.tables(cat), n_log, ld)
+        lay = ops.CfLayout(segs, dec.tables(cat), *dec.row_width(cat, cont))
         lay.cat, lay.where = cat, where
         if lay.raw_ld == 0:
             raise ValueError("explain: nothing to optimise (every attribute is ignored and z is not trained)")
-        self._layouts[key] = lay
         return lay
 
     def _buffers(self, lay, B, device):
@@ -164,33 +107,20 @@ class HingeCFStepper:
         return st
 
     # ---- one step and the closing forward: what the graphs record
-    def _forward(self, lay, st, given, save):
-        rows, attrs = ops.cf_input_fwd(lay, st["raw"], given)
-        B = rows.shape[0]
-        pG, pC = get_plan(self.dec.layers), get_plan(self.classifier)
-        xg, sG = chain_forward(pG, rows.reshape(B, 1, 1, lay.ld), self.decoder.training, lay.n_log, save)
-        H, W = self.dec.image_hw()
-        x_cf = xg.reshape(B, 1, H, W)
-        return rows, attrs, x_cf, (sG, xg.shape), pG, pC
-
     def _step(self, lay, st, lr, x, given, target, orig_pred):
-        rows, attrs, x_cf, (sG, g_shape), pG, pC = self._forward(lay, st, given, True)
-        B = rows.shape[0]
-        logits, sC = chain_forward(pC, nhwc_input(x_cf), self.classifier.training, 1, True)
-        xc = x_cf.reshape(B, -1)
-        m = ops.row_dist(x, xc, ops.DIST_L1)
-        out3, glogit = ops.cf_hinge(logits.reshape(B, -1), target, m, self.c, orig_pred=orig_pred)
-        gx, _ = chain_backward(pC, sC, glogit.reshape(logits.shape), 1, True, need_params=False)
-        gy = ops.cf_join(gx.contiguous(), xc, x)
-        g_rows, _ = chain_backward(pG, sG, gy.reshape(g_shape), lay.n_log, True, need_params=False)
-        ops.cf_input_step(lay, g_rows.reshape(B, lay.ld), rows, attrs, st["raw"], st["m"], st["v"], st["step"], lr,
-                          self.betas, self.eps, graw=st["graw"])
-        st["probe"] = {"logits": logits.reshape(B, -1), "glogit": glogit, "x_cf": x_cf, "m": m}   # (tests, inspection)
+        rows, attrs = ops.cf_input_fwd(lay, st["raw"], given)
+        x_cf, logits, saved = self.pipe.forward(rows, lay.n_log, True)
+        m = ops.row_dist(x, x_cf.reshape(rows.shape[0], -1), ops.DIST_L1)
+        out3, glogit = ops.cf_hinge(logits, target, m, self.c, orig_pred=orig_pred)
+        g_rows = self.pipe.row_grad(saved, glogit, x_cf, x)
+        ops.cf_input_step(lay, g_rows, rows, attrs, st["raw"], st["m"], st["v"], st["step"], lr, self.betas, self.eps,
+                          graw=st["graw"])
+        st["probe"] = {"logits": logits, "glogit": glogit, "x_cf": x_cf, "m": m}                  # (tests, inspection)
         return out3
 
     def _final(self, lay, st, given):
-        _, attrs, x_cf, _, _, _ = self._forward(lay, st, given, False)
-        return x_cf, attrs
+        rows, attrs = ops.cf_input_fwd(lay, st["raw"], given)
+        return self.pipe.generate(rows, lay.n_log)[0], attrs
 
     @torch.no_grad()
     def run(self, x, attrs, codes, target=None, init=None, steps=30, lr=0.1, train_z=True, update_z=False):
@@ -237,10 +167,7 @@ class HingeCFStepper:
             args, extra = (xf, given, target, orig_pred), where + (float(lr),)
             if steps > 0:
                 out3 = self._graphs(lambda *a: self._step(lay, st, lr, *a), args, extra, state)
-                ent = self._graphs.entries[graph_key(args, extra)]        # the inputs are in place: replay only
-                for _ in range(steps - 1):
-                    for g in ent.graphs:
-                        g.replay()
+                self._graphs.replay(args, extra, steps - 1)               # the inputs are in place: replay only
             x_cf, attrs_cf = self._final_graphs(lambda g_: self._final(lay, st, g_), (given,), where)
         if out3 is None:
             out3 = torch.full((B, 3), float("nan"), device=dev)
@@ -272,8 +199,8 @@ class MixtureSweep:
     METRICS = ("mixture", "mse", "ssim")
 
     def __init__(self, decoder, classifier, target_feature, capture=True):
-        self.dec = _Decoder(decoder)
-        _check_classifier(classifier)
+        self.pipe = DecodeClassify(classifier, decoder)
+        self.dec = self.pipe.dec
         self.decoder, self.classifier = decoder, classifier
         self.target_feature = target_feature
         self.capture = capture
@@ -291,11 +218,9 @@ class MixtureSweep:
     def _sweep(self, S, metric, x, codes, attrs, target, orig):
         dec = self.dec
         cat, cont = dec.keys(attrs)
-        n_log, ld = _row_width(dec, cat, cont)
-        pG, pC = get_plan(dec.layers), get_plan(self.classifier)
+        n_log, ld = dec.row_width(cat, cont)
         if orig is None:
-            lx, _ = chain_forward(pC, nhwc_input(x), self.classifier.training, 1, False)
-            lx = lx.reshape(1, -1)
+            lx, _ = self.pipe.classify(x)
             _, _, orig = ops.softmax_xent(lx, lx, want_grad=False, want_pred=True)
         p, eye = self._constants(S, attrs[self.target_feature].shape[1], x.device)
         e_orig = eye.index_select(0, orig.long())
@@ -306,17 +231,13 @@ class MixtureSweep:
         z = codes.reshape(1, -1).float().expand(S, -1).contiguous()
         cvals = torch.cat([rep[k] for k in cont], dim=1).contiguous() if cont else None
         rows = ops.g_input(z, [rep[k].contiguous() for k in cat], dec.tables(cat), cvals, ld)
-        xs, _ = chain_forward(pG, rows.reshape(S, 1, 1, ld), self.decoder.training, n_log, False)
-        H, W = dec.image_hw()
-        samples = xs.reshape(S, 1, H, W)
-        logits, _ = chain_forward(pC, nhwc_input(samples), self.classifier.training, 1, False)
-        logits = logits.reshape(S, -1)
+        samples, logits, _ = self.pipe.forward(rows, n_log)
         if metric == "mixture":
             mval = p.reshape(S).clone()
         elif metric == "mse":
             mval = ops.row_dist(x.reshape(1, -1).float().contiguous(), samples.reshape(S, -1), ops.DIST_L2)
         else:
-            xv = x.float().expand(S, 1, H, W).contiguous()
+            xv = x.float().expand(samples.shape).contiguous()
             mval = (1 - _ssim.ssim((xv + 1) / 2, (samples + 1) / 2, data_range=1.0, size_average=False)).contiguous()
         pred, order, n_hit = ops.cf_select(logits, mval, target)
         return {"samples": samples, "metric": mval, "pred": pred, "order": order, "n_hit": n_hit, "logits": logits,
