@@ -212,6 +212,7 @@ SIGNATURES = {
                          + [c_void_p]),
     "ali_tconv1_wgrad": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int64, c_int64, c_int64]
                          + [c_int32] * 7 + [c_void_p, c_size_t, c_void_p]),
+    "ali_tconv1_route": (c_int32, [c_int32] * 9 + [c_size_t]),
     "ali_ssim_fwd": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int32, c_float, c_float,
                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "ali_ssim_bwd": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32,

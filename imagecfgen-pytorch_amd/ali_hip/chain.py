@@ -408,13 +408,24 @@ def route(st: Stage, in_shape, c_log: int) -> Route:
         return Route("flat_gemm", ("flat_repack", None if m.bias is None else "colsum"),
                      ("flat_repack", None if m.bias is None else "colsum"), dgrad="flat_gemm", planes=None,
                      fold_ok=st.act in (ACT_NONE, ACT_LEAKY), bn_leave=False, bn_reduce=False)
-    # ConvTranspose2d(C -> 1), stride 1, no output padding: served by the direct one-channel kernels
+    # ConvTranspose2d(C -> 1), stride 1, no output padding: served by the direct one-channel kernels -- when all three
+    # of them take the shape (ops.tconv1_route: the launches' own plan; e.g. no 128 channels x 16 taps, whose weight
+    # gradient needs more accumulators than a thread has, and no rectangular kernel, which the forward refuses)
     tconv1 = (st.kind == "convT" and m.out_channels == 1 and m.stride[0] == 1 and m.output_padding[0] == 0
               and m.kernel_size[0] <= 5 and Cp in (32, 64, 128, 256))
-    # first Conv2d of a stack (<= 8 real input channels, stride 1): per-channel direct weight gradient and single-plane
-    # data gradient (ali_tconv1_*)
-    first_direct = (st.index == 0 and st.kind == "conv" and m.stride[0] == 1 and c_log <= 8
-                    and m.out_channels in (32, 64, 128, 256) and m.kernel_size[0] <= 5)
+    if tconv1:
+        big = (in_shape[0], in_shape[1], in_shape[2], Cp, *m.kernel_size, m.padding[0])
+        tconv1 = all(ops.tconv1_route(op, *big) is not None for op in ("fwd", "dgrad", "wgrad"))
+    # first Conv2d of a stack (<= 8 real input channels, stride 1): per-channel direct weight gradient (ali_tconv1_wgrad
+    # with the output gradient as the many-channel map) and single-plane data gradient (ali_tconv1_fwd), each when
+    # its launch takes the shape
+    first_direct = first_planes = (st.index == 0 and st.kind == "conv" and m.stride[0] == 1 and c_log <= 8
+                                   and m.out_channels in (32, 64, 128, 256) and m.kernel_size[0] <= 5)
+    if first_direct:
+        (R, S), pad = m.kernel_size, m.padding[0]
+        big = (in_shape[0], in_shape[1] + 2 * pad - R + 1, in_shape[2] + 2 * pad - S + 1, m.out_channels, R, S, pad)
+        first_direct = ops.tconv1_route("wgrad", *big, nc=c_log) is not None
+        first_planes = ops.tconv1_route("fwd", *big) is not None
     gemm = "convT" if st.kind == "convT" else "conv"
     if (st.kind == "conv" and m.out_channels == 1 and taps == 1 and m.stride[0] == 1 and m.padding[0] == 0
             and tuple(in_shape[1:3]) == (1, 1) and Cp % 4 == 0 and st.act == ACT_NONE):
@@ -444,7 +455,7 @@ def route(st: Stage, in_shape, c_log: int) -> Route:
             wgrad_fold = wgrad
     planes = None
     if st.index == 0 and st.bn is None and st.kind == "conv":
-        planes = "direct" if first_direct else "scatter" if m.out_channels % 4 == 0 else None
+        planes = "direct" if first_planes else "scatter" if m.out_channels % 4 == 0 else None
     return Route(fwd, wgrad, wgrad_fold, dgrad="tconv1" if tconv1 else gemm, planes=planes,
                  fold_ok=st.kind != "linear" and st.act in (ACT_NONE, ACT_LEAKY) and not tconv1,
                  bn_leave=st.kind == "conv", bn_reduce=st.kind != "linear" and not tconv1)
@@ -528,7 +539,7 @@ def _fwd_pack_strides(st: Stage):
         return (R * S * C, 1, S * C, C) if C % 4 == 0 else None
     if st.kind == "convT":
         Ci, Co, R, S = w.shape
-        if Ci % 32 != 0 or route(st, (1, 1, 1, Ci), Ci).fwd != "convT":     # (a ConvT's route does not look at H, W)
+        if Ci % 32 != 0 or route(st, (1, 1, 1, Ci), Ci).fwd != "convT":     # (H, W do not decide whether it is the GEMM)
             return None
         return (1, R * S * Ci, S * Ci, Ci)
     return None

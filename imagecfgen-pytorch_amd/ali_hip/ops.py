@@ -710,6 +710,35 @@ def tconv1_wgrad(big, small, sstride, nc, dw, s_k, s_tap, s_c, B, P, Q, K, R, S,
     return dw
 
 
+_T1_OPS = {"fwd": 0, "dgrad": 1, "wgrad": 2}
+
+
+def tconv1_route(op, B, P, Q, K, R, S, pad, nc=1, ws_bytes=None):
+    """The kernel ``tconv1_fwd`` / ``tconv1_dgrad`` / ``tconv1_wgrad`` (``op``: "fwd", "dgrad", "wgrad") launches for a
+    shape, by the instantiation's name -- "fwd_mfma<2,4>", "fwd<16,4>", "dgrad_band<9>", "dgrad<25>", "wgrad_mfma<1,8>",
+    "wgrad_rb<5,3>", "wgrad<7>" -- or None when the launch refuses the shape (ALI_T1_* of include/ali_hip.h).  ``nc``
+    and ``ws_bytes`` (default: the workspace every launch gets) matter to the weight gradient only.  Host arithmetic of
+    the library: needs no GPU."""
+    ws_bytes = _WS_BYTES if ws_bytes is None else int(ws_bytes)
+    code = _lib.load().ali_tconv1_route(_T1_OPS[op], B, P, Q, K, R, S, pad, nc, ws_bytes)
+    if code < 0:
+        return None
+    fam, arg = divmod(code, 1000)
+    if fam == 1:
+        return f"fwd_mfma<{arg // 10},{arg % 10}>"
+    if fam == 2:
+        return f"fwd<{arg * arg},{arg}>"
+    if fam in (3, 4):
+        return f"{'dgrad_band' if fam == 3 else 'dgrad'}<{arg}>"
+    if fam == 5:
+        return f"wgrad_mfma<{arg},8>"
+    if fam == 6:
+        return f"wgrad_rb<{arg // 10},{arg % 10}>"
+    if fam == 7:
+        return f"wgrad<{arg}>"
+    raise ValueError(f"ali_tconv1_route: unknown route code {code}")
+
+
 _PACK_BATCH = None
 _PACK_AFTER = []          # callbacks to run once the pending pack jobs have been launched (fp16 twins of the packs)
 

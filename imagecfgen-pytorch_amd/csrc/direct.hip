@@ -440,6 +440,7 @@ __global__ __launch_bounds__(256) void tconv1_dgrad_band_kernel(const T1Desc d, 
 constexpr int T1W_RB = 4;
 constexpr int T1W_MAXACC = 7;
 constexpr int T1W_MAXNC = 8;
+constexpr int T1W_MW = 8;                // waves per block of the matrix-core weight gradient
 template <int NC>
 __global__ __launch_bounds__(256) void tconv1_wgrad_kernel(const T1Desc d, int nitems, int bands) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -799,48 +800,155 @@ static int t1_check(const char* what, int B, int P, int Q, int K, int H, int W, 
   return ALI_OK;
 }
 
+// ---------------------------------------------------------------- launch plans
+// Which kernel (and which instantiation) serves a shape, with the launch parameters that follow from the choice: decided
+// ONCE per entry point, read by the launch and by the host query ali_tconv1_route.  `route` is an ALI_T1_* code of
+// include/ali_hip.h.  The plans make no HIP call (the query runs without a GPU); a refusal leaves its reason in
+// ali_last_error.
+struct T1Plan {
+  int route;
+  size_t lds;
+  dim3 grid;
+  int LDC;                  // fwd, matrix-core form: pitch of the contribution rows
+  int rbv;                  // dgrad, band form: output rows per block
+  int nitems, bands, nblk;  // wgrad: (image, band) work items, bands per image, blocks = partial slabs
+};
+
+static int t1_plan_fwd(int B, int P, int Q, int K, int R, int S, int pad, T1Plan& pl) {
+  const int H = P + R - 1 - 2 * pad, W = Q + S - 1 - 2 * pad;
+  int rc = t1_check("ali_tconv1_fwd", B, P, Q, K, H, W, R, S, pad);
+  if (rc) return rc;
+  if ((K % T1F_KC) != 0 || R != S) { set_error("ali_tconv1_fwd: needs K %% 32 == 0 and a square kernel"); return ALI_ERR_BAD_ARG; }
+  // scatter form on the matrix cores: one block per image, its tap contributions in LDS (maps up to ~32 x 32)
+  const int T = R * S;
+  const int LDC = (T <= 16 ? 17 : T) | 1;               // odd pitch: the gather's pixel-strided reads spread over the banks
+  const size_t lds_sc = (size_t)P * Q * LDC * sizeof(float);
+  if ((K == 32 || K == 64) && T <= 32 && lds_sc <= 64 * 1024 && tuning().no_t1_mfma == 0) {
+    pl.route = ALI_T1_FWD_MFMA + (T <= 16 ? 1 : 2) * 10 + K / 16;
+    pl.lds = lds_sc;
+    pl.grid = dim3(B);
+    pl.LDC = LDC;
+    return ALI_OK;
+  }
+  pl.route = ALI_T1_FWD + R;
+  pl.lds = (size_t)(T1F_RB + R - 1) * (T1F_CB + S - 1) * T1F_LDP * sizeof(float);
+  pl.grid = dim3((W + T1F_CB - 1) / T1F_CB, (H + T1F_RB - 1) / T1F_RB, B);
+  return ALI_OK;
+}
+
+static int t1_plan_dgrad(int B, int P, int Q, int K, int R, int S, int pad, T1Plan& pl) {
+  const int H = P + R - 1 - 2 * pad, W = Q + S - 1 - 2 * pad;
+  int rc = t1_check("ali_tconv1_dgrad", B, P, Q, K, H, W, R, S, pad);
+  if (rc) return rc;
+  if (256 % (K / 4) != 0) { set_error("ali_tconv1_dgrad: K/4 must divide 256"); return ALI_ERR_BAD_ARG; }
+  const int T = R * S;
+  if (!(T == 16 || T == 25 || T == 9 || T == 4 || T == 1)) {
+    set_error("ali_tconv1_dgrad: unsupported kernel size %dx%d", R, S);
+    return ALI_ERR_BAD_ARG;
+  }
+  // band form: RB output rows per block so that >= ~2 blocks per CU exist, LDS <= 32 KB
+  int rbv = P;
+  while (rbv > 1 && (long long)B * ((P + rbv - 1) / rbv) < 2 * kNumCU) rbv = (rbv + 1) / 2;
+  const size_t lds = (size_t)(rbv + R - 1) * (Q + S - 1) * sizeof(float);
+  if (lds <= 32 * 1024 && B <= 65535 && tuning().no_t1_mfma == 0) {
+    pl.route = ALI_T1_DGRAD_BAND + T;
+    pl.lds = lds;
+    pl.grid = dim3((P + rbv - 1) / rbv, B);
+    pl.rbv = rbv;
+    return ALI_OK;
+  }
+  const long long total = (long long)B * P * Q * (K / 4);
+  long long nb = (total + 255) / 256;
+  if (nb > 4096) nb = 4096;              // (one output per thread was measured slower: 75 vs 54 us, the tap preload dominates)
+  pl.route = ALI_T1_DGRAD + T;
+  pl.lds = 0;
+  pl.grid = dim3((int)nb);
+  return ALI_OK;
+}
+
+// `ws_bytes`: payload bytes of the workspace (without its reserved head)
+static int t1_plan_wgrad(int B, int P, int Q, int K, int R, int S, int pad, int nc, size_t ws_bytes, T1Plan& pl) {
+  const int H = P + R - 1 - 2 * pad, W = Q + S - 1 - 2 * pad;
+  if (nc < 1 || nc > T1W_MAXNC) { set_error("ali_tconv1_wgrad: bad argument"); return ALI_ERR_BAD_ARG; }
+  int rc = t1_check("ali_tconv1_wgrad", B, P, Q, K, H, W, R, S, pad);
+  if (rc) return rc;
+  const int T = R * S;
+  if (!(K == 32 || K == 64 || K == 128 || K == 256) || (T + 256 / K - 1) / (256 / K) > T1W_MAXACC) {
+    set_error("ali_tconv1_wgrad: unsupported K=%d / taps=%d", K, T);
+    return ALI_ERR_BAD_ARG;
+  }
+  const int bands = (P + T1W_RB - 1) / T1W_RB;
+  const int nitems = bands * B;
+  const int nblk = nitems < 8 * kNumCU ? nitems : 8 * kNumCU;   // (latency bound: as many resident blocks as LDS lets in)
+  if (ws_bytes < (size_t)nblk * nc * K * T * sizeof(float)) { set_error("ali_tconv1_wgrad: workspace too small"); return ALI_ERR_WORKSPACE; }
+  pl.nitems = nitems; pl.bands = bands; pl.nblk = nblk;
+  const int Q4 = (Q + 3) & ~3;
+  const int SWp = (Q4 + S - 1 + 3) & ~3;
+  const size_t lds_rb = ((size_t)T1W_RB * Q4 * K + (size_t)nc * (T1W_RB + R - 1) * SWp) * sizeof(float);
+  const bool rb = (256 / K) >= R && S <= 5 && S >= 3 && lds_rb <= 64 * 1024 && (nc == 1 || nc == 5 || nc == 7);
+  const int mnt = (T + 15) / 16;
+  const size_t lds_m = ((size_t)(((P + R - 1) * (Q + S - 1) + 3) & ~3) + (size_t)T1W_MW * 4 * mnt * 64 * 4) * sizeof(float);
+  if (nc == 1 && K == 64 && T <= 32 && lds_m <= 64 * 1024 && tuning().no_t1_mfma == 0 &&
+      ws_bytes >= (size_t)std::min(B, 2 * kNumCU) * K * T * sizeof(float)) {
+    pl.route = ALI_T1_WGRAD_MFMA + mnt;
+    pl.lds = lds_m;
+    pl.nblk = std::min(B, 2 * kNumCU);
+    pl.grid = dim3(pl.nblk);
+    return ALI_OK;
+  }
+  pl.grid = dim3(nblk);
+  if (rb) {
+    pl.route = ALI_T1_WGRAD_RB + nc * 10 + S;
+    pl.lds = lds_rb;
+    return ALI_OK;
+  }
+  pl.route = ALI_T1_WGRAD + nc;
+  pl.lds = ((size_t)T1W_RB * Q * K + (size_t)nc * (T1W_RB + R - 1) * (Q + S - 1)) * sizeof(float);
+  return ALI_OK;
+}
+
 }  // namespace ali
 
 using namespace ali;
+
+extern "C" int32_t ali_tconv1_route(int32_t op, int32_t B, int32_t P, int32_t Q, int32_t K, int32_t R, int32_t S,
+                                    int32_t pad, int32_t nc, size_t ws_bytes) {
+  T1Plan pl = {};
+  int rc;
+  if (op == ALI_T1_OP_FWD) rc = t1_plan_fwd(B, P, Q, K, R, S, pad, pl);
+  else if (op == ALI_T1_OP_DGRAD) rc = t1_plan_dgrad(B, P, Q, K, R, S, pad, pl);
+  else if (op == ALI_T1_OP_WGRAD) rc = t1_plan_wgrad(B, P, Q, K, R, S, pad, nc, ws_payload_bytes(ws_bytes), pl);
+  else { set_error("ali_tconv1_route: bad op %d", op); rc = ALI_ERR_BAD_ARG; }
+  return rc ? rc : pl.route;
+}
 
 extern "C" int ali_tconv1_fwd(const float* big, const float* w_tk, const float* bias, float* out, int32_t B, int32_t P,
                               int32_t Q, int32_t K, int32_t R, int32_t S, int32_t pad, int32_t ostride, int32_t act,
                               float slope, const float* rowscale, int32_t rowscale_ld, ali_stream_t stream) {
   const int H = P + R - 1 - 2 * pad, W = Q + S - 1 - 2 * pad;
   if (!big || !w_tk || !out || ostride < 1) { set_error("ali_tconv1_fwd: bad argument"); return ALI_ERR_BAD_ARG; }
-  int rc = t1_check("ali_tconv1_fwd", B, P, Q, K, H, W, R, S, pad);
+  T1Plan pl = {};
+  int rc = t1_plan_fwd(B, P, Q, K, R, S, pad, pl);
   if (rc) return rc;
   T1Desc d = {};
   d.big = big; d.w = w_tk; d.bias = bias; d.out = out;
   d.B = B; d.P = P; d.Q = Q; d.K = K; d.H = H; d.W = W; d.R = R; d.S = S; d.pad = pad;
   d.ostride = ostride; d.act = act; d.slope = slope;
   d.rowscale = rowscale; d.rowscale_ld = rowscale_ld;
-  if ((K % T1F_KC) != 0 || R != S) { set_error("ali_tconv1_fwd: needs K %% 32 == 0 and a square kernel"); return ALI_ERR_BAD_ARG; }
-  {
-    // scatter form on the matrix cores: one block per image, its tap contributions in LDS (maps up to ~32 x 32)
-    const int T = R * S;
-    const int LDC = (T <= 16 ? 17 : T) | 1;               // odd pitch: the gather's pixel-strided reads spread over the banks
-    const size_t lds_sc = (size_t)P * Q * LDC * sizeof(float);
-    if ((K == 32 || K == 64) && T <= 32 && lds_sc <= 64 * 1024 && tuning().no_t1_mfma == 0) {
-#define T1M(NT_, KC_) hipLaunchKernelGGL((tconv1_fwd_mfma_kernel<NT_, KC_, 8>), dim3(B), dim3(512), lds_sc, (hipStream_t)stream, d, LDC)
-      if (T <= 16 && K == 64) T1M(1, 4);
-      else if (T <= 16) T1M(1, 2);
-      else if (K == 64) T1M(2, 4);
-      else T1M(2, 2);
-#undef T1M
-      return check_launch("tconv1_fwd_mfma_kernel");
-    }
+#define T1M(NT_, KC_) case ALI_T1_FWD_MFMA + NT_ * 10 + KC_: \
+    hipLaunchKernelGGL((tconv1_fwd_mfma_kernel<NT_, KC_, 8>), pl.grid, dim3(512), pl.lds, (hipStream_t)stream, d, pl.LDC); \
+    return check_launch("tconv1_fwd_mfma_kernel")
+#define T1F(T_, S__) case ALI_T1_FWD + S__: \
+    hipLaunchKernelGGL((tconv1_fwd_kernel<T_, S__>), pl.grid, dim3(256), pl.lds, (hipStream_t)stream, d); \
+    return check_launch("tconv1_fwd_kernel")
+  switch (pl.route) {
+    T1M(1, 4); T1M(1, 2); T1M(2, 4); T1M(2, 2);
+    T1F(25, 5); T1F(16, 4); T1F(9, 3); T1F(4, 2); T1F(1, 1);
   }
-  const size_t lds = (size_t)(T1F_RB + R - 1) * (T1F_CB + S - 1) * T1F_LDP * sizeof(float);
-  dim3 grid((W + T1F_CB - 1) / T1F_CB, (H + T1F_RB - 1) / T1F_RB, B);
-#define T1F(T_, S__) hipLaunchKernelGGL((tconv1_fwd_kernel<T_, S__>), grid, dim3(256), lds, (hipStream_t)stream, d)
-  if (R == 5) T1F(25, 5);
-  else if (R == 4) T1F(16, 4);
-  else if (R == 3) T1F(9, 3);
-  else if (R == 2) T1F(4, 2);
-  else T1F(1, 1);
+#undef T1M
 #undef T1F
-  return check_launch("tconv1_fwd_kernel");
+  set_error("ali_tconv1_fwd: no kernel for route %d", pl.route);
+  return ALI_ERR_LAUNCH;
 }
 
 extern "C" int32_t ali_tconv_scatter_ok(int32_t C, int32_t NC, int32_t R, int32_t S, int32_t stride) {
@@ -942,43 +1050,26 @@ extern "C" int ali_tconv1_dgrad(const float* small, int32_t sstride, const float
                                 int32_t R, int32_t S, int32_t pad, ali_stream_t stream) {
   const int H = P + R - 1 - 2 * pad, W = Q + S - 1 - 2 * pad;
   if (!small || !w_tk || !gbig || sstride < 1) { set_error("ali_tconv1_dgrad: bad argument"); return ALI_ERR_BAD_ARG; }
-  int rc = t1_check("ali_tconv1_dgrad", B, P, Q, K, H, W, R, S, pad);
+  T1Plan pl = {};
+  int rc = t1_plan_dgrad(B, P, Q, K, R, S, pad, pl);
   if (rc) return rc;
   T1Desc d = {};
   d.small = small; d.sstride = sstride; d.w = w_tk; d.dact_y = dact_y; d.dact = dact; d.dslope = dslope; d.out = gbig;
   d.B = B; d.P = P; d.Q = Q; d.K = K; d.H = H; d.W = W; d.R = R; d.S = S; d.pad = pad;
-  const long long total = (long long)B * P * Q * (K / 4);
-  long long nb = (total + 255) / 256;
-  if (nb > 4096) nb = 4096;              // (one output per thread was measured slower: 75 vs 54 us, the tap preload dominates)
-  if (256 % (K / 4) != 0) { set_error("ali_tconv1_dgrad: K/4 must divide 256"); return ALI_ERR_BAD_ARG; }
-  const int T = R * S;
-  {
-    // band form: RB output rows per block so that >= ~2 blocks per CU exist, LDS <= 32 KB
-    int rbv = P;
-    while (rbv > 1 && (long long)B * ((P + rbv - 1) / rbv) < 2 * kNumCU) rbv = (rbv + 1) / 2;
-    const size_t lds = (size_t)(rbv + R - 1) * (Q + S - 1) * sizeof(float);
-    if (lds <= 32 * 1024 && B <= 65535 && tuning().no_t1_mfma == 0) {
-      dim3 grid((P + rbv - 1) / rbv, B);
-#define T1B(T_) hipLaunchKernelGGL(tconv1_dgrad_band_kernel<T_>, grid, dim3(256), lds, (hipStream_t)stream, d, rbv)
-      if (T == 16) T1B(16);
-      else if (T == 25) T1B(25);
-      else if (T == 9) T1B(9);
-      else if (T == 4) T1B(4);
-      else if (T == 1) T1B(1);
-      else { set_error("ali_tconv1_dgrad: unsupported kernel size %dx%d", R, S); return ALI_ERR_BAD_ARG; }
-#undef T1B
-      return check_launch("tconv1_dgrad_band_kernel");
-    }
+#define T1B(T_) case ALI_T1_DGRAD_BAND + T_: \
+    hipLaunchKernelGGL(tconv1_dgrad_band_kernel<T_>, pl.grid, dim3(256), pl.lds, (hipStream_t)stream, d, pl.rbv); \
+    return check_launch("tconv1_dgrad_band_kernel")
+#define T1D(T_) case ALI_T1_DGRAD + T_: \
+    hipLaunchKernelGGL(tconv1_dgrad_kernel<T_>, pl.grid, dim3(256), 0, (hipStream_t)stream, d); \
+    return check_launch("tconv1_dgrad_kernel")
+  switch (pl.route) {
+    T1B(16); T1B(25); T1B(9); T1B(4); T1B(1);
+    T1D(16); T1D(25); T1D(9); T1D(4); T1D(1);
   }
-#define T1D(T_) hipLaunchKernelGGL(tconv1_dgrad_kernel<T_>, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, d)
-  if (T == 16) T1D(16);
-  else if (T == 25) T1D(25);
-  else if (T == 9) T1D(9);
-  else if (T == 4) T1D(4);
-  else if (T == 1) T1D(1);
-  else { set_error("ali_tconv1_dgrad: unsupported kernel size %dx%d", R, S); return ALI_ERR_BAD_ARG; }
+#undef T1B
 #undef T1D
-  return check_launch("tconv1_dgrad_kernel");
+  set_error("ali_tconv1_dgrad: no kernel for route %d", pl.route);
+  return ALI_ERR_LAUNCH;
 }
 
 extern "C" int ali_tconv1_wgrad(const float* big, const float* small, int32_t sstride, int32_t nc, float* dw, int64_t s_k,
@@ -991,53 +1082,33 @@ extern "C" int ali_tconv1_wgrad(const float* big, const float* small, int32_t ss
     set_error("ali_tconv1_wgrad: bad argument");
     return ALI_ERR_BAD_ARG;
   }
-  int rc = t1_check("ali_tconv1_wgrad", B, P, Q, K, H, W, R, S, pad);
+  T1Plan pl = {};
+  int rc = t1_plan_wgrad(B, P, Q, K, R, S, pad, nc, ws ? ws_bytes : 0, pl);
   if (rc) return rc;
   const int T = R * S;
-  if (!(K == 32 || K == 64 || K == 128 || K == 256) || (T + 256 / K - 1) / (256 / K) > T1W_MAXACC) {
-    set_error("ali_tconv1_wgrad: unsupported K=%d / taps=%d", K, T);
-    return ALI_ERR_BAD_ARG;
-  }
-  const int bands = (P + T1W_RB - 1) / T1W_RB;
-  const int nitems = bands * B;
-  const int nblk = nitems < 8 * kNumCU ? nitems : 8 * kNumCU;   // (latency bound: as many resident blocks as LDS lets in)
-  if (!ws || ws_bytes < (size_t)nblk * nc * K * T * sizeof(float)) { set_error("ali_tconv1_wgrad: workspace too small"); return ALI_ERR_WORKSPACE; }
   T1Desc d = {};
   d.big = big; d.small = small; d.sstride = sstride; d.part = reinterpret_cast<float*>(ws);
   d.B = B; d.P = P; d.Q = Q; d.K = K; d.H = H; d.W = W; d.R = R; d.S = S; d.pad = pad;
   hipStream_t st = (hipStream_t)stream;
-  const int Q4 = (Q + 3) & ~3;
-  const int SWp = (Q4 + S - 1 + 3) & ~3;
-  const size_t lds_rb = ((size_t)T1W_RB * Q4 * K + (size_t)nc * (T1W_RB + R - 1) * SWp) * sizeof(float);
-  const bool rb = (256 / K) >= R && S <= 5 && S >= 3 && lds_rb <= 64 * 1024 && (nc == 1 || nc == 5 || nc == 7);
-  constexpr int MW = 8;                                   // waves per block of the matrix-core form
-  const int mnt = (T + 15) / 16;
-  const size_t lds_m = ((size_t)(((P + R - 1) * (Q + S - 1) + 3) & ~3) + (size_t)MW * 4 * mnt * 64 * 4) * sizeof(float);
-  if (nc == 1 && K == 64 && T <= 32 && lds_m <= 64 * 1024 && tuning().no_t1_mfma == 0 &&
-      ws_bytes >= (size_t)std::min(B, 2 * kNumCU) * K * T * sizeof(float)) {
-    const int nb = std::min(B, 2 * kNumCU);
-    if (mnt == 1) hipLaunchKernelGGL((tconv1_wgrad_mfma_kernel<1, MW>), dim3(nb), dim3(64 * MW), lds_m, st, d);
-    else hipLaunchKernelGGL((tconv1_wgrad_mfma_kernel<2, MW>), dim3(nb), dim3(64 * MW), lds_m, st, d);
-    hipLaunchKernelGGL(t1_reduce_kernel, dim3(K * T), dim3(64), 0, st, d.part, nb, K, T, 1, dw, (long long)s_k,
-                       (long long)s_tap, (long long)s_c);
-    return check_launch("tconv1_wgrad_mfma");
+#define WM(NT_) case ALI_T1_WGRAD_MFMA + NT_: \
+    hipLaunchKernelGGL((tconv1_wgrad_mfma_kernel<NT_, T1W_MW>), pl.grid, dim3(64 * T1W_MW), pl.lds, st, d); \
+    hipLaunchKernelGGL(t1_reduce_kernel, dim3(K * T), dim3(64), 0, st, d.part, pl.nblk, K, T, 1, dw, (long long)s_k, \
+                       (long long)s_tap, (long long)s_c); \
+    return check_launch("tconv1_wgrad_mfma")
+#define WRB(NC_, S_) case ALI_T1_WGRAD_RB + NC_ * 10 + S_: \
+    hipLaunchKernelGGL((tconv1_wgrad_rb_kernel<NC_, S_>), pl.grid, dim3(256), pl.lds, st, d, pl.nitems, pl.bands); break
+#define WG(NC_) case ALI_T1_WGRAD + NC_: \
+    hipLaunchKernelGGL((tconv1_wgrad_kernel<NC_>), pl.grid, dim3(256), pl.lds, st, d, pl.nitems, pl.bands); break
+  switch (pl.route) {
+    WM(1); WM(2);
+    WRB(1, 3); WRB(1, 4); WRB(1, 5); WRB(5, 3); WRB(5, 4); WRB(5, 5); WRB(7, 3); WRB(7, 4); WRB(7, 5);
+    WG(1); WG(2); WG(3); WG(4); WG(5); WG(6); WG(7); WG(8);
+    default: set_error("ali_tconv1_wgrad: no kernel for route %d", pl.route); return ALI_ERR_LAUNCH;
   }
-  if (rb) {
-#define WRB(NC_, S_) hipLaunchKernelGGL((tconv1_wgrad_rb_kernel<NC_, S_>), dim3(nblk), dim3(256), lds_rb, st, d, nitems, bands)
-    if (nc == 1 && S == 3) WRB(1, 3); else if (nc == 1 && S == 4) WRB(1, 4); else if (nc == 1) WRB(1, 5);
-    else if (nc == 5 && S == 3) WRB(5, 3); else if (nc == 5 && S == 4) WRB(5, 4); else if (nc == 5) WRB(5, 5);
-    else if (nc == 7 && S == 3) WRB(7, 3); else if (nc == 7 && S == 4) WRB(7, 4); else WRB(7, 5);
+#undef WM
 #undef WRB
-  } else {
-  const size_t lds = ((size_t)T1W_RB * Q * K + (size_t)nc * (T1W_RB + R - 1) * (Q + S - 1)) * sizeof(float);
-#define WG(NC_) hipLaunchKernelGGL((tconv1_wgrad_kernel<NC_>), dim3(nblk), dim3(256), lds, st, d, nitems, bands)
-  switch (nc) {
-    case 1: WG(1); break; case 2: WG(2); break; case 3: WG(3); break; case 4: WG(4); break;
-    case 5: WG(5); break; case 6: WG(6); break; case 7: WG(7); break; default: WG(8); break;
-  }
 #undef WG
-  }
-  hipLaunchKernelGGL(t1_reduce_kernel, dim3(nc * K * T), dim3(64), 0, st, d.part, nblk, K, T, nc, dw, (long long)s_k,
+  hipLaunchKernelGGL(t1_reduce_kernel, dim3(nc * K * T), dim3(64), 0, st, d.part, pl.nblk, K, T, nc, dw, (long long)s_k,
                      (long long)s_tap, (long long)s_c);
   return check_launch("tconv1_wgrad");
 }

@@ -286,6 +286,23 @@ int ali_tconv1_dgrad(const float* small, int32_t sstride, const float* w_tk, con
 int ali_tconv1_wgrad(const float* big, const float* small, int32_t sstride, int32_t nc, float* dw, int64_t s_k,
                      int64_t s_tap, int64_t s_c, int32_t B, int32_t P, int32_t Q, int32_t K, int32_t R, int32_t S,
                      int32_t pad, void* ws, size_t ws_bytes, ali_stream_t stream);
+/* Which kernel the three entry points above launch for a shape: the launch and this query read one plan.  `op` is an
+ * ALI_T1_OP_*; `nc` and `ws_bytes` (the whole workspace, reserved head included) matter to the weight gradient only.
+ * Returns an ALI_T1_* family plus the template arguments of the instantiation, or the negative error code with which
+ * the launch would refuse the shape (ali_last_error says why).  Host arithmetic only: works without a GPU.  It reads
+ * ALI_NO_T1_MFMA like the launches do. */
+#define ALI_T1_OP_FWD 0
+#define ALI_T1_OP_DGRAD 1
+#define ALI_T1_OP_WGRAD 2
+#define ALI_T1_FWD_MFMA 1000   /* + 10 NT + KC : tconv1_fwd_mfma_kernel<NT, KC, 8>, NT tap tiles, KC = K / 16 */
+#define ALI_T1_FWD 2000        /* + S          : tconv1_fwd_kernel<S * S, S> */
+#define ALI_T1_DGRAD_BAND 3000 /* + R * S      : tconv1_dgrad_band_kernel<R * S> */
+#define ALI_T1_DGRAD 4000      /* + R * S      : tconv1_dgrad_kernel<R * S> */
+#define ALI_T1_WGRAD_MFMA 5000 /* + NT         : tconv1_wgrad_mfma_kernel<NT, 8> */
+#define ALI_T1_WGRAD_RB 6000   /* + 10 nc + S  : tconv1_wgrad_rb_kernel<nc, S> */
+#define ALI_T1_WGRAD 7000      /* + nc         : tconv1_wgrad_kernel<nc> */
+int32_t ali_tconv1_route(int32_t op, int32_t B, int32_t P, int32_t Q, int32_t K, int32_t R, int32_t S, int32_t pad,
+                         int32_t nc, size_t ws_bytes);
 
 /* dst[(n*T+t)*Cpad + c] = c < C ? src[n*s_n + t*s_tap + c*s_c] : 0.
  * Re-lays reference-layout parameters ([Cout,Cin,kh,kw] Conv2d, [Cin,Cout,kh,kw]

@@ -34,4 +34,9 @@ NEW_STACKS = {
     "linear_unflat_bn": (lambda: nn.Sequential(nn.Linear(10, 48), nn.Unflatten(1, (12, 2, 2)), nn.LeakyReLU(0.2),
                                                nn.BatchNorm2d(12), nn.ConvTranspose2d(12, 4, 3, stride=2)),
                          (4, 1, 1, 12), 10),
+    # one-channel ends the direct kernels refuse (128 channels: 25 / 16 taps need 13 / 8 accumulators per thread, the
+    # weight-gradient kernel has 7): the first conv's weight gradient and the whole tail take the GEMMs of their kind.
+    # (New names go last in sorted order: test_gpu_chain_stacks.build seeds a stack by its sorted position.)
+    "wide_first_k5": (lambda: nn.Sequential(nn.Conv2d(3, 128, 5), nn.LeakyReLU(0.2)), (4, 7, 8, 4), 3),
+    "wide_tail_k4": (lambda: nn.Sequential(nn.ConvTranspose2d(128, 1, 4), nn.Tanh()), (4, 5, 6, 128), 128),
 }

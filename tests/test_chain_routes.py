@@ -400,6 +400,13 @@ NEW_EXPECTED = {
     "linear_unflat_bn": ([('linear', [], 'conv', ('linear_repack', 'unflat'), ('linear_repack', 'unflat'), 'conv', None,
                            False, False, False), _pre(CONVT, ['bn'])],
                          [(4, 1, 1, 12), (4, 2, 2, 12), (4, 5, 5, 4)]),
+    # ali_tconv1_wgrad refuses 128 channels x 25 taps: GEMM weight gradient; the plane form (ali_tconv1_fwd) stays direct
+    "wide_first_k5": ([_pre(CONV, [], planes='direct')],
+                      [(4, 7, 8, 4), (4, 3, 4, 128)]),
+    # ... and 128 channels x 16 taps: no "tconv1" on any pass, the tail is the scatter GEMM of `tail_48`
+    "wide_tail_k4": ([('convT', [], 'scatter_gemm', ('convT', 'colsum'), ('convT', 'colsum'), 'convT', None, False, False,
+                       True)],
+                     [(4, 5, 6, 128), (4, 8, 9, 1)]),
 }
 
 
