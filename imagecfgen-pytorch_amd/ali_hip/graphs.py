@@ -4,6 +4,8 @@
 miss the call runs once outside capture on static copies of the arguments (``_Graphed``: packs, workspace, plans), the
 state it touched is put back (a warm-up is no training step), and it is recorded; a hit copies the arguments in with one
 launch and replays.  ``AliStepper`` records its segmented iteration on ``_Graphed`` directly."""
+import gc
+
 import torch
 
 from . import ops
@@ -27,8 +29,17 @@ class _Graphed:
 
     def capture(self, fn, *args):
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, pool=self._pool, capture_error_mode="thread_local"):
-            out = fn(*args)
+        # No cyclic garbage collection while the stream captures: a collection that starts inside the capture finalises
+        # whatever dead cycles earlier work left behind, and releasing their device memory or graphs is not permitted
+        # on a capturing thread (the process aborts).  They go at the next collection after the capture instead.
+        was_enabled = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.graph(g, pool=self._pool, capture_error_mode="thread_local"):
+                out = fn(*args)
+        finally:
+            if was_enabled:
+                gc.enable()
         self.graphs.append(g)
         return out
 

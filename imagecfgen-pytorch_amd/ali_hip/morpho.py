@@ -9,10 +9,13 @@
                   ``mnist_vae_measured_cf.py`` and the data-set builders -- ``SetThickness``, ``SetSlant``, ``downscale``,
                   the intensity rescale -- as device tensors with no host read: the four launches above and three more
                   per chunk (reshape, shear_reduce, set_intensity).
+  MorphoLocal     ``apply(images, kind)`` returns the images of the five Morpho-MNIST data sets -- plain, ``Thinning``,
+                  ``Thickening``, ``Swelling``, ``Fracture`` and ``downscale`` -- as device tensors with no host read: the four
+                  launches above, then locate, local and shear_reduce (and one more distance map for "thick").
 
 CPU tensors run the statement ``morphomnist.morpho`` row by row in the dtype of the tensor (float64: the tests'
 reference; float32: their yardstick), and ``morphomnist.perturb`` likewise.  What is measured and perturbed is that
-statement, not scikit-image's pipeline (DESIGN 3.16, 3.17).
+statement, not scikit-image's pipeline (DESIGN 3.16, 3.17, 3.20).
 """
 import numpy as np
 import torch
@@ -324,3 +327,146 @@ class MorphoPerturb:
                 "status": col("status", np.int32), "radius": col("radius", np.int32),
                 "thickness_before": col("thickness", dtype), "shear_before": col("shear", np.float64),
                 "intensity_before": col("median", dtype)}
+
+
+KINDS = ops.MORPHO_KINDS
+LOCAL_KEYS = ("images", "bits", "status", "radius", "thickness_before", "n_candidates", "fallback", "centres",
+              "endpoints")
+
+
+def local_image_bytes(H, W, scale):
+    """what one image of a ``MorphoLocal`` chunk holds on the device: ``perturb_image_bytes`` and the complement bitmap
+    with its distance map"""
+    Hh, Wh = H * scale, W * scale
+    return perturb_image_bytes(H, W, scale) + 4 * Hh * Wh + 4 * Hh * ((Wh + 31) // 32)
+
+
+class MorphoLocal:
+    """The five Morpho-MNIST data sets' perturbations for a batch: plain, ``Thinning``, ``Thickening``, ``Swelling`` and
+    ``Fracture`` of ``morphomnist.perturb`` with ``ImageMorphology.downscale`` (``morphomnist.perturb.local_image``).
+
+    ``apply(images, kind)`` takes images as ``MorphoMeasure.measure`` does and ``kind``: one of ``KINDS`` ("plain",
+    "thin", "thick", "swell", "fracture") for the whole batch, or an int32 [B] tensor of kind numbers 0 .. 4 on the
+    images' device, one perturbation per image (a number outside 0 .. 4 gives that image status 4; the tensor is not
+    read on the host).  Returns {"images": float [B, H, W] in 0 .. 255, "bits": the perturbed bitmaps' words int32 [B, H
+    s, ceil(W s / 32)], "status": int32 [B] (0; 1, 2 as ``MorphoMeasure``; 4: nothing left -- no skeleton for any kind
+    but plain, or an empty result; the image is 0 then), "radius": int32 [B] (the disk radius of thin / thick /
+    fracture, int(R) of a swelling), "thickness_before", "n_candidates": int32 [B] (the skeleton pixels the locations
+    were drawn from), "fallback": int32 [B] (1: pruning left none), "centres": int32 [B, 8, 2] (row, column; -1 where
+    unused), "endpoints": int32 [B, 8, 4] (r0, c0, r1, c1 of the cuts)}.
+
+    The locations are draws of the counter RNG ("locate" stream of ``ali_hip.rng``) under (seed, counter, global row):
+    the counter starts at 0 and advances once per ``apply``, so a fresh executor with the same seed repeats them and
+    chunking does not change them.
+
+    CUDA tensors: per chunk the four launches of ``MorphoMeasure``, then locate, local and shear_reduce (csrc/
+    morpho.hip), and for "thick" or a kind tensor the complement and its distance map in front of local; on the current
+    stream, no host read.  CPU tensors run the statement row by row in the tensor's dtype."""
+
+    def __init__(self, scale=16, threshold=.5, seed=0, chunk=None, thin_amount=.7, thick_amount=1., swell_strength=3.,
+                 swell_radius=7., frac_thickness=1.5, frac_prune=2., num_frac=3):
+        from morphomnist import perturb
+        from morphomnist.skeleton import prune_radius
+        self.measure = MorphoMeasure(scale, threshold, seed, chunk)
+        self.scale, self.threshold, self.seed, self.chunk = self.measure.scale, float(threshold), int(seed), chunk
+        if int(num_frac) != num_frac or not 1 <= int(num_frac) <= ops.MORPHO_MAX_DRAWS:
+            raise ValueError(f"MorphoLocal: num_frac in 1 .. {ops.MORPHO_MAX_DRAWS}")
+        if not float(swell_strength) >= 1:
+            raise ValueError("MorphoLocal: swell_strength >= 1")
+        if not (float(thin_amount) >= 0 and float(thick_amount) >= 0 and float(swell_radius) >= 0
+                and float(frac_thickness) >= 0 and (frac_prune is None or float(frac_prune) >= 0)):
+            raise ValueError("MorphoLocal: the amounts, swell_radius, frac_thickness and frac_prune are >= 0")
+        self.params = dict(thin_amount=float(thin_amount), thick_amount=float(thick_amount),
+                           swell_strength=float(swell_strength), swell_radius=float(swell_radius),
+                           frac_thickness=float(frac_thickness), frac_prune=frac_prune, num_frac=int(num_frac))
+        self.frac_radius = perturb.fracture_radius(frac_thickness, self.scale)
+        if self.frac_radius > ops.MORPHO_MAX_STAMP:
+            raise ValueError(f"MorphoLocal: a fracture brush of radius {self.frac_radius} exceeds {ops.MORPHO_MAX_STAMP}")
+        self.prune = prune_radius(frac_prune, self.scale)
+        self.calls = 0                                               # the counter of the CPU path
+        self._rops, self._ws, self._ctr = {}, {}, {}
+
+    def chunk_for(self, H, W):
+        if self.chunk is not None:
+            return max(int(self.chunk), 1)
+        return max(WORKSPACE_BUDGET // local_image_bytes(H, W, self.scale), 1)
+
+    reduce_operators = MorphoPerturb.reduce_operators
+    _workspace = MorphoPerturb._workspace
+
+    def counter(self, device):
+        """the device counter (int64 [1]): the number of ``apply`` calls on ``device`` so far"""
+        if str(device) not in self._ctr:
+            self._ctr[str(device)] = torch.zeros(1, dtype=torch.int64, device=device)
+        return self._ctr[str(device)]
+
+    @torch.no_grad()
+    def apply(self, images, kind):
+        x = as_images(images)
+        if not x.is_floating_point():
+            raise ValueError("MorphoLocal: float images only")
+        B, H, W = x.shape
+        s = self.scale
+        if H * s > ops.MORPHO_MAX_SIDE or W * s > ops.MORPHO_MAX_SIDE:
+            raise ValueError(f"MorphoLocal: {H} x {W} images at scale {s} exceed the limit of "
+                             f"{ops.MORPHO_MAX_SIDE} x {ops.MORPHO_MAX_SIDE} up-sampled pixels")
+        if isinstance(kind, str):
+            if kind not in KINDS:
+                raise ValueError(f"MorphoLocal: kind is one of {KINDS} or an int32 [B] tensor, got {kind!r}")
+            kinds = torch.full((B,), KINDS.index(kind), dtype=torch.int32, device=x.device)
+        else:
+            if not (torch.is_tensor(kind) and tuple(kind.shape) == (B,) and kind.device == x.device
+                    and kind.dtype == torch.int32):
+                raise ValueError(f"MorphoLocal: kind is one of {KINDS} or an int32 [{B}] tensor on {x.device}")
+            kinds = kind.contiguous()
+        if not x.is_cuda:
+            return self._apply_cpu(x, kinds)
+        if x.dtype != torch.float32 or not x[0].is_contiguous():
+            x = x.float().contiguous()
+        dev = x.device
+        Hh, Wh = H * s, W * s
+        i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+        out = {"images": torch.empty(B, H, W, dtype=torch.float32, device=dev), "bits": i32(B, Hh, (Wh + 31) // 32),
+               "status": i32(B), "radius": i32(B), "thickness_before": torch.empty(B, dtype=torch.float32, device=dev),
+               "n_candidates": i32(B), "fallback": i32(B), "centres": i32(B, ops.MORPHO_MAX_DRAWS, 2),
+               "endpoints": i32(B, ops.MORPHO_MAX_DRAWS, 4)}
+        mm = self.measure
+        AH, AW = mm.operators(H, W, dev)
+        RH, RW = self.reduce_operators(H, W, dev)
+        ctr = self.counter(dev)
+        thicken = not isinstance(kind, str) or kind == "thick"
+        p = self.params
+        n = min(self.chunk_for(H, W), B)
+        ws = self._workspace(n, H, W, dev)
+        for lo in range(0, B, n):
+            hi = min(lo + n, B)
+            bits, fg, hstats = ops.morpho_binarise(x[lo:hi], s, AH, AW, self.threshold, ws=ws)
+            d2, st = ops.morpho_edt(bits, Wh, ws=ws)
+            skel = ops.morpho_thin(bits, d2, fg, st, mm._keep, self.seed, ws=ws)
+            _, values, _ = ops.morpho_measure(x[lo:hi], s, skel, d2, fg, hstats, st)
+            n_cand, fb, ce, en = ops.morpho_locate(skel, d2, st, kinds[lo:hi], s, self.prune, self.prune, p["num_frac"],
+                                                   self.seed, ctr, offset=lo)
+            d2c = ops.morpho_edt(ops.morpho_complement(bits, Wh), Wh, ws=ws)[0] if thicken else None
+            new, radius, sums, st = ops.morpho_local(bits, Wh, d2, d2c, values[:, 2], st, kinds[lo:hi], n_cand, ce, en, s,
+                                                     p["thin_amount"], p["thick_amount"], p["swell_strength"],
+                                                     p["swell_radius"], self.frac_radius, p["num_frac"])
+            q, _ = ops.morpho_shear_reduce(new, H, W, s, sums, None, st, RH, RW, ws=ws)
+            for k, v in (("images", q), ("bits", new), ("status", st), ("radius", radius),
+                         ("thickness_before", values[:, 2]), ("n_candidates", n_cand), ("fallback", fb), ("centres", ce),
+                         ("endpoints", en)):
+                out[k][lo:hi] = v
+        ctr += 1
+        return out
+
+    def _apply_cpu(self, x, kinds):
+        from morphomnist import perturb
+        dtype = np.float64 if x.dtype == torch.float64 else np.float32
+        rows = [perturb.local_image(x[b].numpy(), int(kinds[b]), self.scale, self.threshold, self.seed, dtype, self.calls,
+                                    b, **self.params) for b in range(x.shape[0])]
+        self.calls += 1
+        col = lambda k, dt: torch.from_numpy(np.array([r[k] for r in rows], dtype=dt))
+        return {"images": torch.from_numpy(np.stack([r["image"] for r in rows]).astype(dtype)),
+                "bits": pack_bits(np.stack([r["bitmap"] for r in rows])), "status": col("status", np.int32),
+                "radius": col("radius", np.int32), "thickness_before": col("thickness", dtype),
+                "n_candidates": col("n_candidates", np.int32), "fallback": col("fallback", np.int32),
+                "centres": col("centres", np.int32), "endpoints": col("endpoints", np.int32)}

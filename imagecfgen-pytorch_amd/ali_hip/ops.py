@@ -2183,3 +2183,97 @@ def morpho_set_intensity(q, target, status, out=None):
                                             N, _chk(out, "out"), _chk(median, "median"),
                                             _i32(status_out, "status_out"), _stream()), "ali_morpho_set_intensity")
     return out, median, status_out
+
+
+MORPHO_MAX_DRAWS = 8             # locations one image draws per ali_morpho_locate (rng.MAX_DRAWS)
+MORPHO_MAX_STAMP = 1024          # the largest brush radius of ali_morpho_local's fracture
+MORPHO_KINDS = ("plain", "thin", "thick", "swell", "fracture")
+
+
+def _morpho_bits(bits, Wh, who):
+    if not (bits.is_cuda and bits.dtype == torch.int32 and bits.dim() == 3 and bits.is_contiguous()):
+        raise ValueError(f"{who}: need a contiguous int32 CUDA tensor [B, Hh, wpr] of bitmap words")
+    B, Hh, wpr = bits.shape
+    if wpr != (Wh + 31) // 32:
+        raise ValueError(f"{who}: {wpr} words per row do not hold {Wh} pixels")
+    if B < 1 or Hh > MORPHO_MAX_SIDE or Wh > MORPHO_MAX_SIDE:
+        raise ValueError(f"morpho: {Hh} x {Wh} bitmaps exceed the limit of {MORPHO_MAX_SIDE} x {MORPHO_MAX_SIDE} "
+                         f"up-sampled pixels")
+    return B, Hh, wpr
+
+
+def morpho_complement(bits, Wh):
+    """the complement of the bitmaps bits [B, Hh, ceil(Wh / 32)], pad bits 0 (what ``morpho_edt`` takes for ``d2c``)"""
+    wpr = bits.shape[-1]
+    mask = torch.full((wpr,), -1, dtype=torch.int32, device=bits.device)
+    if Wh & 31:
+        mask[-1:].fill_((1 << (Wh & 31)) - 1)                         # (a fill, not a host copy: capturable)
+    return torch.bitwise_not(bits) & mask
+
+
+def morpho_locate(skel, d2, status, kind, scale, prune_tips=None, prune_forks=None, num=3, seed=0, dev_counter=None,
+                  offset=0):
+    """Skeleton locations for the swellings and fractures of a batch (include/ali_hip.h: ali_morpho_locate).  skel, d2,
+    status as ``morpho_thin`` / ``morpho_edt`` left them; kind int32 [B] (``MORPHO_KINDS``); prune_tips / prune_forks:
+    the erase radii of a fracture in up-sampled pixels, or None; num: the locations of a fracture (a swelling draws
+    one); (seed, dev_counter, offset): the "locate" stream, ``offset`` the images in front of image 0.  Returns
+    (n_candidates int32 [B], fallback int32 [B], centres int32 [B, 8, 2] = (row, column), -1 where unused, endpoints
+    int32 [B, 8, 4] = r0, c0, r1, c1)."""
+    lib = _lib.load()
+    B, Hh, Wh = d2.shape
+    _morpho_bits(skel, Wh, "morpho_locate")
+    if not 1 <= int(num) <= MORPHO_MAX_DRAWS:
+        raise ValueError(f"morpho_locate: num in 1 .. {MORPHO_MAX_DRAWS}")
+    radius = lambda r: -1 if r is None else int(r)
+    if (prune_tips is not None and int(prune_tips) < 0) or (prune_forks is not None and int(prune_forks) < 0):
+        raise ValueError("morpho_locate: a prune radius is >= 0, or None")
+    dev = skel.device
+    n_cand = torch.empty(B, dtype=torch.int32, device=dev)
+    fallback = torch.empty(B, dtype=torch.int32, device=dev)
+    centres = torch.empty(B, MORPHO_MAX_DRAWS, 2, dtype=torch.int32, device=dev)
+    endpoints = torch.empty(B, MORPHO_MAX_DRAWS, 4, dtype=torch.int32, device=dev)
+    seed, ctr, offset = _rng_args(seed, dev_counter, offset)
+    _lib.check(lib.ali_morpho_locate(_i32s(skel, (B, Hh, (Wh + 31) // 32), "skel"), _i32s(d2, (B, Hh, Wh), "d2"),
+                                     _i32(status, "status", B), _i32s(kind, (B,), "kind"), B, Hh, Wh, int(scale),
+                                     radius(prune_tips), radius(prune_forks), int(num), seed, ctr, offset,
+                                     _i32(n_cand, "n_candidates"), _i32(fallback, "fallback"), _i32(centres, "centres"),
+                                     _i32(endpoints, "endpoints"), _stream()), "ali_morpho_locate")
+    return n_cand, fallback, centres, endpoints
+
+
+def morpho_local(bits, Wh, d2, d2c, thickness, status, kind, n_candidates, centres, endpoints, scale, thin_amount=.7,
+                 thick_amount=1., swell_strength=3., swell_radius=7., frac_radius=12, num_frac=3):
+    """The five Morpho-MNIST perturbations on the bitmaps bits [B, Hh, ceil(Wh / 32)] by kind int32 [B] (include/
+    ali_hip.h: ali_morpho_local).  d2: the distance map; d2c: that of ``morpho_complement(bits)``, or None when no image
+    is thickened; thickness: fp32 [B], any stride; n_candidates, centres, endpoints: ``morpho_locate``'s; frac_radius:
+    the brush radius in up-sampled pixels (``morphomnist.perturb.fracture_radius``).  Returns (the new bitmaps, radius
+    int32 [B], moment sums int64 [B, 6], status int32 [B])."""
+    lib = _lib.load()
+    B, Hh, wpr = _morpho_bits(bits, Wh, "morpho_local")
+    if not (thickness.is_cuda and thickness.dtype == torch.float32 and tuple(thickness.shape) == (B,)
+            and (B == 1 or thickness.stride(0) >= 1)):
+        raise ValueError(f"morpho_local: thickness is an fp32 CUDA tensor [{B}]")
+    if not 0 <= int(frac_radius) <= MORPHO_MAX_STAMP:
+        raise ValueError(f"morpho_local: frac_radius in 0 .. {MORPHO_MAX_STAMP}")
+    if not 1 <= int(num_frac) <= MORPHO_MAX_DRAWS:
+        raise ValueError(f"morpho_local: num_frac in 1 .. {MORPHO_MAX_DRAWS}")
+    if not (float(swell_strength) >= 1 and float(thin_amount) >= 0 and float(thick_amount) >= 0
+            and float(swell_radius) >= 0):
+        raise ValueError("morpho_local: swell_strength >= 1, and the amounts and swell_radius >= 0")
+    dev = bits.device
+    out = torch.empty_like(bits)
+    radius = torch.empty(B, dtype=torch.int32, device=dev)
+    sums = torch.empty(B, 6, dtype=torch.int64, device=dev)
+    status_out = torch.empty(B, dtype=torch.int32, device=dev)
+    _lib.check(lib.ali_morpho_local(c_void_p(bits.data_ptr()), _i32s(d2, (B, Hh, Wh), "d2"),
+                                    None if d2c is None else _i32s(d2c, (B, Hh, Wh), "d2c"),
+                                    c_void_p(thickness.data_ptr()), max(thickness.stride(0), 1),
+                                    _i32(status, "status", B), _i32s(kind, (B,), "kind"),
+                                    _i32(n_candidates, "n_candidates", B),
+                                    _i32s(centres, (B, MORPHO_MAX_DRAWS, 2), "centres"),
+                                    _i32s(endpoints, (B, MORPHO_MAX_DRAWS, 4), "endpoints"), float(thin_amount),
+                                    float(thick_amount), float(swell_strength), float(swell_radius), int(frac_radius),
+                                    int(num_frac), B, Hh, Wh, int(scale), _i32(out, "out"), _i32(radius, "radius"),
+                                    c_void_p(sums.data_ptr()), _i32(status_out, "status_out"), _stream()),
+               "ali_morpho_local")
+    return out, radius, sums, status_out

@@ -1,7 +1,8 @@
 """The counter RNG of the HIP path on the host: the key schedule of csrc/ali_rng.h (the table there is the statement)
 and the references that reproduce a run's draws from (seed, counter, index) -- Dropout2d masks, latents, the WGAN-GP
 ``eps``, Gumbel noise, Griffin-Lim phases, the tiebreak of the thinning order and the background rows and mixing weights
-of the expected-gradients estimator.  The integers are exact on both sides."""
+of the expected-gradients estimator, and the skeleton locations of the Morpho-MNIST local perturbations.  The integers
+are exact on both sides."""
 import numpy as np
 import torch
 
@@ -10,9 +11,11 @@ LATENT_STREAM, GP_STREAM = 0x4C4154454E545A31, 0x47504D4958455053
 GUMBEL_STREAM, PHASE_STREAM = 0x47554D42454C3031, 0x474C504841534531
 THIN_STREAM = 0x5448494E4B455931
 EG_STREAM = 0x4547425249445831
+LOCATE_STREAM = 0x534B454C4C4F4331                                   # "SKELLOC1"
+MAX_DRAWS = 8                    # locations one image draws per call (ali_morpho_locate)
 STREAMS = {"mask": (), "latent": (LATENT_STREAM,), "gp": (LATENT_STREAM, GP_STREAM),       # the tags mixed into the
            "gumbel": (LATENT_STREAM, GUMBEL_STREAM), "phase": (PHASE_STREAM,),               # base key, in order
-           "thin": (THIN_STREAM,), "eg": (EG_STREAM,)}
+           "thin": (THIN_STREAM,), "eg": (EG_STREAM,), "locate": (LOCATE_STREAM,)}
 M64, TWO24 = (1 << 64) - 1, 16777216.0
 
 
@@ -120,3 +123,14 @@ def eg_index_reference(seed, counter, n, n_background, offset=0):
 def eg_t_reference(seed, counter, n, offset=0):
     """The mixing weights of the same pairs: a float32 CPU tensor [n] in [0, 1), lo24 / 2^24 of the same hash.  Exact."""
     return torch.from_numpy((lo24(hashes(key(seed, counter, "eg"), n, offset)) / TWO24).astype(np.float32))
+
+
+def locate_reference(seed, counter, n_candidates, row, k):
+    """Draw ``k`` (< MAX_DRAWS) of image ``row`` of ``ali_morpho_locate(seed, &counter, offset, ...)``: an index into the
+    image's ``n_candidates`` skeleton candidates in row-major order, ``(hi24 * n_candidates) >> 24`` of hash
+    ``row * MAX_DRAWS + k`` under the "locate" key.  ``row`` counts from the first image of the whole call (the
+    launcher's ``offset`` plus the row of the launch).  Exact; draw k does not depend on how many are drawn."""
+    if not 0 <= int(k) < MAX_DRAWS:
+        raise ValueError(f"locate_reference: draw {k} outside 0 .. {MAX_DRAWS - 1}")
+    h = hi24(hashes(key(seed, counter, "locate"), 1, int(row) * MAX_DRAWS + int(k)))
+    return int((int(h[0]) * int(n_candidates)) >> 24)

@@ -9,6 +9,7 @@
 //   phase   = mix64(base   ^ kPhaseStream)       ali_gl_init
 //   thin    = mix64(base   ^ kThinStream)       ali_morpho_thin (the tiebreak of the thinning order; no counter)
 //   eg      = mix64(base   ^ kEgStream)         ali_eg_input (background index from hi24, mixing weight t from lo24)
+//   locate  = mix64(base   ^ kLocateStream)     ali_morpho_locate (candidate index from hi24 of hash row * 8 + draw)
 //   hash(e) = mix64(key ^ e)
 //   hi24    = bits 40..63 of a hash
 //   lo24    = bits 16..39 of a hash
@@ -24,6 +25,7 @@ constexpr uint64_t kLatentStream = 0x4C4154454E545A31ull, kGpStream = 0x47504D49
 constexpr uint64_t kGumbelStream = 0x47554D42454C3031ull, kPhaseStream = 0x474C504841534531ull;   // "GUMBEL01", "GLPHASE1"
 constexpr uint64_t kThinStream = 0x5448494E4B455931ull;                                           // "THINKEY1"
 constexpr uint64_t kEgStream = 0x4547425249445831ull;                                             // "EGBRIDX1"
+constexpr uint64_t kLocateStream = 0x534B454C4C4F4331ull;                                         // "SKELLOC1"
 constexpr float kInv24 = 1.f / 16777216.f;   // a 24-bit field times this is exact in fp32, in [0, 1)
 
 __host__ __device__ __forceinline__ uint64_t mix64(uint64_t z) {   // splitmix64's finaliser
@@ -42,6 +44,7 @@ __device__ __forceinline__ uint64_t gumbel_key(uint64_t base) { return sub_key(l
 __device__ __forceinline__ uint64_t phase_key(uint64_t base) { return sub_key(base, kPhaseStream); }
 __device__ __forceinline__ uint64_t thin_key(uint64_t base) { return sub_key(base, kThinStream); }
 __device__ __forceinline__ uint64_t eg_key(uint64_t base) { return sub_key(base, kEgStream); }
+__device__ __forceinline__ uint64_t locate_key(uint64_t base) { return sub_key(base, kLocateStream); }
 __device__ __forceinline__ uint64_t hash_at(uint64_t key, uint64_t e) { return mix64(key ^ e); }
 __device__ __forceinline__ uint32_t hi24(uint64_t r) { return (uint32_t)(r >> 40); }
 __device__ __forceinline__ uint32_t lo24(uint64_t r) { return (uint32_t)(r >> 16) & 0xFFFFFFu; }

@@ -36,6 +36,8 @@
 //   shear_reduce  SetSlant as an exact fp64 shift per row, then downscale: T = warped RWt and 255 RH T in fp64, rounded
 //             once, quantised with a guard of 1/128 grey level.
 //   set_intensity  the median of the bright pixels by `measure`'s selection, q * (target / median) clipped to 0 .. 255.
+// The local perturbations (ali_morpho_locate, ali_morpho_local; the statement is morphomnist/skeleton.py and the second
+// half of morphomnist/perturb.py) are described in front of their kernels below.
 // Every sum runs in a fixed order (ali_reduce.h): the same inputs give the same bits on every run.
 #include "ali_reduce.h"
 
@@ -733,6 +735,351 @@ morpho_set_intensity_kernel(const float* __restrict__ q, const float* __restrict
   }
 }
 
+// ---------------------------------------------------------------------------------------------- locate and local
+// The Morpho-MNIST local perturbations (ali_morpho_locate, ali_morpho_local; the statement is morphomnist/skeleton.py
+// and the second half of morphomnist/perturb.py): plain, thinning, thickening, swelling and fracture of the bitmaps,
+// from the distance map and the skeleton the measurement kernels left on the device.
+//   locate    two bitmaps in LDS, the skeleton the seeds are read from and the one the disks around them are cleared in
+//             (integer atomicAnd on LDS words: the result does not depend on the order).  Tips are found on the
+//             skeleton, forks on what the first erase left.  Candidates are counted per row; draw k is the
+//             ((hi24 * n) >> 24)-th set pixel in row-major order.  For a fracture the block then takes the six integer
+//             sums of the skeleton in the window around each centre, and thread 0 forms direction and end points in
+//             fp64 with every operation rounded on its own.
+//   local     the new bitmap is built in LDS by kind -- copy, d2 > r^2, !(d2c > r^2), the gather of the radial warp, or
+//             the bitmap less a disk around every pixel of every line -- then written with its six moment sums (what
+//             ali_morpho_shear_reduce takes for the low-resolution image).
+constexpr int kMoDraws = 8;                                          // MAX_DRAWS of ali_hip/rng.py
+constexpr int kMoStampMax = 1024;                                    // a disk radius above the diagonal of any image
+constexpr double kMoRadiusLimit = 32768.0;                           // RADIUS_LIMIT of morphomnist/perturb.py
+enum { kMoPlain = 0, kMoThin = 1, kMoThick = 2, kMoSwell = 3, kMoFracture = 4 };
+
+struct LocalParams {
+  double thin_amount, thick_amount, swell_exponent, swell_radius;
+  int frac_r, n_frac;
+};
+
+// floor(sqrt(v)), 0 <= v <= 2^21
+__device__ __forceinline__ int isqrt_floor(int v) {
+  int s = (int)sqrtf((float)v);
+  while (s * s > v) --s;
+  while ((s + 1) * (s + 1) <= v) ++s;
+  return s;
+}
+// clear, in row y of an LDS bitmap, the pixels within r of (cy, cx); the centre may lie outside the image
+__device__ __forceinline__ void stamp_row(uint32_t* bm, int Hh, int Wh, int wpr, int cy, int cx, int r, int y) {
+  const int dy = y - cy;
+  if (y < 0 || y >= Hh || dy > r || dy < -r) return;
+  const int half = isqrt_floor(r * r - dy * dy);
+  const int x_lo = max(cx - half, 0), x_hi = min(cx + half, Wh - 1);
+  if (x_lo > x_hi) return;
+  for (int w = x_lo >> 5; w <= (x_hi >> 5); ++w) {
+    const int a = max(x_lo - 32 * w, 0), b = min(x_hi - 32 * w, 31);
+    const uint32_t mask = (0xFFFFFFFFu >> (31 - b)) & (0xFFFFFFFFu << a);
+    atomicAnd(&bm[y * wpr + w], ~mask);
+  }
+}
+// erase(from = the bitmap the seeds are read in, into): the disks of radius r around the pixels of `from` with exactly
+// `want` neighbours
+__device__ void erase_around(const uint32_t* from, uint32_t* into, int Hh, int Wh, int wpr, int want, int r) {
+  const int nw = Hh * wpr;
+  for (int w = threadIdx.x; w < nw; w += kMoBlock) {
+    uint32_t u = from[w];
+    const int y = w / wpr, x0 = (w % wpr) * 32;
+    while (u) {
+      const int bit = __ffs(u) - 1;
+      u &= u - 1;
+      if (__popc(nbhd(from, Hh, wpr, y, x0 + bit) & ~16u) != want) continue;
+      for (int yy = max(y - r, 0); yy <= min(y + r, Hh - 1); ++yy) stamp_row(into, Hh, Wh, wpr, y, x0 + bit, r, yy);
+    }
+  }
+}
+
+// (cos, sin) of the major axis from the six integer sums, fp64, nothing fused: skeleton.direction
+__device__ void local_direction(const long long* q, double* c, double* s) {
+#pragma clang fp contract(off)
+  const long long n = q[0], sx = q[1], sy = q[2], sxx = q[3], sxy = q[4], syy = q[5];
+  const long long A = n * sxx - sx * sx, C = n * syy - sy * sy, Bc = n * sxy - sx * sy;
+  const double a = (double)(A - C), b = (double)(2 * Bc);
+  const double aa = a * a, bb = b * b;
+  const double h = __dsqrt_rn(aa + bb);
+  if (h == 0.0) {
+    *c = 1.0;
+    *s = 0.0;
+    return;
+  }
+  const double c2 = a / h;
+  const double up = (1.0 + c2) / 2.0, dn = (1.0 - c2) / 2.0;
+  *c = __dsqrt_rn(up);
+  *s = copysign(__dsqrt_rn(dn), b);
+}
+// the ends of the cut through (i, j): perturb.fracture_endpoints
+__device__ void local_endpoints(double c, double s, int d2, int i, int j, int scale, int* out) {
+#pragma clang fp contract(off)
+  const double ext = 0.5 * (double)scale;
+  const double L = __dsqrt_rn((double)d2) + ext;
+  const double nr = L * c, ls = L * s;
+  const double nc = -ls, fi = (double)i, fj = (double)j;
+  const double r0 = fi + nr, c0 = fj + nc, r1 = fi - nr, c1 = fj - nc;
+  out[0] = (int)r0; out[1] = (int)c0; out[2] = (int)r1; out[3] = (int)c1;
+}
+
+__global__ void __launch_bounds__(kMoBlock)
+morpho_locate_kernel(const uint32_t* __restrict__ skel, const int* __restrict__ d2, const int* __restrict__ status,
+                     const int* __restrict__ kind, int Hh, int Wh, int wpr, int scale, int r_tips, int r_forks, int num,
+                     uint64_t seed, const long long* __restrict__ dev_counter, uint64_t offset,
+                     int* __restrict__ n_cand, int* __restrict__ fallback, int* __restrict__ centres,
+                     int* __restrict__ endpoints) {
+  extern __shared__ uint32_t s_two[];
+  __shared__ int s_rows[kMoMaxSide];
+  __shared__ int s_i[kMoWaves];
+  __shared__ long long s_l[kMoWaves];
+  __shared__ int s_c[kMoDraws][2];
+  const int b = blockIdx.x, tid = threadIdx.x, nw = Hh * wpr;
+  uint32_t* from = s_two;                                            // the skeleton the seeds are read in
+  uint32_t* cand = s_two + nw;                                       // the candidates
+  const uint32_t* sk = skel + (long long)b * nw;
+  int* ce = centres + (long long)b * kMoDraws * 2;
+  int* en = endpoints + (long long)b * kMoDraws * 4;
+  if (tid < kMoDraws * 2) ce[tid] = -1;
+  if (tid < kMoDraws * 4) en[tid] = 0;
+  const int kd = kind[b];
+  if (status[b] != 0 || (kd != kMoSwell && kd != kMoFracture)) {     // (uniform)
+    if (tid == 0) {
+      n_cand[b] = 0;
+      fallback[b] = 0;
+    }
+    return;
+  }
+  const int n_draw = kd == kMoSwell ? 1 : num;
+  const int rt = kd == kMoFracture ? r_tips : -1, rf = kd == kMoFracture ? r_forks : -1;
+  for (int w = tid; w < nw; w += kMoBlock) from[w] = cand[w] = sk[w] & tail_mask(w, wpr, Wh);
+  __syncthreads();
+  if (rt >= 0) {
+    erase_around(from, cand, Hh, Wh, wpr, 1, rt);
+    __syncthreads();
+  }
+  if (rf >= 0) {
+    if (rt >= 0) {
+      for (int w = tid; w < nw; w += kMoBlock) from[w] = cand[w];
+      __syncthreads();
+    }
+    erase_around(from, cand, Hh, Wh, wpr, 3, rf);
+    __syncthreads();
+  }
+  auto count = [&]() {
+    int n = 0;
+    for (int y = tid; y < Hh; y += kMoBlock) {
+      int c = 0;
+      for (int w = 0; w < wpr; ++w) c += __popc(cand[y * wpr + w]);
+      s_rows[y] = c;
+      n += c;
+    }
+    return block_isum<kMoWaves>(n, s_i);                             // (its barriers publish s_rows)
+  };
+  int n = count(), fb = 0;
+  if (n == 0 && (rt >= 0 || rf >= 0)) {                              // overpruned: the whole skeleton (uniform)
+    for (int w = tid; w < nw; w += kMoBlock) cand[w] = sk[w] & tail_mask(w, wpr, Wh);
+    __syncthreads();
+    n = count();
+    fb = n > 0;
+  }
+  if (tid == 0) {
+    n_cand[b] = n;
+    fallback[b] = fb;
+  }
+  if (n == 0) return;                                                // (uniform)
+  if (tid < n_draw) {
+    const uint64_t key = locate_key(rng_base_key(seed, dev_counter));
+    const uint64_t e = (offset + (uint64_t)b) * (uint64_t)kMoDraws + (uint64_t)tid;
+    int idx = (int)(((uint64_t)hi24(hash_at(key, e)) * (uint64_t)n) >> 24);   // < n
+    int y = 0;
+    while (y < Hh - 1 && idx >= s_rows[y]) idx -= s_rows[y++];
+    int w = 0;
+    while (w < wpr - 1 && idx >= __popc(cand[y * wpr + w])) idx -= __popc(cand[y * wpr + w++]);
+    uint32_t u = cand[y * wpr + w];
+    for (int i = 0; i < idx; ++i) u &= u - 1;
+    const int x = 32 * w + __ffs(u) - 1;
+    s_c[tid][0] = y;
+    s_c[tid][1] = x;
+    ce[2 * tid] = y;
+    ce[2 * tid + 1] = x;
+  }
+  if (kd != kMoFracture) return;                                     // (uniform)
+  __syncthreads();
+  const int* D = d2 + (long long)b * Hh * Wh;
+  const int r = 2 * scale;                                           // the reference's _ANGLE_WINDOW
+  for (int k = 0; k < n_draw; ++k) {
+    const int ci = s_c[k][0], cj = s_c[k][1];
+    const int y_lo = max(ci - r, 0), y_hi = min(ci + r, Hh - 1), x_lo = max(cj - r, 0), x_hi = min(cj + r, Wh - 1);
+    const int w_lo = x_lo >> 5, n_w = (x_hi >> 5) - w_lo + 1;
+    long long m[6] = {0, 0, 0, 0, 0, 0};
+    for (int e = tid; e < (y_hi - y_lo + 1) * n_w; e += kMoBlock) {
+      const int y = y_lo + e / n_w, w = w_lo + e % n_w;
+      const int a = max(x_lo - 32 * w, 0), z = min(x_hi - 32 * w, 31);
+      uint32_t u = sk[y * wpr + w] & tail_mask(w, wpr, Wh) & (0xFFFFFFFFu >> (31 - z)) & (0xFFFFFFFFu << a);
+      const long long yy = y - (ci - r);
+      while (u) {
+        const int bit = __ffs(u) - 1;
+        u &= u - 1;
+        const long long xx = 32 * w + bit - (cj - r);
+        m[0] += 1; m[1] += xx; m[2] += yy; m[3] += xx * xx; m[4] += xx * yy; m[5] += yy * yy;
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 6; ++q) m[q] = waves_sum<kMoWaves>(wave_lsum(m[q]), s_l);
+    if (tid == 0) {
+      double c, s;
+      local_direction(m, &c, &s);
+      local_endpoints(c, s, D[ci * Wh + cj], ci, cj, scale, en + 4 * k);
+    }
+  }
+}
+
+// the source pixel of the radial warp for output pixel (y, x): perturb.swell
+__device__ bool swell_source(const uint32_t* bm, int Hh, int Wh, int wpr, int cy, int cx, double RR, double ex, int y,
+                             int x) {
+#pragma clang fp contract(off)
+  const int idx = x - cx, idy = y - cy;
+  const double dx = (double)idx, dy = (double)idy, dd = (double)(idx * idx + idy * idy);
+  double w = 1.0;
+  if (!(dd > RR)) {
+    const double q = dd / RR;
+    w = ex == 1.0 ? q : pow(q, ex);
+  }
+  const double wy = w * dy, wx = w * dx;
+  const double ty = (double)cy + wy, tx = (double)cx + wx;
+  const double fy = ty + 0.5, fx = tx + 0.5;
+  const double sy = floor(fy), sx = floor(fx);
+  if (!(sy >= 0.0 && sy < (double)Hh && sx >= 0.0 && sx < (double)Wh)) return false;
+  const int iy = (int)sy, ix = (int)sx;
+  return (bm[iy * wpr + (ix >> 5)] >> (ix & 31)) & 1u;
+}
+__device__ int disk_radius(double amount, int scale, double thick) {
+#pragma clang fp contract(off)
+  const double as = amount * (double)scale;
+  const double at = as * thick;
+  return (int)fmin(at / 2.0, kMoRadiusLimit);
+}
+__device__ double swelling_radius(double radius, int scale, double thick) {
+#pragma clang fp contract(off)
+  const double rs = radius * __dsqrt_rn(thick);
+  const double h = rs / 2.0;
+  return h * (double)scale;
+}
+
+__global__ void __launch_bounds__(kMoBlock)
+morpho_local_kernel(const uint32_t* __restrict__ bin, const int* __restrict__ d2, const int* __restrict__ d2c,
+                    const float* __restrict__ thickness, long long thick_ld, const int* __restrict__ status_in,
+                    const int* __restrict__ kind, const int* __restrict__ n_cand, const int* __restrict__ centres,
+                    const int* __restrict__ endpoints, LocalParams p, int Hh, int Wh, int wpr, int scale,
+                    uint32_t* __restrict__ out, int* __restrict__ radius, long long* __restrict__ sums,
+                    int* __restrict__ status_out) {
+  __shared__ uint32_t s_o[kMoMaxSide * (kMoMaxSide / 32)];
+  __shared__ long long s_l[kMoWaves];
+  const int b = blockIdx.x, tid = threadIdx.x, nw = Hh * wpr;
+  const uint32_t* bm = bin + (long long)b * nw;
+  uint32_t* ob = out + (long long)b * nw;
+  const int kd = kind[b];
+  const double thick = (double)thickness[(long long)b * thick_ld];
+  const bool nan = thick != thick;
+  int st = status_in[b], r = 0;
+  double RR = 0.0;
+  if (st == 0) {
+    if (kd == kMoThin || kd == kMoThick) {
+      if (nan || (kd == kMoThick && !d2c)) st = kMoStuck;
+      else r = disk_radius(kd == kMoThin ? p.thin_amount : p.thick_amount, scale, thick);
+    } else if (kd == kMoSwell) {
+      if (nan || n_cand[b] == 0) {
+        st = kMoStuck;
+      } else {
+        const double R = swelling_radius(p.swell_radius, scale, thick);
+        RR = __dmul_rn(R, R);
+        r = (int)fmin(R, kMoRadiusLimit);
+      }
+    } else if (kd == kMoFracture) {
+      if (n_cand[b] == 0) st = kMoStuck;
+      else r = p.frac_r;
+    } else if (kd != kMoPlain) {
+      st = kMoStuck;                                                 // not a kind
+    }
+  }
+  if (st != 0) {                                                     // (uniform)
+    for (int w = tid; w < nw; w += kMoBlock) ob[w] = 0u;
+    if (tid == 0) {
+      radius[b] = 0;
+      status_out[b] = st;
+      for (int q = 0; q < 6; ++q) sums[(long long)b * 6 + q] = 0;
+    }
+    return;
+  }
+  if (kd == kMoPlain || kd == kMoFracture) {
+    for (int w = tid; w < nw; w += kMoBlock) s_o[w] = bm[w] & tail_mask(w, wpr, Wh);
+    if (kd == kMoFracture) {
+      __syncthreads();
+      const int* en = endpoints + (long long)b * kMoDraws * 4;
+      const int rows = 2 * r + 1;
+      for (int k = 0; k < p.n_frac; ++k) {
+        const int r0 = en[4 * k], c0 = en[4 * k + 1], dr = en[4 * k + 2] - r0, dc = en[4 * k + 3] - c0;
+        const int ar = abs(dr), ac = abs(dc), m = max(ar, ac);
+        const int sr = (dr > 0) - (dr < 0), sc = (dc > 0) - (dc < 0);
+        for (int e = tid; e < (m + 1) * rows; e += kMoBlock) {
+          const int t = e / rows, dy = e % rows - r;
+          int py = r0, px = c0;
+          if (m > 0) {
+            if (ar > ac) {
+              py = r0 + sr * t;
+              px = c0 + sc * ((2 * t * ac + m) / (2 * m));
+            } else {
+              py = r0 + sr * ((2 * t * ar + m) / (2 * m));
+              px = c0 + sc * t;
+            }
+          }
+          stamp_row(s_o, Hh, Wh, wpr, py, px, r, py + dy);
+        }
+      }
+    }
+  } else {
+    const int* D = (kd == kMoThick ? d2c : d2) + (long long)b * Hh * Wh;
+    const int rr = r * r;                                            // (r <= 2^15)
+    const int cy = centres[(long long)b * kMoDraws * 2], cx = centres[(long long)b * kMoDraws * 2 + 1];
+    for (int y = 0; y < Hh; ++y)
+      for (int j0 = 0; j0 < Wh; j0 += kMoBlock) {                    // (uniform trip count: every lane reaches the ballot)
+        const int j = j0 + tid;
+        bool set = false;
+        if (j < Wh) {
+          if (kd == kMoThin) set = D[y * Wh + j] > rr;
+          else if (kd == kMoThick) set = !(D[y * Wh + j] > rr);
+          else set = swell_source(bm, Hh, Wh, wpr, cy, cx, RR, p.swell_exponent, y, j);
+        }
+        const unsigned long long bits = __ballot(set);
+        const int w0 = (j0 + (tid & ~63)) >> 5;
+        if ((tid & 63) == 0 && w0 < wpr) s_o[y * wpr + w0] = (uint32_t)bits;
+        if ((tid & 63) == 32 && w0 + 1 < wpr) s_o[y * wpr + w0 + 1] = (uint32_t)(bits >> 32);
+      }
+  }
+  __syncthreads();
+  long long m[6] = {0, 0, 0, 0, 0, 0};
+  for (int w = tid; w < nw; w += kMoBlock) {
+    uint32_t u = s_o[w];
+    ob[w] = u;
+    const long long yy = w / wpr;
+    const int x0 = (w % wpr) * 32;
+    while (u) {
+      const int bit = __ffs(u) - 1;
+      u &= u - 1;
+      const long long xx = x0 + bit;
+      m[0] += 1; m[1] += xx; m[2] += yy; m[3] += xx * xx; m[4] += xx * yy; m[5] += yy * yy;
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 6; ++q) m[q] = waves_sum<kMoWaves>(wave_lsum(m[q]), s_l);
+  if (tid == 0) {
+    radius[b] = r;
+    status_out[b] = m[0] == 0 ? kMoStuck : 0;                        // (an empty bitmap is written as it is: zeros)
+    for (int q = 0; q < 6; ++q) sums[(long long)b * 6 + q] = m[q];
+  }
+}
+
 // the side limits every entry point shares
 static int morpho_check_dims(const char* who, int32_t B, int32_t Hh, int32_t Wh) {
   if (B < 1 || Hh < 1 || Wh < 1 || Hh > kMoMaxSide || Wh > kMoMaxSide) {
@@ -925,4 +1272,82 @@ extern "C" int ali_morpho_set_intensity(const float* q, const float* target, con
   hipLaunchKernelGGL(morpho_set_intensity_kernel, dim3((unsigned)B), dim3(kMoBlock), 0, ST(stream), q, target,
                      reinterpret_cast<const int*>(status_in), (int)N, out, median, reinterpret_cast<int*>(status_out));
   return check_launch("morpho_set_intensity_kernel");
+}
+
+extern "C" int ali_morpho_locate(const uint32_t* skel, const int32_t* d2, const int32_t* status, const int32_t* kind,
+                                 int32_t B, int32_t Hh, int32_t Wh, int32_t scale, int32_t r_tips, int32_t r_forks,
+                                 int32_t num, uint64_t seed, const int64_t* dev_counter, uint64_t offset,
+                                 int32_t* n_candidates, int32_t* fallback, int32_t* centres, int32_t* endpoints,
+                                 ali_stream_t stream) {
+  if (!skel || !d2 || !status || !kind || !n_candidates || !fallback || !centres || !endpoints) {
+    set_error("ali_morpho_locate: NULL argument");
+    return ALI_ERR_BAD_ARG;
+  }
+  if (scale < 1 || scale > kMoMaxSide || num < 1 || num > kMoDraws) {
+    set_error("ali_morpho_locate: scale = %d outside [1, %d] or num = %d outside [1, %d]", (int)scale, kMoMaxSide,
+              (int)num, kMoDraws);
+    return ALI_ERR_BAD_ARG;
+  }
+  const int rc = morpho_check_dims("ali_morpho_locate", B, Hh, Wh);
+  if (rc != ALI_OK) return rc;
+  const int wpr = (Wh + 31) / 32;
+  const size_t lds = 2 * sizeof(uint32_t) * (size_t)Hh * wpr;        // <= 64 KB of the CU's 160
+  if (lds + 4096 > 64 * 1024) {                                      // (with the static arrays above the default limit)
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(morpho_locate_kernel),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             2 * (int)sizeof(uint32_t) * kMoMaxSide * (kMoMaxSide / 32));
+    if (e != hipSuccess) {
+      set_error("ali_morpho_locate: cannot raise the kernel's LDS limit: %s", hipGetErrorString(e));
+      return ALI_ERR_LAUNCH;
+    }
+  }
+  // a disk of radius kMoStampMax already covers every image: larger radii erase the same pixels
+  const int rt = r_tips < 0 ? -1 : (r_tips > kMoStampMax ? kMoStampMax : (int)r_tips);
+  const int rf = r_forks < 0 ? -1 : (r_forks > kMoStampMax ? kMoStampMax : (int)r_forks);
+  hipLaunchKernelGGL(morpho_locate_kernel, dim3((unsigned)B), dim3(kMoBlock), lds, ST(stream), skel,
+                     reinterpret_cast<const int*>(d2), reinterpret_cast<const int*>(status),
+                     reinterpret_cast<const int*>(kind), (int)Hh, (int)Wh, wpr, (int)scale, rt, rf, (int)num, seed,
+                     reinterpret_cast<const long long*>(dev_counter), offset, reinterpret_cast<int*>(n_candidates),
+                     reinterpret_cast<int*>(fallback), reinterpret_cast<int*>(centres),
+                     reinterpret_cast<int*>(endpoints));
+  return check_launch("morpho_locate_kernel");
+}
+
+extern "C" int ali_morpho_local(const uint32_t* bin, const int32_t* d2, const int32_t* d2c, const float* thickness,
+                                int64_t thickness_ld, const int32_t* status_in, const int32_t* kind,
+                                const int32_t* n_candidates, const int32_t* centres, const int32_t* endpoints,
+                                double thin_amount, double thick_amount, double swell_strength, double swell_radius,
+                                int32_t frac_radius, int32_t num_frac, int32_t B, int32_t Hh, int32_t Wh, int32_t scale,
+                                uint32_t* out, int32_t* radius, int64_t* sums, int32_t* status_out,
+                                ali_stream_t stream) {
+  if (!bin || !d2 || !thickness || !status_in || !kind || !n_candidates || !centres || !endpoints || !out || !radius ||
+      !sums || !status_out) {
+    set_error("ali_morpho_local: NULL argument");
+    return ALI_ERR_BAD_ARG;
+  }
+  if (!(thin_amount >= 0.0) || !(thick_amount >= 0.0) || !(swell_strength >= 1.0) || !(swell_radius >= 0.0) ||
+      frac_radius < 0 || frac_radius > kMoStampMax || num_frac < 1 || num_frac > kMoDraws || scale < 1 ||
+      scale > kMoMaxSide || thickness_ld < 1) {
+    set_error("ali_morpho_local: an amount or the swelling radius < 0, swell_strength < 1, frac_radius = %d outside "
+              "[0, %d], num_frac = %d outside [1, %d], scale = %d outside [1, %d] or thickness_ld = %lld < 1",
+              (int)frac_radius, kMoStampMax, (int)num_frac, kMoDraws, (int)scale, kMoMaxSide, (long long)thickness_ld);
+    return ALI_ERR_BAD_ARG;
+  }
+  const int rc = morpho_check_dims("ali_morpho_local", B, Hh, Wh);
+  if (rc != ALI_OK) return rc;
+  LocalParams p;
+  p.thin_amount = thin_amount;
+  p.thick_amount = thick_amount;
+  p.swell_exponent = (swell_strength - 1.0) / 2.0;
+  p.swell_radius = swell_radius;
+  p.frac_r = (int)frac_radius;
+  p.n_frac = (int)num_frac;
+  hipLaunchKernelGGL(morpho_local_kernel, dim3((unsigned)B), dim3(kMoBlock), 0, ST(stream), bin,
+                     reinterpret_cast<const int*>(d2), reinterpret_cast<const int*>(d2c), thickness,
+                     (long long)thickness_ld, reinterpret_cast<const int*>(status_in),
+                     reinterpret_cast<const int*>(kind), reinterpret_cast<const int*>(n_candidates),
+                     reinterpret_cast<const int*>(centres), reinterpret_cast<const int*>(endpoints), p, (int)Hh, (int)Wh,
+                     (Wh + 31) / 32, (int)scale, out, reinterpret_cast<int*>(radius), reinterpret_cast<long long*>(sums),
+                     reinterpret_cast<int*>(status_out));
+  return check_launch("morpho_local_kernel");
 }

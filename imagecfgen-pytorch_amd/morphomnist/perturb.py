@@ -1,9 +1,11 @@
 """The perturbations the measured-counterfactual scripts and the data-set builders use -- ``SetThickness``, ``SetSlant``,
-``SetIntensity`` (and ``Thinning`` / ``Thickening``) -- written on numpy and scipy alone, and the scripts' five-line chain
-for one image, ``counterfactual_image``.  This module is the *statement* the kernels ``ali_morpho_reshape``,
-``ali_morpho_shear_reduce`` and ``ali_morpho_set_intensity`` (csrc/morpho.hip) are tested against; agreement with
-scikit-image's ``dilation`` / ``pyramid_reduce`` / ``warp`` has not been checked (DESIGN 3.17 says why, and lists the
-deviations).  ``Swelling``, ``Fracture`` and ``SetWidth`` are not built.
+``SetIntensity`` -- and the four of the published Morpho-MNIST data sets -- ``Thinning``, ``Thickening``, ``Swelling``,
+``Fracture`` -- written on numpy and scipy alone, with the scripts' five-line chain for one image,
+``counterfactual_image``, and the data sets' chain, ``local_image``.  This module is the *statement* the kernels
+``ali_morpho_reshape``, ``ali_morpho_shear_reduce``, ``ali_morpho_set_intensity``, ``ali_morpho_locate`` and
+``ali_morpho_local`` (csrc/morpho.hip) are tested against; agreement with scikit-image's ``dilation`` / ``pyramid_reduce`` /
+``warp`` / ``draw.line`` has not been checked (DESIGN 3.17 and 3.20 say why, and list the deviations).  ``SetWidth`` is
+not built.
 
   footprint  ``SetThickness`` dilates / erodes by a disk of 16 r made small again: the support of zoom(gaussian(disk(16 r),
              16 / 3), (2 r + 1) / (32 r + 1), order 1).  The 16 is the reference's constant in ``_get_disk``, not the
@@ -13,6 +15,10 @@ deviations).  ``Swelling``, ``Fracture`` and ``SetWidth`` are not built.
   shear      row y of the bitmap read at column x + floor(0.5 - delta (y - cy)): nearest neighbour, constant 0.
   reduce     ``ImageMorphology.downscale``: quantise(RH bitmap RW^T) (morphomnist/morpho.py).
   intensity  clip(q * (target / median), 0, 255), the median of the pixels of q in the upper half of its range.
+  thin       ``Thinning``: d2 > r^2, r = int(amount * scale * thickness / 2); ``Thickening``: the same of the complement.
+  swell      ``Swelling``: the radial power warp around a location drawn on the skeleton, nearest neighbour, 0 outside.
+  fracture   ``Fracture``: cuts of a disk brush along digital lines across the stroke, at locations drawn on the skeleton
+             away from its tips and forks (``morphomnist.skeleton``), perpendicular to its local direction.
 """
 import functools
 
@@ -176,7 +182,7 @@ def _disk_erode(bitmap, radius):
 
 
 class Thinning(Perturbation):
-    """thin a digit by ``amount`` of its thickness: erosion by the exact disk (host only)"""
+    """thin a digit by ``amount`` of its thickness: erosion by the exact disk"""
 
     def __init__(self, amount=.7):
         self.amount = amount
@@ -187,7 +193,7 @@ class Thinning(Perturbation):
 
 
 class Thickening(Perturbation):
-    """thicken a digit by ``amount`` of its thickness: dilation by the exact disk (host only)"""
+    """thicken a digit by ``amount`` of its thickness: dilation by the exact disk"""
 
     def __init__(self, amount=1):
         self.amount = amount
@@ -307,3 +313,219 @@ def counterfactual_image(image, thickness=None, slant=None, intensity=None, scal
     return continue_from(morph.binary_image, morph.mean_thickness, H, W, thickness,
                          None if slant is None else -np.tan(np.float64(slant)), intensity, scale, morph.status, dtype,
                          max_radius)
+
+
+# ------------------------------------------------------------ the local perturbations: thin, thick, swell, fracture
+KINDS = ("plain", "thin", "thick", "swell", "fracture")              # the five Morpho-MNIST data sets, by kind number
+PLAIN, THIN, THICK, SWELL, FRACTURE = range(5)
+RADIUS_LIMIT = 2 ** 15           # a disk radius is held to this (its square exceeds every d2 of a 512 x 512 image)
+ANGLE_WINDOW, FRAC_EXTENSION = 2, .5                                 # the reference's ``Fracture`` constants
+
+
+def disk_radius(thickness, amount, scale):
+    """``Thinning`` / ``Thickening``'s radius in fp64 from the thickness as given: int(amount * scale * thickness / 2),
+    held to RADIUS_LIMIT.  None for a NaN."""
+    v = np.float64(amount) * np.float64(scale) * np.float64(thickness) / np.float64(2)
+    return None if np.isnan(v) else int(min(v, np.float64(RADIUS_LIMIT)))
+
+
+def swelling_radius(thickness, radius, scale):
+    """R = (radius * sqrt(thickness) / 2) * scale in fp64 from the thickness as given"""
+    return (np.float64(radius) * np.sqrt(np.float64(thickness)) / np.float64(2)) * np.float64(scale)
+
+
+def swell(bitmap, centre, R, strength=3):
+    """The radial warp: output pixel (y, x) reads column floor(cx + w dx + 0.5) and row floor(cy + w dy + 0.5), dx = x -
+    cx, dy = y - cy, w = (d2 / R^2) ** ((strength - 1) / 2) where d2 = dx^2 + dy^2 <= R^2 and 1 beyond; nearest
+    neighbour, 0 outside the image.  fp64, every operation rounded once; an exponent of 1 takes no ``pow``.
+    Returns (bool [H, W], the source coordinates before the floor: float64 [2, H, W] = row, column)."""
+    bitmap = np.asarray(bitmap, dtype=bool)
+    H, W = bitmap.shape
+    cy, cx = int(centre[0]), int(centre[1])
+    y, x = np.mgrid[:H, :W]
+    dy, dx = (y - cy).astype(np.float64), (x - cx).astype(np.float64)
+    d2 = ((y - cy) ** 2 + (x - cx) ** 2).astype(np.float64)
+    RR = np.float64(R) * np.float64(R)
+    e = (np.float64(strength) - np.float64(1)) / np.float64(2)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        q = d2 / RR
+        w = np.where(d2 > RR, np.float64(1), q if e == 1 else np.power(q, e))
+    fy, fx = np.float64(cy) + w * dy + np.float64(.5), np.float64(cx) + w * dx + np.float64(.5)
+    sy, sx = np.floor(fy), np.floor(fx)
+    inside = (sy >= 0) & (sy < H) & (sx >= 0) & (sx < W)
+    src = bitmap[np.clip(sy, 0, H - 1).astype(np.int64), np.clip(sx, 0, W - 1).astype(np.int64)]
+    return inside & src, np.stack([fy, fx])
+
+
+def line(p0, p1):
+    """The digital line from p0 to p1, both (row, column) and both included: int64 [m + 1, 2], m = max(|dr|, |dc|).
+    Pixel t has major coordinate major0 + sign * t (the major axis is the row when |dr| > |dc|, else the column) and
+    minor coordinate minor0 + sign * ((2 t |dminor| + m) // (2 m)), in integers."""
+    r0, c0, r1, c1 = int(p0[0]), int(p0[1]), int(p1[0]), int(p1[1])
+    dr, dc = r1 - r0, c1 - c0
+    m = max(abs(dr), abs(dc))
+    if m == 0:
+        return np.array([[r0, c0]], dtype=np.int64)
+    t = np.arange(m + 1, dtype=np.int64)
+    sr, sc = (dr > 0) - (dr < 0), (dc > 0) - (dc < 0)
+    if abs(dr) > abs(dc):
+        rows, cols = r0 + sr * t, c0 + sc * ((2 * t * abs(dc) + m) // (2 * m))
+    else:
+        rows, cols = r0 + sr * ((2 * t * abs(dr) + m) // (2 * m)), c0 + sc * t
+    return np.stack([rows, cols], axis=1)
+
+
+def fracture_radius(thickness, scale):
+    """the brush radius of ``Fracture``: max(ceil((thickness * scale - 1) / 2), 0)"""
+    return max(int(np.ceil((np.float64(thickness) * np.float64(scale) - 1) / 2)), 0)
+
+
+def fracture_endpoints(skeleton, d2, centre, scale):
+    """(r0, c0, r1, c1): the ends of the cut through ``centre``, perpendicular to the skeleton's local direction, as long
+    as the stroke is wide there plus FRAC_EXTENSION * scale to either side; truncated toward zero"""
+    from .skeleton import direction, window_sums
+    i, j = int(centre[0]), int(centre[1])
+    c, s = direction(window_sums(skeleton, i, j, ANGLE_WINDOW * int(scale)))
+    L = np.sqrt(np.float64(d2[i, j])) + np.float64(FRAC_EXTENSION * int(scale))
+    nr, nc = L * c, -(L * s)
+    fi, fj = np.float64(i), np.float64(j)
+    return tuple(int(np.trunc(v)) for v in (fi + nr, fj + nc, fi - nr, fj - nc))
+
+
+def cut(bitmap, lines, r):
+    """``bitmap`` without the pixels within squared distance r^2 of a pixel of one of ``lines`` (each [n, 2], inside the
+    image or not)"""
+    out = np.asarray(bitmap, dtype=bool).copy()
+    H, W = out.shape
+    r = int(r)
+    for pixels in lines:
+        for i, j in np.asarray(pixels).tolist():
+            lo_i, hi_i, lo_j, hi_j = max(i - r, 0), min(i + r + 1, H), max(j - r, 0), min(j + r + 1, W)
+            if lo_i >= hi_i or lo_j >= hi_j:
+                continue
+            y, x = np.mgrid[lo_i:hi_i, lo_j:hi_j]
+            out[lo_i:hi_i, lo_j:hi_j] &= (y - i) ** 2 + (x - j) ** 2 > r * r
+    return out
+
+
+class Swelling(Perturbation):
+    """A local swelling at a location drawn along the (unpruned) skeleton: the radial power warp of ``swell`` with R =
+    ``swelling_radius(thickness, radius, scale)``.  ``centre``: use this (row, column) instead of drawing."""
+
+    def __init__(self, strength=3, radius=7):
+        if not strength >= 1:
+            raise ValueError("Swelling: strength >= 1")
+        self.strength, self.radius = strength, radius
+
+    def __call__(self, morph, seed=0, counter=0, row=0, centre=None):
+        from .skeleton import LocationSampler
+        if centre is None:
+            centre = LocationSampler().sample(morph, None, seed, counter, row)
+        R = swelling_radius(morph.mean_thickness, self.radius, morph.scale)
+        return swell(morph.binary_image, centre, R, self.strength)[0]
+
+
+class Fracture(Perturbation):
+    """``num_frac`` cuts across the stroke at locations drawn along the skeleton away from its tips and forks (from the
+    whole skeleton if that leaves none), each perpendicular to the skeleton's local direction.  ``centres``: use these
+    [n, 2] (row, column) instead of drawing."""
+
+    def __init__(self, thickness=1.5, prune=2, num_frac=3):
+        from ali_hip.rng import MAX_DRAWS
+        if not 1 <= int(num_frac) <= MAX_DRAWS:
+            raise ValueError(f"Fracture: num_frac in 1 .. {MAX_DRAWS}")
+        self.thickness, self.prune, self.num_frac = thickness, prune, int(num_frac)
+
+    def centres(self, morph, seed=0, counter=0, row=0):
+        """(centres int64 [num_frac, 2], candidates drawn from, fallback)"""
+        from .skeleton import LocationSampler
+        for fallback, sampler in enumerate((LocationSampler(self.prune, self.prune), LocationSampler())):
+            n = int(sampler.candidates(morph).sum())
+            if n:
+                return sampler.sample(morph, self.num_frac, seed, counter, row), n, fallback
+        raise ValueError("Overpruned skeleton")
+
+    def __call__(self, morph, seed=0, counter=0, row=0, centres=None):
+        if centres is None:
+            centres = self.centres(morph, seed, counter, row)[0]
+        ends = [fracture_endpoints(morph.skeleton, morph.squared_distance, c, morph.scale) for c in centres]
+        return cut(morph.binary_image, [line(e[:2], e[2:]) for e in ends], fracture_radius(self.thickness, morph.scale))
+
+
+class _Given:
+    """what a perturbation reads of an ``ImageMorphology``, from given intermediates (the thickness in fp64)"""
+
+    def __init__(self, binary, d2, skeleton, thickness, scale):
+        self.binary_image, self.skeleton = np.asarray(binary, dtype=bool), np.asarray(skeleton, dtype=bool)
+        self.squared_distance = None if d2 is None else np.asarray(d2, dtype=np.int64)
+        self.mean_thickness, self.scale = np.float64(thickness), int(scale)
+
+
+def local_continue_from(binary, d2, skeleton, thickness, kind, H, W, scale=16, status=OK, dtype=np.float64, seed=0,
+                        counter=0, row=0, thin_amount=.7, thick_amount=1., swell_strength=3., swell_radius=7.,
+                        frac_thickness=1.5, frac_prune=2., num_frac=3):
+    """The chain of ``local_image`` from a binary image [H s, W s], its squared distance map, skeleton and measured
+    thickness on (the tests hand it the device's own): the dict of ``local_image``."""
+    from ali_hip.rng import MAX_DRAWS
+    if isinstance(kind, str) and kind not in KINDS:
+        raise ValueError(f"local: kind is one of {KINDS} or a kind number")
+    kind = KINDS.index(kind) if isinstance(kind, str) else int(kind)     # (a number that is no kind: status 4)
+    Hh, Wh = H * scale, W * scale
+    out = dict(bitmap=np.zeros((Hh, Wh), dtype=bool), raw=np.zeros((H, W), dtype=dtype),
+               image=np.zeros((H, W), dtype=dtype), thickness=thickness, radius=0, n_candidates=0, fallback=0,
+               centres=np.full((MAX_DRAWS, 2), -1, dtype=np.int64), endpoints=np.zeros((MAX_DRAWS, 4), dtype=np.int64),
+               status=int(status))
+    if status:
+        return out
+    m = _Given(binary, d2, skeleton, thickness, scale)
+    nan = bool(np.isnan(m.mean_thickness))
+    result = None
+    if kind == PLAIN:
+        result = m.binary_image
+    elif kind in (THIN, THICK):
+        if not nan:
+            op = Thinning(thin_amount) if kind == THIN else Thickening(thick_amount)
+            out["radius"] = disk_radius(thickness, op.amount, scale)
+            result = op(m)
+    elif kind == SWELL:
+        from .skeleton import LocationSampler
+        out["n_candidates"] = n = int(m.skeleton.sum())
+        if n:
+            out["centres"][0] = centre = LocationSampler().sample(m, None, seed, counter, row)
+            if not nan:
+                op = Swelling(swell_strength, swell_radius)
+                out["radius"] = int(min(swelling_radius(thickness, swell_radius, scale), np.float64(RADIUS_LIMIT)))
+                result = op(m, centre=centre)
+    elif kind == FRACTURE:
+        op = Fracture(frac_thickness, frac_prune, num_frac)
+        if m.skeleton.any():
+            centres, out["n_candidates"], out["fallback"] = op.centres(m, seed, counter, row)
+            out["centres"][:op.num_frac] = centres
+            out["endpoints"][:op.num_frac] = [fracture_endpoints(m.skeleton, m.squared_distance, c, scale)
+                                              for c in centres]
+            out["radius"] = fracture_radius(frac_thickness, scale)
+            result = op(m, centres=centres)
+    if result is None or not result.any():
+        out["status"] = NOTHING_LEFT
+        return out
+    out["bitmap"] = result
+    out["raw"] = dtype(255) * reduce(result, scale, dtype)
+    out["image"] = quantise_levels(out["raw"])
+    return out
+
+
+def local_image(image, kind, scale=16, threshold=.5, seed=0, dtype=np.float64, counter=0, row=0, **params):
+    """One image [H, W] through one of the five Morpho-MNIST data sets' perturbations (``kind``: a name of KINDS or its
+    number) and ``morph.downscale``.  Returns a dict: ``bitmap`` (the perturbed hi-res image), ``image`` [H, W] in 0 ..
+    255 (= ``morph.downscale(bitmap)``) and ``raw`` (255 * reduce, before the quantiser), ``thickness`` (measured),
+    ``radius`` (the disk radius of thin / thick / fracture, int(R) of a swelling, 0 for plain), ``n_candidates`` (the
+    skeleton pixels the locations were drawn from; 0 for plain / thin / thick), ``fallback`` (1: pruning left none, the
+    whole skeleton was used), ``centres`` int64 [8, 2] (-1 where unused), ``endpoints`` int64 [8, 4] = r0, c0, r1, c1 (0
+    where unused), ``status``: 0, or 1 / 2 as ``ImageMorphology`` has them, or 4 when nothing is left -- no skeleton for
+    any kind but plain, or an empty result.  A non-zero status: ``bitmap`` and ``image`` are 0.  ``params``: those of
+    ``local_continue_from``.  The draws are those of image ``row`` under (seed, counter)."""
+    image = np.asarray(image, dtype=dtype)
+    H, W = image.shape
+    morph = ImageMorphology(image, threshold, scale, seed, dtype)
+    return local_continue_from(morph.binary_image, morph.squared_distance, morph.skeleton, morph.mean_thickness, kind, H,
+                               W, scale, morph.status, dtype, seed, counter, row, **params)

@@ -860,6 +860,50 @@ int ali_morpho_shear_reduce(const uint32_t* bin, const int64_t* sums, const doub
 int ali_morpho_set_intensity(const float* q, const float* target, const int32_t* status_in, int32_t B, int32_t N,
                              float* out, float* median, int32_t* status_out, ali_stream_t stream);
 
+/* The Morpho-MNIST local perturbations (morphomnist/skeleton.py: LocationSampler, direction; morphomnist/perturb.py:
+ * Thinning, Thickening, Swelling, Fracture, local_image -- the plain / thin / thick / swelling / fractures data sets),
+ * on the bitmaps, distance maps and skeletons of the measurement kernels.  Same layout and limits; one workgroup per
+ * image; integers, integer LDS atomics (atomicAnd: order-free) and fp64 with every operation rounded on its own: the
+ * same inputs give the same bits on every run, and the integers are the statement's.  kind [B] int32: 0 plain, 1 thin,
+ * 2 thick, 3 swell, 4 fracture; another value gives status 4.  An image with a status != 0 passes through as zeros.
+ *
+ * ali_morpho_locate: skel and d2 as ali_morpho_thin / ali_morpho_edt wrote them.  Kinds 0 .. 2 and images with a status
+ *   draw nothing (n_candidates 0).  Kind 3 draws 1 location from the whole skeleton.  Kind 4 draws `num` (1 .. 8)
+ *   from the skeleton less the disks of radius r_tips around its pixels with exactly 1 neighbour (8-connected, zero
+ *   padded), then less the disks of radius r_forks around the pixels with exactly 3 neighbours of what is left (a
+ *   radius < 0: that erase is skipped; |p - q|^2 <= r^2, radius 0 clears the seeds alone); if nothing is left the
+ *   whole skeleton is used and fallback[b] = 1.  n_candidates[b]: the pixels drawn from.  Draw k is the ((hi24 *
+ *   n_candidates) >> 24)-th of them in row-major order, hi24 of hash (offset + b) * 8 + k under the "locate" key of
+ *   (seed, *dev_counter) (csrc/ali_rng.h); `offset` counts the images in front of image 0, so a call split into row
+ *   ranges draws what the whole call draws.  centres [B][8][2] int32 = (row, column), -1 where unused.  For kind 4,
+ *   endpoints [B][8][4] = (r0, c0, r1, c1), 0 where unused: with (n, sx, sy, sxx, sxy, syy) the integer sums of the
+ *   skeleton inside the (4 scale + 1)^2 window around the centre (window coordinates, outside the image 0), a = n sxx -
+ *   sx^2 - (n syy - sy^2), b = 2 (n sxy - sx sy), h = sqrt(a a + b b), cos = sqrt((1 + a / h) / 2), sin =
+ *   copysign(sqrt((1 - a / h) / 2), b) ((1, 0) when h == 0), L = sqrt(d2[centre]) + scale / 2, p0 = trunc(centre +
+ *   L (cos, -sin)), p1 = trunc(centre - L (cos, -sin)).  LDS: 8 * Hh * ceil(Wh / 32) + 2.2 KB.
+ * ali_morpho_local: thickness as ali_morpho_reshape takes it.  By kind: 0 the bitmap; 1 d2 > r^2, r = (int)min(thin_amount
+ *   * scale * thickness / 2, 2^15) in fp64; 2 !(d2c > r^2) with thick_amount, d2c the distance map of the complement
+ *   bitmap (ali_morpho_edt of ~bin with pad bits 0; NULL says no image is of kind 2: one that is gets status 4); 3 the
+ *   radial warp around centre 0: output (y, x) reads row floor(cy + w dy + 0.5) and column floor(cx + w dx + 0.5), w =
+ *   (dd / R^2) ** ((swell_strength - 1) / 2) where dd = dx^2 + dy^2 <= R^2 (no pow when the exponent is 1) and 1
+ *   beyond, R = (swell_radius * sqrt(thickness) / 2) * scale, 0 outside the image; 4 the bitmap less every pixel within
+ *   frac_radius of a pixel t = 0 .. m of the lines p0 -> p1 of the first num_frac end points, m = max(|dr|, |dc|), the
+ *   major coordinate moving by t and the minor by (2 t |dminor| + m) / (2 m) in integers; line pixels outside the image
+ *   count.  radius[b]: r, min(R, 2^15) truncated, or frac_radius.  Status 4: NaN thickness (kinds 1 .. 3), no candidate
+ *   (kinds 3, 4), or an empty result.  out has pad bits 0; sums [B][6] int64 are its moment sums (count, x, y, xx, xy,
+ *   yy), what ali_morpho_shear_reduce with target_shear NULL takes to form the low-resolution image.  frac_radius <=
+ *   1024.  LDS: 32 KB. */
+int ali_morpho_locate(const uint32_t* skel, const int32_t* d2, const int32_t* status, const int32_t* kind, int32_t B,
+                      int32_t Hh, int32_t Wh, int32_t scale, int32_t r_tips, int32_t r_forks, int32_t num, uint64_t seed,
+                      const int64_t* dev_counter, uint64_t offset, int32_t* n_candidates, int32_t* fallback,
+                      int32_t* centres, int32_t* endpoints, ali_stream_t stream);
+int ali_morpho_local(const uint32_t* bin, const int32_t* d2, const int32_t* d2c, const float* thickness,
+                     int64_t thickness_ld, const int32_t* status_in, const int32_t* kind, const int32_t* n_candidates,
+                     const int32_t* centres, const int32_t* endpoints, double thin_amount, double thick_amount,
+                     double swell_strength, double swell_radius, int32_t frac_radius, int32_t num_frac, int32_t B,
+                     int32_t Hh, int32_t Wh, int32_t scale, uint32_t* out, int32_t* radius, int64_t* sums,
+                     int32_t* status_out, ali_stream_t stream);
+
 /* Attribute plumbing of one batch (mnist.py:47-55, audio_mnist.py:203-210, whalecalls.py:455): idx[b*n_cat + j] =
  * argmax of categorical attribute j (one-hot rows of n_classes[j] floats, or int32 when cat_is_int[j]; first maximum
  * like torch.argmax); cont[b*n_cont + j] = cont_in[j][b]. */
