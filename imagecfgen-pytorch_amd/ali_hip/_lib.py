@@ -111,6 +111,7 @@ SIGNATURES = {
     "ali_bn_bwd_from_partials": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p,
                                            c_void_p, c_void_p]),
+    "ali_ew_plan": (c_int32, [c_int32, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32)]),
     "ali_bce_logits": (c_int32, [c_void_p, c_int32, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     "ali_softmax_xent": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_float, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -997,6 +997,23 @@ def bn_bwd(x, g, mask_in, mask_pre, st, gamma, B, rows_per_img, C, batch_stats, 
     return out_dgamma, out_dbeta, gx
 
 
+_EW_OPS = {"bn_stats": 0, "bn_apply": 1, "bn_bwd": 2, "bn_bwd_from_partials": 3, "colsum": 4, "act_bwd": 5}
+
+
+def ew_plan(op, rows_per_group, rows_per_img, C, ld=None, groups=1, aligned=True):
+    """(route, reduce_blocks, apply_blocks) the entry ``ali_<op>`` launches for a shape (include/ali_hip.h:
+    ali_ew_plan): route "vec" (float4 kernels) or "scalar", reduction blocks per group and blocks of the element-wise
+    pass (0 where the entry runs no such pass) -- or None when the launch refuses the shape.  ``ld`` (colsum's row
+    stride) defaults to C; ``aligned``: every tensor operand the entry names is 16-byte aligned.  Host arithmetic of the
+    library: needs no GPU."""
+    blocks = (ctypes.c_int32 * 2)(0, 0)
+    code = _lib.load().ali_ew_plan(_EW_OPS[op], rows_per_group, rows_per_img, C, C if ld is None else ld, groups,
+                                   int(bool(aligned)), blocks)
+    if code < 0:
+        return None
+    return ("vec" if code == 1 else "scalar"), blocks[0], blocks[1]
+
+
 def plane_table_grad(g, g_ch, x0, x_ch, idx, idx_col, n_rows, out=None, table=None):
     """Embedding-table gradient from the gradient ``g`` [B,H,W,Cg] of the assembled planes ``x0`` [B,H,W,Cx]
     (include/ali_hip.h: ali_plane_table_grad).  Returns / fills ``out`` [n_rows, 256].  ``table`` [n_rows, 256]: take

@@ -603,6 +603,56 @@ static int reduce_blocks_vec(long long rows, int C) {
   if (nb < 1) nb = 1;
   return (int)nb;
 }
+static int reduce_blocks(long long rows, int C) {
+  int lanes_c = 1;
+  const int cw = C < kEwBlock ? C : kEwBlock;
+  while (lanes_c < cw) lanes_c <<= 1;
+  const int lanes_r = kEwBlock / lanes_c;
+  long long nb = (rows + (long long)lanes_r * 8 - 1) / ((long long)lanes_r * 8);
+  if (nb > 512) nb = 512;
+  if (nb < 1) nb = 1;
+  return (int)nb;
+}
+
+// ---- launch plans of the stand-alone BatchNorm, column-sum and act-bwd passes: the kernel family and the grids,
+// decided ONCE per entry point and read by the launch and by the host query ali_ew_plan.  `rows`: rows of one group;
+// `aligned`: every tensor operand the entry names is 16-byte aligned.  No HIP call (the query runs without a GPU).
+struct EwPlan {
+  bool vec;   // float4 kernels: rowreduce_vec_kernel<MODE>, bn_apply_vec_kernel, bn_bwd_apply_vec_kernel
+  int nb;     // reduction blocks per group (= partial slabs), 0: the entry runs no reduction pass
+  int ew;     // blocks (grid x) of the element-wise pass, 0: the entry runs none
+};
+static int ew_plan(int op, long long rows, int rows_per_img, int C, int ld, int groups, bool aligned, EwPlan& pl) {
+  pl = EwPlan{false, 0, 0};
+  if (rows <= 0 || rows_per_img <= 0 || C <= 0 || groups < 1 || op < ALI_EW_OP_BN_STATS || op > ALI_EW_OP_ACT_BWD ||
+      (op != ALI_EW_OP_BN_STATS && op != ALI_EW_OP_BN_APPLY && groups != 1)) {
+    set_error("ali_ew_plan: bad argument (op %d)", op);
+    return ALI_ERR_BAD_ARG;
+  }
+  if ((op == ALI_EW_OP_BN_STATS || op == ALI_EW_OP_BN_BWD) && C > kEwBlock) {
+    set_error("ali_ew_plan: C must be <= 256 for the reduction passes of ali_bn_stats / ali_bn_bwd");
+    return ALI_ERR_BAD_ARG;
+  }
+  if (op == ALI_EW_OP_COLSUM && ld < C) { set_error("ali_ew_plan: ld < C"); return ALI_ERR_BAD_ARG; }
+  const long long n = rows * C;
+  if (op == ALI_EW_OP_ACT_BWD) { pl.ew = ew_grid(n); return ALI_OK; }
+  pl.vec = vec_ok(rows * groups, C) && aligned;
+  if (op == ALI_EW_OP_COLSUM) pl.vec = pl.vec && (ld % 4) == 0 && rows * ld < (1LL << 31);
+  if (op == ALI_EW_OP_BN_STATS || op == ALI_EW_OP_BN_BWD || op == ALI_EW_OP_COLSUM)
+    pl.nb = pl.vec ? reduce_blocks_vec(rows, C) : reduce_blocks(rows, C);
+  if (op == ALI_EW_OP_BN_APPLY || op == ALI_EW_OP_BN_BWD || op == ALI_EW_OP_BN_BWD_FROM_PARTIALS)
+    pl.ew = pl.vec ? ew_grid(n / 4) : ew_grid(n);
+  return ALI_OK;
+}
+
+extern "C" int32_t ali_ew_plan(int32_t op, int64_t rows_per_group, int32_t rows_per_img, int32_t C, int32_t ld,
+                               int32_t groups, int32_t aligned, int32_t* out_blocks) {
+  EwPlan pl;
+  const int rc = ew_plan(op, rows_per_group, rows_per_img, C, ld, groups, aligned != 0, pl);
+  if (rc) return rc;
+  if (out_blocks) { out_blocks[0] = pl.nb; out_blocks[1] = pl.ew; }
+  return pl.vec ? 1 : 0;
+}
 
 // ---- embedding-table gradient of the conditioning planes: one block per table cell, threads over samples.
 // Every thread first gathers the contribution of its (<= 8) samples -- all loads up front --, then the per-class sums
@@ -1230,19 +1280,11 @@ extern "C" int ali_act_bwd(const float* gy, const float* y, float* gpre, int64_t
                            ali_stream_t stream) {
   if (!gy || !y || !gpre || n < 0) { set_error("ali_act_bwd: bad argument"); return ALI_ERR_BAD_ARG; }
   if (n == 0) return ALI_OK;
-  hipLaunchKernelGGL(act_bwd_kernel, dim3(ew_grid(n)), dim3(kEwBlock), 0, ST(stream), gy, y, gpre, (long long)n, act, slope);
+  EwPlan pl;
+  const int rc = ew_plan(ALI_EW_OP_ACT_BWD, n, 1, 1, 1, 1, false, pl);
+  if (rc) return rc;
+  hipLaunchKernelGGL(act_bwd_kernel, dim3(pl.ew), dim3(kEwBlock), 0, ST(stream), gy, y, gpre, (long long)n, act, slope);
   return check_launch("act_bwd_kernel");
-}
-
-static int reduce_blocks(long long rows, int C) {
-  int lanes_c = 1;
-  const int cw = C < kEwBlock ? C : kEwBlock;
-  while (lanes_c < cw) lanes_c <<= 1;
-  const int lanes_r = kEwBlock / lanes_c;
-  long long nb = (rows + (long long)lanes_r * 8 - 1) / ((long long)lanes_r * 8);
-  if (nb > 512) nb = 512;
-  if (nb < 1) nb = 1;
-  return (int)nb;
 }
 
 extern "C" int ali_colsum(const float* x, int64_t rows, int32_t C, int32_t ld, float* out, void* ws, size_t ws_bytes,
@@ -1250,11 +1292,13 @@ extern "C" int ali_colsum(const float* x, int64_t rows, int32_t C, int32_t ld, f
   ws = ws_payload(ws);
   ws_bytes = ws_payload_bytes(ws_bytes);
   if (!x || !out || rows <= 0 || C <= 0 || ld < C) { set_error("ali_colsum: bad argument"); return ALI_ERR_BAD_ARG; }
-  const bool vec = vec_ok(rows, C) && (ld % 4) == 0 && (long long)rows * ld < (1LL << 31) && aligned16(x);
-  const int nb = vec ? reduce_blocks_vec(rows, C) : reduce_blocks(rows, C);
+  EwPlan pl;
+  const int rc = ew_plan(ALI_EW_OP_COLSUM, rows, 1, C, ld, 1, aligned16(x), pl);
+  if (rc) return rc;
+  const int nb = pl.nb;
   if (!ws || ws_bytes < (size_t)nb * C * sizeof(float)) { set_error("ali_colsum: workspace too small"); return ALI_ERR_WORKSPACE; }
   float* part = reinterpret_cast<float*>(ws);
-  if (vec)
+  if (pl.vec)
     hipLaunchKernelGGL(rowreduce_vec_kernel<2>, dim3(nb), dim3(kEwBlock), 0, ST(stream), x, (const float*)nullptr,
                        (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr,
                        (unsigned)rows, 1u, (unsigned)C, (unsigned)ld, part);
@@ -1356,11 +1400,13 @@ extern "C" int ali_bn_stats(const float* x, const float* mask, int32_t B, int32_
   }
   const int Bg = B / groups;
   const long long rows = (long long)Bg * rows_per_img;       // per group
-  const bool vec = vec_ok(rows * groups, C) && aligned16(x) && (!mask || aligned16(mask));
-  const int nb = vec ? reduce_blocks_vec(rows, C) : reduce_blocks(rows, C);
+  EwPlan pl;
+  const int rc = ew_plan(ALI_EW_OP_BN_STATS, rows, rows_per_img, C, C, groups, aligned16(x) && (!mask || aligned16(mask)), pl);
+  if (rc) return rc;
+  const int nb = pl.nb;
   if (!ws || ws_bytes < (size_t)groups * nb * 2 * C * sizeof(float)) { set_error("ali_bn_stats: workspace too small"); return ALI_ERR_WORKSPACE; }
   float* part = reinterpret_cast<float*>(ws);
-  if (training && vec)
+  if (training && pl.vec)
     hipLaunchKernelGGL(rowreduce_vec_kernel<0>, dim3(nb, groups), dim3(kEwBlock), 0, ST(stream), x, (const float*)nullptr, mask,
                        (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (unsigned)rows,
                        (unsigned)rows_per_img, (unsigned)C, (unsigned)C, part);
@@ -1401,13 +1447,17 @@ extern "C" int ali_bn_apply(const float* x, const float* sc, const float* sh, co
   }
   const int Bg = B / groups;
   const long long rows = (long long)Bg * rows_per_img, n = rows * C;   // per group
-  if (vec_ok(rows * groups, C) && aligned16(x) && aligned16(out) && (!mask_in || aligned16(mask_in)) &&
-      (!mask_post || aligned16(mask_post)))
-    hipLaunchKernelGGL(bn_apply_vec_kernel, dim3(ew_grid(n / 4), groups), dim3(kEwBlock), 0, ST(stream), x, sc, sh, mask_in,
+  EwPlan pl;
+  const int rc = ew_plan(ALI_EW_OP_BN_APPLY, rows, rows_per_img, C, C, groups,
+                         aligned16(x) && aligned16(out) && (!mask_in || aligned16(mask_in)) &&
+                             (!mask_post || aligned16(mask_post)), pl);
+  if (rc) return rc;
+  if (pl.vec)
+    hipLaunchKernelGGL(bn_apply_vec_kernel, dim3(pl.ew, groups), dim3(kEwBlock), 0, ST(stream), x, sc, sh, mask_in,
                        mask_post, out, (unsigned)rows, (unsigned)rows_per_img, (unsigned)C, (long long)stat_stride);
   else
     for (int gi = 0; gi < groups; ++gi)
-      hipLaunchKernelGGL(bn_apply_kernel, dim3(ew_grid(n)), dim3(kEwBlock), 0, ST(stream), x + (size_t)gi * n,
+      hipLaunchKernelGGL(bn_apply_kernel, dim3(pl.ew), dim3(kEwBlock), 0, ST(stream), x + (size_t)gi * n,
                          sc + gi * stat_stride, sh + gi * stat_stride, mask_in ? mask_in + (size_t)gi * Bg * C : nullptr,
                          mask_post ? mask_post + (size_t)gi * Bg * C : nullptr, out + (size_t)gi * n, n, rows_per_img, C);
   return check_launch("bn_apply_kernel");
@@ -1416,14 +1466,14 @@ extern "C" int ali_bn_apply(const float* x, const float* sc, const float* sh, co
 static void launch_bn_bwd_apply(const float* x, const float* g, const float* mask_in, const float* mask_pre,
                                 const float* mean, const float* invstd, const float* gamma, const float* dgamma,
                                 const float* dbeta, long long rows, int rows_per_img, int C, int batch_stats,
-                                float lrelu_slope, float* gx, bool vec, hipStream_t stream) {
+                                float lrelu_slope, float* gx, const EwPlan& pl, hipStream_t stream) {
   const long long n = rows * C;
-  if (vec)
-    hipLaunchKernelGGL(bn_bwd_apply_vec_kernel, dim3(ew_grid(n / 4)), dim3(kEwBlock), 0, stream, x, g, mask_in, mask_pre,
+  if (pl.vec)
+    hipLaunchKernelGGL(bn_bwd_apply_vec_kernel, dim3(pl.ew), dim3(kEwBlock), 0, stream, x, g, mask_in, mask_pre,
                        mean, invstd, gamma, dgamma, dbeta, (unsigned)rows, (unsigned)rows_per_img, (unsigned)C,
                        1.f / (float)rows, batch_stats, lrelu_slope, gx);
   else
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(ew_grid(n)), dim3(kEwBlock), 0, stream, x, g, mask_in, mask_pre, mean,
+    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(pl.ew), dim3(kEwBlock), 0, stream, x, g, mask_in, mask_pre, mean,
                        invstd, gamma, dgamma, dbeta, n, rows_per_img, C, 1.f / (float)rows, batch_stats, lrelu_slope, gx);
 }
 
@@ -1438,13 +1488,15 @@ extern "C" int ali_bn_bwd(const float* x, const float* g, const float* mask_in, 
     return ALI_ERR_BAD_ARG;
   }
   const long long rows = (long long)B * rows_per_img;
-  const bool vec = vec_ok(rows, C) && aligned16(x) && aligned16(g) && (!gx || aligned16(gx)) &&
-                   (!mask_in || aligned16(mask_in)) && (!mask_pre || aligned16(mask_pre)) && aligned16(mean) &&
-                   aligned16(invstd);
-  const int nb = vec ? reduce_blocks_vec(rows, C) : reduce_blocks(rows, C);
+  const bool aligned = aligned16(x) && aligned16(g) && (!gx || aligned16(gx)) && (!mask_in || aligned16(mask_in)) &&
+                       (!mask_pre || aligned16(mask_pre)) && aligned16(mean) && aligned16(invstd);
+  EwPlan pl;
+  const int rc = ew_plan(ALI_EW_OP_BN_BWD, rows, rows_per_img, C, C, 1, aligned, pl);
+  if (rc) return rc;
+  const int nb = pl.nb;
   if (!ws || ws_bytes < (size_t)nb * 2 * C * sizeof(float)) { set_error("ali_bn_bwd: workspace too small"); return ALI_ERR_WORKSPACE; }
   float* part = reinterpret_cast<float*>(ws);
-  if (vec)
+  if (pl.vec)
     hipLaunchKernelGGL(rowreduce_vec_kernel<1>, dim3(nb), dim3(kEwBlock), 0, ST(stream), x, g, mask_in, mask_pre, mean,
                        invstd, (unsigned)rows, (unsigned)rows_per_img, (unsigned)C, (unsigned)C, part);
   else
@@ -1453,7 +1505,7 @@ extern "C" int ali_bn_bwd(const float* x, const float* g, const float* mask_in, 
   const PartLayout lay = {0LL, 2LL * C, (long long)C, 1LL};
   hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(C), dim3(kEwBlock), 0, ST(stream), part, lay, nb, C, dgamma, dbeta);
   if (gx) launch_bn_bwd_apply(x, g, mask_in, mask_pre, mean, invstd, gamma, dgamma, dbeta, rows, rows_per_img, C,
-                              batch_stats, lrelu_slope, gx, vec, ST(stream));
+                              batch_stats, lrelu_slope, gx, pl, ST(stream));
   return check_launch("bn_bwd");
 }
 
@@ -1467,13 +1519,15 @@ extern "C" int ali_bn_bwd_from_partials(const float* part, int32_t slots, const 
     return ALI_ERR_BAD_ARG;
   }
   const long long rows = (long long)B * rows_per_img;
-  const bool vec = vec_ok(rows, C) && aligned16(x) && aligned16(g) && (!gx || aligned16(gx)) &&
-                   (!mask_in || aligned16(mask_in)) && (!mask_pre || aligned16(mask_pre)) && aligned16(mean) &&
-                   aligned16(invstd);
+  const bool aligned = aligned16(x) && aligned16(g) && (!gx || aligned16(gx)) && (!mask_in || aligned16(mask_in)) &&
+                       (!mask_pre || aligned16(mask_pre)) && aligned16(mean) && aligned16(invstd);
+  EwPlan pl;
+  const int rc = ew_plan(ALI_EW_OP_BN_BWD_FROM_PARTIALS, rows, rows_per_img, C, C, 1, aligned, pl);
+  if (rc) return rc;
   const PartLayout lay = {0LL, 1LL, (long long)C * slots, (long long)slots};
   hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(C), dim3(kEwBlock), 0, ST(stream), part, lay, slots, C, dgamma, dbeta);
   if (gx) launch_bn_bwd_apply(x, g, mask_in, mask_pre, mean, invstd, gamma, dgamma, dbeta, rows, rows_per_img, C,
-                              batch_stats, lrelu_slope, gx, vec, ST(stream));
+                              batch_stats, lrelu_slope, gx, pl, ST(stream));
   return check_launch("bn_bwd_from_partials");
 }
 

@@ -377,6 +377,22 @@ int ali_bn_bwd_from_partials(const float* part, int32_t slots, const float* x, c
                              const float* mask_pre, const float* mean, const float* invstd, const float* gamma,
                              int32_t B, int32_t rows_per_img, int32_t C, int32_t batch_stats, float lrelu_slope,
                              float* dgamma, float* dbeta, float* gx, ali_stream_t stream);
+/* Which kernels ali_bn_stats, ali_bn_apply, ali_bn_bwd, ali_bn_bwd_from_partials, ali_colsum and ali_act_bwd launch for
+ * a shape: the launches and this query read one plan.  `op` is an ALI_EW_OP_*; `rows_per_group` = B/groups *
+ * rows_per_img (ali_colsum: rows, ali_act_bwd: n with C = 1); `ld` the row stride of ali_colsum (the others: C);
+ * `groups` > 1 for stats and apply only; `aligned` = every tensor operand the entry names is 16-byte aligned.  Returns 1
+ * (float4 kernels), 0 (scalar kernels; with groups > 1 one launch per group) with out_blocks (may be NULL) = {reduction
+ * blocks per group, 0 without a reduction pass; blocks of the element-wise pass, 0 without one}, or the negative error
+ * code with which the launch would refuse the shape.  ali_bn_stats_from_partials has no route to choose (one
+ * 256-thread block per channel).  Host arithmetic only: works without a GPU. */
+#define ALI_EW_OP_BN_STATS 0
+#define ALI_EW_OP_BN_APPLY 1
+#define ALI_EW_OP_BN_BWD 2
+#define ALI_EW_OP_BN_BWD_FROM_PARTIALS 3
+#define ALI_EW_OP_COLSUM 4
+#define ALI_EW_OP_ACT_BWD 5
+int32_t ali_ew_plan(int32_t op, int64_t rows_per_group, int32_t rows_per_img, int32_t C, int32_t ld, int32_t groups,
+                    int32_t aligned, int32_t* out_blocks);
 
 /* nn.BCEWithLogitsLoss (mean) against a constant target, forward + gradient,
  * and the diagnostic sigmoid().mean() (mnist.py:181,228-248).
