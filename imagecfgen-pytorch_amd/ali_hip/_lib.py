@@ -149,6 +149,10 @@ SIGNATURES = {
                                                                           c_int64] + [c_void_p] * 5),
     "ali_ct_ce_update": (c_int32, [c_void_p, c_int32] + [c_void_p] * 8 + [c_int32] + [c_double] * 6
                          + [c_int32, c_int64, c_void_p, c_void_p, c_void_p]),
+    "ali_ct_pp_attack": (c_int32, [c_void_p] + [c_int32] * 5 + [c_void_p, c_void_p, c_double, c_void_p, c_int32,
+                                                                c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ali_ct_pp_update": (c_int32, [c_void_p, c_int32] + [c_void_p] * 3 + [c_float] + [c_void_p] * 2
+                         + [c_int32, c_double, c_double, c_double, c_int32, c_int64] + [c_void_p] * 5),
     "ali_bce_logits_pair": (c_int32, [c_void_p, c_int32, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     "ali_gp_mix": (c_int32, [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_int32, c_int64, c_void_p,
                             c_void_p, c_void_p]),

@@ -21,8 +21,17 @@ y' <= x0.  Every v' is evaluated; the best is the success with the smallest |v' 
 ``ce_statement`` is Adam (0.9 / 0.999 / 1e-8) on v:  g = c dA(f(v))/dv + gamma sign(v - x0), the same clip, the Adam
 step, the clamp to [lo, hi].  Every updated v is evaluated; the best is the success with the smallest |v - x0|_1.
 
+``cem_pp_statement`` is the pertinent positive (``'pp'``, what ``uncertainty_evolution.py`` reads) around a "no
+information" pixel value b = ``background`` (fp32, default 0): the box of pixel i is [min(b, x0_i), max(b, x0_i)];
+Apos(s) = max(0, other - own + kappa), dApos/ds = e_other - e_t0 where other - own + kappa > 0; a success is an
+iterate whose first arg-max is t0.  With ``cem_pn_statement``'s hyper-parameters and v = y = b at the start of a round,
+for k = 0 .. K-1:  g = c dApos(f(y))/dy + 2 (y - b), the same clip;  u = y - learning_rate sqrt(1 - k / K) g;
+w = u - beta / b / u + beta for u - b > beta / |u - b| <= beta / u - b < -beta;  v' = w clamped to the box;
+y' = v' + k / (k + 3) (v' - v) clamped to the box.  The best is the success with the smallest |v' - b|_2^2 +
+beta |v' - b|_1; the c table and the unfound rows are as above (x0 is always a trivial positive).
+
 What is stated is the published algorithm with omnixai's default hyper-parameters; agreement with the omnixai package
-itself has not been checked (it is not a dependency).  Pertinent positives are not built.
+itself has not been checked (it is not a dependency).
 
 ``ContrastiveSearch`` is the device executor: the searches of a batch as replays of one HIP graph, no host read
 inside.  CPU tensors and models that are no ``ClassifierStack`` run the statements.
@@ -107,6 +116,47 @@ def ce_update_statement(v, x0, gcls, m, v2, t, lr, gamma, clip, lo, hi, betas=AD
     return vn, m, v2, (vn - x0).abs().sum(dim=1), norm
 
 
+def attack_pp_statement(s, t0, c, kappa):
+    """The pertinent-positive hinge: (Apos [B], seed [B, C] = c * dApos/ds, other [B]) of logits s [B, C], labels t0 [B]
+    and constants c [B]; Apos = max(0, other - own + kappa), dApos/ds = e_other - e_t0 where that is > 0"""
+    B = s.shape[0]
+    rows = torch.arange(B, device=s.device)
+    t0 = t0.long()
+    masked = s.clone()
+    masked[rows, t0] = -math.inf
+    other = masked.argmax(dim=1)                                  # (torch.argmax: the first maximum)
+    margin = (s[rows, other] - s[rows, t0]) + kappa
+    active = margin > 0
+    seed = torch.zeros_like(s)
+    seed[rows, other] = 1
+    seed[rows, t0] = -1
+    seed = seed * (c.to(s.dtype) * active.to(s.dtype)).unsqueeze(1)
+    return torch.where(active, margin, torch.zeros_like(margin)), seed, other
+
+
+def pp_box(x0, background):
+    """(lo, hi) [B, N]: per pixel min / max of the background and x0"""
+    b = torch.full_like(x0, background)
+    return torch.minimum(b, x0), torch.maximum(b, x0)
+
+
+def pp_update_statement(v, y, x0, gcls, k, K, lr, beta, clip, background):
+    """One FISTA step of the pertinent-positive search: (v', y', l1, l2, norm) of v, y, x0 and gcls = c dApos(f(y))/dy
+    [B, N]; the shrink is centred on ``background`` (a float), the box is ``pp_box``, the distances are from the
+    background"""
+    lo, hi = pp_box(x0, background)
+    b = torch.full_like(x0, background)
+    g, norm = clip_statement(gcls + 2 * (y - b), clip)
+    u = y - lr * math.sqrt(1 - k / K) * g
+    d = u - b
+    w = torch.where(d > beta, u - beta, torch.where(d < -beta, u + beta, b))
+    vn = torch.minimum(torch.maximum(w, lo), hi)
+    yn = vn + (k / (k + 3)) * (vn - v)
+    yn = torch.minimum(torch.maximum(yn, lo), hi)
+    diff = vn - b
+    return vn, yn, diff.abs().sum(dim=1), diff.pow(2).sum(dim=1), norm
+
+
 def c_table_statement(c, c_lo, c_hi, success):
     """The binary search on c after a round: (c, c_lo, c_hi) [B] of the same and ``success`` [B] bool"""
     hi_s = torch.minimum(c_hi, c)
@@ -124,21 +174,28 @@ def row_bounds(x0, bounds):
     return torch.full_like(x0[:, 0], float(lo)), torch.full_like(x0[:, 0], float(hi))
 
 
-def class_gradient(f, point, t0, c, kappa):
-    """c * dA(f(point))/dpoint in the shape of ``point`` (autograd through ``f``)"""
+def class_gradient(f, point, t0, c, kappa, attack=attack_statement):
+    """c * dA(f(point))/dpoint in the shape of ``point`` (autograd through ``f``; ``attack``: the hinge's statement,
+    ``attack_pp_statement`` for pertinent positives)"""
     with torch.enable_grad():
         p = point.detach().requires_grad_(True)
         s = f(p)
-        _, seed, _ = attack_statement(s.detach(), t0, c, kappa)
+        _, seed, _ = attack(s.detach(), t0, c, kappa)
         g, = torch.autograd.grad(s, p, seed)
     return g.detach()
 
 
-def _search(f, x, mode, hp, bounds, record):
+def as_fp32(value):
+    """a Python float that is an fp32 value: the background as the kernels take it"""
+    return float(torch.tensor(float(value), dtype=torch.float32))
+
+
+def _search(f, x, mode, hp, bounds, record, background=None):
     x = x.detach()
     B, shape = x.shape[0], x.shape
     x0 = x.reshape(B, -1)
     K, rounds = hp["num_iterations"], hp["binary_search_steps"]
+    fista = mode in ("pn", "pp")
     with torch.no_grad():
         t0 = f(x).argmax(dim=1)
     lo, hi = row_bounds(x0, bounds)
@@ -147,21 +204,29 @@ def _search(f, x, mode, hp, bounds, record):
     best, best_dist = x0.clone(), torch.full_like(lo, math.inf)
     best_label, found = t0.clone(), torch.zeros(B, dtype=torch.bool, device=x.device)
     for r in range(rounds):
-        v, y = x0.clone(), x0.clone()
+        if mode == "pp":
+            v, y = torch.full_like(x0, background), torch.full_like(x0, background)
+        else:
+            v, y = x0.clone(), x0.clone()
         m, v2 = torch.zeros_like(x0), torch.zeros_like(x0)
         round_succ = torch.zeros(B, dtype=torch.bool, device=x.device)
         for k in range(K):
-            gcls = class_gradient(f, (y if mode == "pn" else v).reshape(shape), t0, c, hp["kappa"]).reshape(B, -1)
+            gcls = class_gradient(f, (y if fista else v).reshape(shape), t0, c, hp["kappa"],
+                                  attack_pp_statement if mode == "pp" else attack_statement).reshape(B, -1)
             if mode == "pn":
                 v, y, l1, l2, _ = cem_update_statement(v, y, x0, gcls, k, K, hp["learning_rate"], hp["beta"],
                                                        hp["grad_clip"], lo, hi)
+                dist = l2 + hp["beta"] * l1
+            elif mode == "pp":
+                v, y, l1, l2, _ = pp_update_statement(v, y, x0, gcls, k, K, hp["learning_rate"], hp["beta"],
+                                                      hp["grad_clip"], background)
                 dist = l2 + hp["beta"] * l1
             else:
                 v, m, v2, dist, _ = ce_update_statement(v, x0, gcls, m, v2, k + 1, hp["learning_rate"], hp["gamma"],
                                                         hp["grad_clip"], lo, hi)
             with torch.no_grad():
                 pred = f(v.reshape(shape)).argmax(dim=1)
-            succ = pred != t0
+            succ = pred == t0 if mode == "pp" else pred != t0
             better = succ & (dist < best_dist)
             best = torch.where(better.unsqueeze(1), v, best)
             best_dist = torch.where(better, dist, best_dist)
@@ -188,32 +253,51 @@ def ce_statement(f, x, bounds=None, record=None, **hyper):
     return _search(f, x, "ce", hyper_parameters("ce", hyper), bounds, record)
 
 
+def cem_pp_statement(f, x, background=0.0, record=None, **hyper):
+    """Pertinent positives of x [B, ...] under the logits ``f`` around the "no information" value ``background`` (an
+    fp32 scalar; module docstring), with the hyper-parameters and defaults of ``cem_pn_statement``; returns what
+    ``cem_pn_statement`` does, ``dist`` measured from the background."""
+    return _search(f, x, "pp", hyper_parameters("pn", hyper), None, record, as_fp32(background))
+
+
 # ---------------------------------------------------------------------- the device executor
 class ContrastiveSearch:
     """``run(x [B,1,H,W] cuda)`` -> {"image" [B,1,H,W], "label" [B] int32, "found" [B] int32, "dist" [B], "c" [B]} on the
-    device, without a host read: ``mode`` "pn" is ``cem_pn_statement``, "ce" is ``ce_statement``, B rows as B searches.
+    device, without a host read: ``mode`` "pn" is ``cem_pn_statement``, "ce" is ``ce_statement``, "pp" is
+    ``cem_pp_statement`` around ``background`` (default 0.0; "pp" only), B rows as B searches.
 
     One replay of the recorded graph at iteration counter k (device memory, per row) is: the classifier's forward chain
-    over the iterates v_k (and, "pn", the slack rows y_k behind them: one chain call of 2B rows), ``ali_ct_attack``
-    (evaluation of v_k, seed at the gradient point), ``ali_ct_book`` (best so far; at k == K the move of c), the
-    chain's data-gradient pass over the gradient point's rows (``need_params=False``: no parameter or ``.grad`` is
-    touched) and the mode's update kernel (k < K: the step to v_(k+1); k == K: the next round starts from x0).  A round
-    is K + 1 replays, a search ``binary_search_steps`` * (K + 1); the graph is recorded once per (B, H, W, mode,
-    hyper-parameters, module mode).
+    over the iterates v_k (and, "pn" / "pp", the slack rows y_k behind them: one chain call of 2B rows),
+    ``ali_ct_attack`` (``ali_ct_pp_attack`` in "pp"; evaluation of v_k, seed at the gradient point), ``ali_ct_book``
+    (best so far; at k == K the move of c), the chain's data-gradient pass over the gradient point's rows
+    (``need_params=False``: no parameter or ``.grad`` is touched) and the mode's update kernel (k < K: the step to
+    v_(k+1); k == K: the next round starts from x0, in "pp" from the background).  A round is K + 1 replays, a search
+    ``binary_search_steps`` * (K + 1); the graph is recorded once per (B, H, W, mode, hyper-parameters, bounds,
+    background, module mode).
 
-    The classifier must be a ``ClassifierStack`` (``TypeError`` otherwise) in eval mode and, for "pn", without
+    The classifier must be a ``ClassifierStack`` (``TypeError`` otherwise) in eval mode and, for "pn" and "pp", without
     BatchNorm layers (``ValueError``: the slack rows' gradient is taken from a 2B-row pass); CPU tensors are refused
-    (the statements serve them).  t0 is the first arg-max of the logits of x0 in a pass of the batch shape the replays
-    use (2B rows for "pn", B for "ce").  ``start`` / ``advance`` / ``result`` are ``run`` in pieces (tests, inspection)."""
+    (the statements serve them), and so are ``bounds`` in "pp" and ``background`` in "pn" / "ce" (``ValueError``).  t0 is
+    the first arg-max of the logits of x0 in a pass of the batch shape the replays use (2B rows for "pn" / "pp", B for
+    "ce").  ``start`` / ``advance`` / ``result`` are ``run`` in pieces (tests, inspection)."""
 
-    def __init__(self, classifier, mode="pn", capture=True, bounds=None, **hyper):
+    def __init__(self, classifier, mode="pn", capture=True, bounds=None, background=None, **hyper):
         self.pipe = DecodeClassify(classifier)
         self.classifier, self.mode, self.capture = classifier, mode, capture
-        self.hp = hyper_parameters(mode, hyper)
+        self.hp = hyper_parameters("pn" if mode == "pp" else mode, hyper)
+        if mode == "pp":
+            if bounds is not None:
+                raise ValueError("ContrastiveSearch: mode 'pp' takes its box from x0 and the background; bounds are "
+                                 "for 'pn' / 'ce'")
+            background = as_fp32(0.0 if background is None else background)
+        elif background is not None:
+            raise ValueError(f"ContrastiveSearch: background belongs to mode 'pp', not {mode!r}")
+        self.background = background
         self.bounds = None if bounds is None else (float(bounds[0]), float(bounds[1]))
         self._check_eval()
-        if mode == "pn" and any(isinstance(m, torch.nn.modules.batchnorm._BatchNorm) for m in classifier.modules()):
-            raise ValueError("ContrastiveSearch: mode 'pn' takes the data gradient over the slack rows of a 2B-row "
+        if mode in ("pn", "pp") and any(isinstance(m, torch.nn.modules.batchnorm._BatchNorm)
+                                        for m in classifier.modules()):
+            raise ValueError(f"ContrastiveSearch: mode {mode!r} takes the data gradient over the slack rows of a 2B-row "
                              "forward pass, which needs a classifier without BatchNorm layers")
         self._graphs = GraphCache(modules=[classifier])
         self._state = {}
@@ -230,7 +314,7 @@ class ContrastiveSearch:
         key = (B, H, W, str(device))
         st = self._state.get(key)
         if st is None:
-            N, R = H * W, (2 * B if self.mode == "pn" else B)
+            N, R = H * W, (2 * B if self.mode in ("pn", "pp") else B)
             f = dict(dtype=torch.float32, device=device)
             i = dict(dtype=torch.int32, device=device)
             st = self._state[key] = dict(
@@ -252,19 +336,25 @@ class ContrastiveSearch:
 
     # ---- what the graph records: one replay
     def _iter(self, st, x0, lo, hi, t0):
-        B, N, hp, pn = st["B"], st["N"], self.hp, self.mode == "pn"
+        B, N, hp, pp = st["B"], st["N"], self.hp, self.mode == "pp"
+        fista = self.mode in ("pn", "pp")
         rows = st["rows"]
         R = rows.shape[0]
         lg, saved = self.pipe.classify(rows, save=True)
         flat = rows.reshape(R, N)
         v = flat[:B]
-        seed, A, pred, succ = ops.ct_attack(lg, B, t0, st["ctab"][0], hp["kappa"], 0, B if pn else 0)
-        dist = st["dist"] if pn else st["l1"]
+        attack = ops.ct_pp_attack if pp else ops.ct_attack
+        seed, A, pred, succ = attack(lg, B, t0, st["ctab"][0], hp["kappa"], 0, B if fista else 0)
+        dist = st["dist"] if fista else st["l1"]
         ops.ct_book(v, dist, succ, pred, st["it"], hp["num_iterations"], st["best"], st["best_dist"], st["best_label"],
                     st["found"], st["round_succ"], st["ctab"], st["copied"])
-        # "pn": the slack rows alone -- rows of a stack without BatchNorm are independent
-        gx = self.pipe.image_grad(saved, seed, rows=(B, 2 * B) if pn else None)
-        if pn:
+        # "pn" / "pp": the slack rows alone -- rows of a stack without BatchNorm are independent
+        gx = self.pipe.image_grad(saved, seed, rows=(B, 2 * B) if fista else None)
+        if pp:
+            ops.ct_pp_update(gx, v, flat[B:], x0, self.background, st["it"], st["rnd"], hp["num_iterations"],
+                             hp["learning_rate"], hp["beta"], hp["grad_clip"], st["l1"], st["l2"], st["dist"],
+                             st["gnorm"])
+        elif fista:
             ops.ct_cem_update(gx, v, flat[B:], x0, lo, hi, st["it"], st["rnd"], hp["num_iterations"],
                               hp["learning_rate"], hp["beta"], hp["grad_clip"], st["l1"], st["l2"], st["dist"],
                               st["gnorm"])
@@ -299,6 +389,8 @@ class ContrastiveSearch:
         logits, _ = self.pipe.classify(rows, save=True)                                          # (as a replay's)
         _, _, t0, _ = ops.ct_attack(logits, B)
         st["t0"].copy_(t0)
+        if self.mode == "pp":                                       # the iterates start from the background
+            rows.fill_(self.background)
         st["ctab"][0].fill_(self.hp["c0"])
         st["ctab"][1].zero_()
         st["ctab"][2].fill_(C_HI0)
@@ -325,7 +417,8 @@ class ContrastiveSearch:
             for _ in range(n):
                 self._iter(st, *args)
             return
-        extra = (st["key"], self.mode, tuple(sorted(self.hp.items())), self.bounds, self.classifier.training)
+        extra = (st["key"], self.mode, tuple(sorted(self.hp.items())), self.bounds, self.background,
+                 self.classifier.training)
         self._graphs(lambda *a: self._iter(st, *a), args, extra, self._mutable(st))
         self._graphs.replay(args, extra, n - 1)                           # the inputs are in place: replay only
 

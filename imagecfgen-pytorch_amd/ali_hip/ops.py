@@ -1863,6 +1863,43 @@ def ct_cem_update(gx, v, y, x0, lo, hi, it, rnd, K, lr, beta, clip, l1, l2, dist
                                      _stream()), "ali_ct_cem_update")
 
 
+def ct_pp_attack(logit, B, t0, c, kappa=0.0, eval_off=0, grad_off=0, seed_ld=None):
+    """``ct_attack`` of the pertinent-positive search (include/ali_hip.h: ali_ct_pp_attack): succ = (pred == t0), the
+    hinge max(0, other - own + kappa) and its seed c * (e_other - e_t0).  t0 is required.  Returns (seed [B, seed_ld],
+    A [B], pred [B] int32, succ [B] int32)."""
+    lib = _lib.load()
+    if logit.dim() != 2:
+        raise ValueError(f"ct_pp_attack: need [R, C] logits, got {tuple(logit.shape)}")
+    R, C = logit.shape
+    B = int(B)
+    dev = logit.device
+    ld = C if seed_ld is None else int(seed_ld)
+    seed = torch.empty(B, ld, dtype=torch.float32, device=dev)
+    A = torch.empty(B, dtype=torch.float32, device=dev)
+    pred = torch.empty(B, dtype=torch.int32, device=dev)
+    succ = torch.empty(B, dtype=torch.int32, device=dev)
+    _lib.check(lib.ali_ct_pp_attack(_chk(logit, "logit"), R, C, B, int(eval_off), int(grad_off), _i32(t0, "t0", B),
+                                    _ct_f32(c, B, "c"), float(kappa), _chk(seed, "seed"), ld, _chk(A, "A"),
+                                    _i32(pred, "pred"), _i32(succ, "succ"), _stream()), "ali_ct_pp_attack")
+    return seed, A, pred, succ
+
+
+def ct_pp_update(gx, v, y, x0, background, it, rnd, K, lr, beta, clip, l1, l2, dist, gnorm):
+    """One FISTA step of the pertinent-positive search on every row, or the start of the next round (v = y = the
+    background) where it == K (include/ali_hip.h: ali_ct_pp_update): gx the classifier's input gradient at y ([B, N]
+    or NHWC [B, H, W, Cpad], plane 0), v / y / x0 [B, N], ``background`` a float (used as fp32), everything else [B].
+    In place."""
+    lib = _lib.load()
+    B = v.shape[0]
+    N = v.numel() // B
+    g, gs = _ct_gx(gx, B, N, "ct_pp_update")
+    _lib.check(lib.ali_ct_pp_update(g, gs, _chk(v, "v"), _ct_f32(y, B * N, "y"), _ct_f32(x0, B * N, "x0"),
+                                    float(background), _i32(it, "it", B), _i32(rnd, "rnd", B), int(K), float(lr),
+                                    float(beta), float(clip), B, N, _ct_f32(l1, B, "l1"), _ct_f32(l2, B, "l2"),
+                                    _ct_f32(dist, B, "dist"), _ct_f32(gnorm, B, "gnorm"), _stream()),
+               "ali_ct_pp_update")
+
+
 def ct_ce_update(gx, v, x0, lo, hi, m, v2, it, rnd, K, lr, gamma, clip, l1, gnorm, betas=(0.9, 0.999), eps=1e-8):
     """One Adam step of the counterfactual search on every row, or the start of the next round where it == K
     (include/ali_hip.h: ali_ct_ce_update): gx the classifier's input gradient at v, v / x0 / m / v2 [B, N].  In place."""

@@ -1,17 +1,19 @@
-// The contrastive family (include/ali_hip.h: ali_ct_attack, ali_ct_book, ali_ct_cem_update, ali_ct_ce_update): what sits
-// around the classifier's conv chain when the pertinent-negative search of the contrastive explanation method
-// (Dhurandhar et al. 2018) and the counterfactual search of Wachter et al. 2017 run B rows as B independent searches.
-// The chain carries all the arithmetic that matters; these four are bound by the launch (a row is a 28 x 28 image, a
+// The contrastive family (include/ali_hip.h: ali_ct_attack, ali_ct_book, ali_ct_cem_update, ali_ct_ce_update,
+// ali_ct_pp_attack, ali_ct_pp_update): what sits around the classifier's conv chain when the pertinent-negative and
+// pertinent-positive searches of the contrastive explanation method (Dhurandhar et al. 2018) and the counterfactual
+// search of Wachter et al. 2017 run B rows as B independent searches.
+// The chain carries all the arithmetic that matters; these six are bound by the launch (a row is a 28 x 28 image, a
 // logit row ten numbers), so the row arithmetic is fp64 -- every fp32 result is the rounding of an fp64 evaluation --
 // and every sum runs in a fixed order (ali_reduce.h).  No float atomics, no host reads, no allocation: the same inputs
 // give the same bits.  Everything that decides what a launch does -- the iteration of the round, the round, the row's
 // c -- is read from device memory, so ONE recorded graph serves every iteration of every round.
 //
 // One replay at iteration counter k = it[b] (0 <= k <= K):
-//   ali_ct_attack       logits of the iterate v_k (evaluation) and of the gradient point (seed of the data gradient)
+//   ali_ct_(pp_)attack  logits of the iterate v_k (evaluation) and of the gradient point (seed of the data gradient)
 //   ali_ct_book         v_k into the best-so-far (k >= 1); at k == K the row's c / c_lo / c_hi move
 //   ali_ct_*_update     k <  K: the step to v_(k+1), its distances, it[b] = k + 1
-//                       k == K: the round is over: v (y, the moments) start again from x0, it[b] = 0, rnd[b] += 1
+//                       k == K: the round is over: v (y, the moments) start again from x0 (pp: from the background),
+//                       it[b] = 0, rnd[b] += 1
 // ali_ct_book runs before the update, so both see the same k.
 //
 // NaN (what falls out, untested): comparisons with NaN are false, so a NaN logit never becomes the arg-max, a NaN
@@ -28,37 +30,75 @@ constexpr int kCtWaves = kCtBlock / 64;
 // ---------------------------------------------------------------------------------------------------- ali_ct_attack
 // One thread per search row b (the eg_seed argument: C is ten, a wave per row would idle 54 lanes).  Strict > in
 // ascending column order keeps the first maximum, as ali_softmax_xent does.
+__device__ __forceinline__ int ct_argmax(const float* __restrict__ z, int C) {
+  float zmax = -INFINITY;
+  int zi = 0;                                                        // (a row of -inf / NaN only: column 0)
+  for (int j = 0; j < C; ++j) {
+    const float zv = z[j];
+    if (zv > zmax) { zmax = zv; zi = j; }
+  }
+  return zi;
+}
+
+// the first largest column other than t (t in [0, C), C >= 2)
+__device__ __forceinline__ int ct_other(const float* __restrict__ z, int C, int t) {
+  float omax = -INFINITY;
+  int oi = t == 0 ? 1 : 0;
+  for (int j = 0; j < C; ++j) {
+    const float zv = z[j];
+    if (j != t && zv > omax) { omax = zv; oi = j; }
+  }
+  return oi;
+}
+
+__device__ __forceinline__ int ct_clamp_label(int tg, int C) {
+  return tg < 0 ? 0 : (tg >= C ? C - 1 : tg);                        // (a label outside [0, C) reads no other row)
+}
+
 __global__ void __launch_bounds__(kCtBlock)
 ct_attack_kernel(const float* __restrict__ logit, int C, int B, int eval_off, int grad_off,
                  const int* __restrict__ t0, const float* __restrict__ c, double kappa, float* __restrict__ seed,
                  int seed_ld, float* __restrict__ A, int* __restrict__ pred, int* __restrict__ succ) {
   const int b = blockIdx.x * kCtBlock + threadIdx.x;
   if (b >= B) return;
-  const float* ze = logit + (long long)(eval_off + b) * C;
-  float zmax = -INFINITY;
-  int zi = 0;                                                        // (a row of -inf / NaN only: column 0)
-  for (int j = 0; j < C; ++j) {
-    const float zv = ze[j];
-    if (zv > zmax) { zmax = zv; zi = j; }
-  }
+  const int zi = ct_argmax(logit + (long long)(eval_off + b) * C, C);
   pred[b] = zi;
   if (!t0) return;
   const int tg = t0[b];
   succ[b] = zi != tg ? 1 : 0;
-  const int t = tg < 0 ? 0 : (tg >= C ? C - 1 : tg);                 // (a label outside [0, C) reads no other row)
+  const int t = ct_clamp_label(tg, C);
   const float* zg = logit + (long long)(grad_off + b) * C;
-  float omax = -INFINITY;
-  int oi = t == 0 ? 1 : 0;
-  for (int j = 0; j < C; ++j) {
-    const float zv = zg[j];
-    if (j != t && zv > omax) { omax = zv; oi = j; }
-  }
+  const int oi = ct_other(zg, C, t);
   const double margin = ((double)zg[t] - (double)zg[oi]) + kappa;
   const bool active = margin > 0.0;
   A[b] = active ? (float)margin : 0.f;
   const float cv = c[b];
   float* sr = seed + (long long)b * seed_ld;
   for (int j = 0; j < seed_ld; ++j) sr[j] = !active ? 0.f : (j == t ? cv : (j == oi ? -cv : 0.f));
+}
+
+// --------------------------------------------------------------------------------------------- ali_ct_pp_attack
+// The pertinent-positive hinge: the sense turned round.  A success keeps t0; A = max(0, other - own +
+// kappa) and its seed c (e_other - e_t0).  t0 is required.
+__global__ void __launch_bounds__(kCtBlock)
+ct_pp_attack_kernel(const float* __restrict__ logit, int C, int B, int eval_off, int grad_off,
+                    const int* __restrict__ t0, const float* __restrict__ c, double kappa, float* __restrict__ seed,
+                    int seed_ld, float* __restrict__ A, int* __restrict__ pred, int* __restrict__ succ) {
+  const int b = blockIdx.x * kCtBlock + threadIdx.x;
+  if (b >= B) return;
+  const int zi = ct_argmax(logit + (long long)(eval_off + b) * C, C);
+  pred[b] = zi;
+  const int tg = t0[b];
+  succ[b] = zi == tg ? 1 : 0;
+  const int t = ct_clamp_label(tg, C);
+  const float* zg = logit + (long long)(grad_off + b) * C;
+  const int oi = ct_other(zg, C, t);
+  const double margin = ((double)zg[oi] - (double)zg[t]) + kappa;
+  const bool active = margin > 0.0;
+  A[b] = active ? (float)margin : 0.f;
+  const float cv = c[b];
+  float* sr = seed + (long long)b * seed_ld;
+  for (int j = 0; j < seed_ld; ++j) sr[j] = !active ? 0.f : (j == oi ? cv : (j == t ? -cv : 0.f));
 }
 
 // ------------------------------------------------------------------------------------------------------ ali_ct_book
@@ -230,6 +270,95 @@ ct_cem_update_kernel(const float* __restrict__ gx, int gs, float* __restrict__ v
   }
 }
 
+// FISTA step of the pertinent-positive search ("Pertinent positives"): ct_cem_update_kernel's shape with
+// the shrink centred on the background b and the box [min(b, x0_i), max(b, x0_i)] per pixel.  b, x0_i and the box ends
+// are fp32 values, so a pixel clamped to an end or shrunk to b stores that float itself.
+template <int V>
+__global__ void __launch_bounds__(kCtBlock)
+ct_pp_update_kernel(const float* __restrict__ gx, int gs, float* __restrict__ v, float* __restrict__ y,
+                    const float* __restrict__ x0, float bg, int* __restrict__ it, int* __restrict__ rnd, int K,
+                    double lr, double beta, double clip, long long N, float* __restrict__ l1, float* __restrict__ l2,
+                    float* __restrict__ dist, float* __restrict__ gnorm) {
+  __shared__ double s_red[kCtWaves];
+  const long long b = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int k = it[b];
+  __syncthreads();                                                   // every wave has read it[b] before thread 0 moves it
+  float* vr = v + b * N;
+  float* yr = y + b * N;
+  const float* xr = x0 + b * N;
+  const float* gr = gx + b * N * gs;
+  if (k >= K) {                                                      // the round is over: start again from b
+    Vec<V> bv;
+#pragma unroll
+    for (int j = 0; j < V; ++j) bv.e[j] = bg;
+    for (long long i = (long long)tid * V; i < N; i += kCtBlock * V) {
+      bv.store(vr + i);
+      bv.store(yr + i);
+    }
+    if (tid == 0) {
+      it[b] = 0;
+      rnd[b] += 1;
+      l1[b] = 0.f; l2[b] = 0.f; dist[b] = 0.f;
+    }
+    return;
+  }
+  const double bd = (double)bg;
+  double ss = 0.0;
+  for (long long i = (long long)tid * V; i < N; i += kCtBlock * V) {
+    Vec<V> yv;
+    yv.load(yr + i);
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      const double g = (double)gr[(i + j) * gs] + 2.0 * ((double)yv.e[j] - bd);
+      ss += g * g;
+    }
+  }
+  ss = block_sum<kCtWaves>(ss, s_red);
+  const double norm = sqrt(ss);
+  const double scale = norm > clip ? clip / norm : 1.0;
+  const double step = lr * sqrt(1.0 - (double)k / (double)K);
+  const double mom = (double)k / (double)(k + 3);
+  double a1 = 0.0, a2 = 0.0;
+  for (long long i = (long long)tid * V; i < N; i += kCtBlock * V) {
+    Vec<V> xv, yv, vv;
+    xv.load(xr + i);
+    yv.load(yr + i);
+    vv.load(vr + i);
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      const double x = (double)xv.e[j], yo = (double)yv.e[j];
+      const double lo = fmin(bd, x), hi = fmax(bd, x);
+      const double g = ((double)gr[(i + j) * gs] + 2.0 * (yo - bd)) * scale;
+      const double u = yo - step * g;
+      const double d = u - bd;
+      double w = bd;                                                 // shrink around b
+      if (d > beta) w = u - beta;
+      else if (d < -beta) w = u + beta;
+      const double vn = w < lo ? lo : (w > hi ? hi : w);            // into the box
+      const double ym = vn + mom * (vn - (double)vv.e[j]);
+      const double yn = ym < lo ? lo : (ym > hi ? hi : ym);
+      const float vf = (float)vn;
+      yv.e[j] = (float)yn;
+      vv.e[j] = vf;
+      const double df = (double)vf - bd;                             // the distances of the iterate as stored
+      a1 += fabs(df);
+      a2 += df * df;
+    }
+    vv.store(vr + i);
+    yv.store(yr + i);
+  }
+  a1 = block_sum<kCtWaves>(a1, s_red);
+  a2 = block_sum<kCtWaves>(a2, s_red);
+  if (tid == 0) {
+    l1[b] = (float)a1;
+    l2[b] = (float)a2;
+    dist[b] = (float)(a2 + beta * a1);
+    gnorm[b] = (float)norm;
+    it[b] = k + 1;
+  }
+}
+
 // Adam step of the counterfactual search
 template <int V>
 __global__ void __launch_bounds__(kCtBlock)
@@ -363,6 +492,26 @@ extern "C" int ali_ct_attack(const float* logit, int32_t R, int32_t C, int32_t B
   return check_launch("ct_attack_kernel");
 }
 
+extern "C" int ali_ct_pp_attack(const float* logit, int32_t R, int32_t C, int32_t B, int32_t eval_off,
+                                int32_t grad_off, const int32_t* t0, const float* c, double kappa, float* seed,
+                                int32_t seed_ld, float* A, int32_t* pred, int32_t* succ, ali_stream_t stream) {
+  if (B < 1 || C < 2 || C > 1024 || eval_off < 0 || grad_off < 0 || (long long)eval_off + B > R ||
+      (long long)grad_off + B > R || (long long)R * C >= (1LL << 31)) {
+    set_error("ali_ct_pp_attack: B = %d, C = %d outside [2, 1024], or the rows [%d, %d + B) / [%d, %d + B) leave the "
+              "%d logit rows", (int)B, (int)C, (int)eval_off, (int)eval_off, (int)grad_off, (int)grad_off, (int)R);
+    return ALI_ERR_BAD_ARG;
+  }
+  if (!logit || !pred || !t0 || !c || !seed || !A || !succ || seed_ld < C || (long long)B * seed_ld >= (1LL << 31)) {
+    set_error("ali_ct_pp_attack: no pointer may be NULL and seed_ld = %d must be at least C = %d", (int)seed_ld, (int)C);
+    return ALI_ERR_BAD_ARG;
+  }
+  hipLaunchKernelGGL(ct_pp_attack_kernel, dim3((unsigned)((B + kCtBlock - 1) / kCtBlock)), dim3(kCtBlock), 0,
+                     ST(stream), logit, (int)C, (int)B, (int)eval_off, (int)grad_off,
+                     reinterpret_cast<const int*>(t0), c, kappa, seed, (int)seed_ld, A, reinterpret_cast<int*>(pred),
+                     reinterpret_cast<int*>(succ));
+  return check_launch("ct_pp_attack_kernel");
+}
+
 extern "C" int ali_ct_book(const float* v, const float* dist, const int32_t* succ, const int32_t* pred,
                            const int32_t* it, int32_t K, int32_t B, int64_t N, float* best, float* best_dist,
                            int32_t* best_label, int32_t* found, int32_t* round_succ, float* c, float* c_lo, float* c_hi,
@@ -402,6 +551,27 @@ extern "C" int ali_ct_cem_update(const float* gx, int32_t gx_stride, float* v, f
     hipLaunchKernelGGL(ct_cem_update_kernel<1>, dim3((unsigned)B), dim3(kCtBlock), 0, ST(stream), gx, (int)gx_stride, v,
                        y, x0, lo, hi, itp, rp, (int)K, lr, beta, clip, (long long)N, l1, l2, dist, gnorm);
   return check_launch("ct_cem_update_kernel");
+}
+
+extern "C" int ali_ct_pp_update(const float* gx, int32_t gx_stride, float* v, float* y, const float* x0,
+                                float background, int32_t* it, int32_t* rnd, int32_t K, double lr, double beta,
+                                double clip, int32_t B, int64_t N, float* l1, float* l2, float* dist, float* gnorm,
+                                ali_stream_t stream) {
+  const int rc = ct_rows("ali_ct_pp_update", B, N, gx_stride, K);
+  if (rc != ALI_OK) return rc;
+  if (!gx || !v || !y || !x0 || !it || !rnd || !l1 || !l2 || !dist || !gnorm) {
+    set_error("ali_ct_pp_update: no argument may be NULL");
+    return ALI_ERR_BAD_ARG;
+  }
+  int* itp = reinterpret_cast<int*>(it);
+  int* rp = reinterpret_cast<int*>(rnd);
+  if (ct_vec4(N, {v, y, x0}))
+    hipLaunchKernelGGL(ct_pp_update_kernel<4>, dim3((unsigned)B), dim3(kCtBlock), 0, ST(stream), gx, (int)gx_stride, v,
+                       y, x0, background, itp, rp, (int)K, lr, beta, clip, (long long)N, l1, l2, dist, gnorm);
+  else
+    hipLaunchKernelGGL(ct_pp_update_kernel<1>, dim3((unsigned)B), dim3(kCtBlock), 0, ST(stream), gx, (int)gx_stride, v,
+                       y, x0, background, itp, rp, (int)K, lr, beta, clip, (long long)N, l1, l2, dist, gnorm);
+  return check_launch("ct_pp_update_kernel");
 }
 
 extern "C" int ali_ct_ce_update(const float* gx, int32_t gx_stride, float* v, const float* x0, const float* lo,

@@ -27,12 +27,20 @@ negatives; Wachter et al. 2017, as omnixai's "ce") with omnixai's default hyper-
 kappa = 10, binary_search_steps = 5, learning_rate = 1e-2, num_iterations = 1000, grad_clip = 1e3; cf: c0 = 10,
 kappa = 10, gamma = 1, binary_search_steps = 5, learning_rate = 1e-2, num_iterations = 100, grad_clip = 1e3 -- as
 ``ali_hip.contrast`` states it.  Agreement with the omnixai package itself has not been checked (the package is not a
-dependency).  Pertinent positives are not provided.
+dependency).
+
+Pertinent positives (``'pp'``, what ``uncertainty_evolution.py`` reads) come with ``positives=True``: each row also
+gets ``cem_pp_statement``'s search (pn's hyper-parameters) around a "no information" pixel value ``background``, in
+the units the model takes.  That script feeds ``[0, 1]`` images through a ``ScaledClf`` wrapper (``clf(2 x - 1)``),
+which is no ``ClassifierStack`` and runs the statement with ``background=0.0``; on the device the classifier itself
+takes ``2 x - 1`` with ``background=-1.0`` and ``(pp + 1) / 2`` maps the images back -- a search in ``[-1, 1]`` units,
+whose iterates and distances are not the same numbers as the one in ``[0, 1]`` units.
 """
 import numpy as np
 import torch
 
-from ali_hip.contrast import ContrastiveSearch, ce_statement, cem_pn_statement, hyper_parameters
+from ali_hip.contrast import (ContrastiveSearch, as_fp32, ce_statement, cem_pn_statement, cem_pp_statement,
+                              hyper_parameters)
 
 
 class Image:
@@ -78,9 +86,13 @@ class _SearchExplainer:
         if self.on_device and model.training:
             raise ValueError(f"{type(self).__name__}: the model is in training mode; the device search is defined in "
                              f"eval mode only -- call model.eval() before building the explainer")
-        self._executor = None
+        self._executors = {}
         self._shapes = {}
         hyper_parameters(self.MODE, hyper)           # (an unknown name is refused here, on either route)
+
+    def _searches(self):
+        """(mode, image key, found key, keyword arguments) of every search a row gets"""
+        return [(self.MODE, self.KEY, "found", dict(bounds=self.bounds))]
 
     # ---- the model's input shape, learnt from the preprocess function on one probe
     def _input_shape(self, shape):
@@ -102,15 +114,16 @@ class _SearchExplainer:
             self._shapes[shape] = got
         return got
 
-    def _search(self, x):
-        """x [B, *model input shape] on the model's device -> the search's result dict there"""
+    def _search(self, x, mode, kw):
+        """x [B, *model input shape] on the model's device -> the result dict of search ``mode`` there"""
         if self.on_device and x.dim() == 4 and x.shape[1] == 1:
-            if self._executor is None:
-                self._executor = ContrastiveSearch(self.model, self.MODE, capture=self.capture, bounds=self.bounds,
-                                                   **self.hyper)
-            return self._executor.run(x)
-        statement = cem_pn_statement if self.MODE == "pn" else ce_statement
-        return statement(self.model, x, bounds=self.bounds, **self.hyper)
+            ex = self._executors.get(mode)
+            if ex is None:
+                ex = self._executors[mode] = ContrastiveSearch(self.model, mode, capture=self.capture, **kw,
+                                                               **self.hyper)
+            return ex.run(x)
+        statement = {"pn": cem_pn_statement, "ce": ce_statement, "pp": cem_pp_statement}[mode]
+        return statement(self.model, x, **kw, **self.hyper)
 
     def _tensor(self, X):
         data = X.data if isinstance(X, Image) else X
@@ -119,40 +132,65 @@ class _SearchExplainer:
         return data
 
     def _run(self, data):
-        """data [B, ...] tensor in the caller's layout -> (images [B, n] in that layout's order, label, found)"""
+        """data [B, ...] tensor in the caller's layout -> [(key, found key, images [B, n] in that layout's order, label,
+        found)] for every search"""
         B = data.shape[0]
         x = data.to(self.device).float().reshape((B,) + self._input_shape(data.shape[1:]))
-        out = self._search(x)
-        return out["image"].reshape(B, -1), out["label"], out["found"]
+        out = []
+        for mode, key, fkey, kw in self._searches():
+            res = self._search(x, mode, kw)
+            out.append((key, fkey, res["image"].reshape(B, -1), res["label"], res["found"]))
+        return out
 
     def explain(self, X):
         data = self._tensor(X)
-        img, label, found = self._run(data)
-        img = img.reshape(data.shape).cpu().numpy()
-        label, found = label.cpu().numpy(), found.cpu().numpy()
-        return Explanations([{self.KEY: img[i], self.KEY + "_label": int(label[i]), "found": int(found[i])}
-                             for i in range(data.shape[0])])
+        rows = [{} for _ in range(data.shape[0])]
+        for key, fkey, img, label, found in self._run(data):
+            img = img.reshape(data.shape).cpu().numpy()
+            label, found = label.cpu().numpy(), found.cpu().numpy()
+            for i, row in enumerate(rows):
+                row.update({key: img[i], key + "_label": int(label[i]), fkey: int(found[i])})
+        return Explanations(rows)
 
     def explain_all(self, images, batch=64):
         """The scripts' loop over the test rows: ``batch`` rows per search, the results kept on the model's device, one
         host read at the end.  Returns {key: images in the input's layout, key_label: int64 [n], "found": int64 [n]}
-        as numpy arrays, rows in the input's order."""
+        (and, with positives, "pp", "pp_label", "pp_found") as numpy arrays, rows in the input's order."""
         data = self._tensor(images)
         n = data.shape[0]
-        parts = []
+        parts, names = [], []
         for lo in range(0, n, batch):
-            img, label, found = self._run(data[lo:lo + batch])
-            parts.append(torch.cat([img, label.to(img.dtype).unsqueeze(1), found.to(img.dtype).unsqueeze(1)], dim=1))
+            res = self._run(data[lo:lo + batch])
+            names = [(key, fkey) for key, fkey, _, _, _ in res]
+            parts.append(torch.cat([torch.cat([img, label.to(img.dtype).unsqueeze(1), found.to(img.dtype).unsqueeze(1)],
+                                              dim=1) for _, _, img, label, found in res], dim=1))
         every = torch.cat(parts, dim=0).cpu().numpy()                # (labels and flags are small integers: exact)
-        return {self.KEY: every[:, :-2].reshape(tuple(data.shape)), self.KEY + "_label": every[:, -2].astype(np.int64),
-                "found": every[:, -1].astype(np.int64)}
+        width = every.shape[1] // len(names)
+        out = {}
+        for j, (key, fkey) in enumerate(names):
+            blk = every[:, j * width:(j + 1) * width]
+            out.update({key: blk[:, :-2].reshape(tuple(data.shape)), key + "_label": blk[:, -2].astype(np.int64),
+                        fkey: blk[:, -1].astype(np.int64)})
+        return out
 
 
 class ContrastiveExplainer(_SearchExplainer):
-    """``ContrastiveExplainer(model, preprocess_function=None, **hyper)``: ``explain(Image(...))`` returns an object
-    whose ``.explanations[i]`` is {"pn": image in the input's layout, "pn_label": int, "found": 0 / 1}; a row without a
-    pertinent negative gets its own image and label back (``found`` = 0)."""
+    """``ContrastiveExplainer(model, preprocess_function=None, positives=False, background=0.0, **hyper)``:
+    ``explain(Image(...))`` returns an object whose ``.explanations[i]`` is {"pn": image in the input's layout,
+    "pn_label": int, "found": 0 / 1}; a row without a pertinent negative gets its own image and label back (``found`` =
+    0).  With ``positives`` each row also gets the pertinent positive around the "no information" value ``background``
+    (in the model's input units): "pp", "pp_label", "pp_found" (a row without one: its own image, its label, 0).  The
+    hyper-parameters serve both searches; ``bounds`` is the pertinent negative's alone."""
     MODE, KEY = "pn", "pn"
+
+    def __init__(self, model, preprocess_function=None, capture=True, bounds=None, positives=False, background=0.0,
+                 **hyper):
+        super().__init__(model, preprocess_function=preprocess_function, capture=capture, bounds=bounds, **hyper)
+        self.positives, self.background = bool(positives), as_fp32(background)
+
+    def _searches(self):
+        pp = [("pp", "pp", "pp_found", dict(background=self.background))] if self.positives else []
+        return super()._searches() + pp
 
 
 class CounterfactualExplainer(_SearchExplainer):

@@ -600,6 +600,24 @@ int ali_ct_ce_update(const float* gx, int32_t gx_stride, float* v, const float* 
                      float* m, float* v2, int32_t* it, int32_t* rnd, int32_t K, double lr, double gamma, double clip,
                      double beta1, double beta2, double eps, int32_t B, int64_t N, float* l1, float* gnorm,
                      ali_stream_t stream);
+/* The pertinent-positive search ("Pertinent positives"): the background b (an fp32 "no information" pixel
+ * value) replaces x0 as the centre, the box of pixel i is [min(b, x0_i), max(b, x0_i)].  ali_ct_book serves it as is.
+ * ali_ct_pp_attack: ali_ct_attack's arguments with t0 required and the hinge turned round: succ[b] = pred[b] == t0[b];
+ *   A[b] = max(0, other - own + kappa) and seed[b][:] = c[b] * (e_other - e_t0) where other - own + kappa > 0, else 0;
+ *   the columns [C, seed_ld) are 0.
+ * ali_ct_pp_update: one block per row.  k == K: v = y = b, it = 0, rnd += 1, the distances 0.  k < K, with gx the
+ *   classifier's input gradient at y:
+ *     g = gx + 2 (y - b);  norm = |g|_2 -> gnorm;  g *= clip / norm if norm > clip;  u = y - lr sqrt(1 - k / K) g
+ *     w = u - beta if u - b > beta, u + beta if u - b < -beta, else b;  v' = w clamped to the box
+ *     y' = v' + k / (k + 3) (v' - v) clamped to the box;  l1 = |v' - b|_1, l2 = |v' - b|_2^2 of v' as stored,
+ *     dist = l2 + beta l1;  it = k + 1.  Pixels that fall back to b or x0 receive those floats themselves.
+ *   Rows and gx as ali_ct_cem_update. */
+int ali_ct_pp_attack(const float* logit, int32_t R, int32_t C, int32_t B, int32_t eval_off, int32_t grad_off,
+                     const int32_t* t0, const float* c, double kappa, float* seed, int32_t seed_ld, float* A,
+                     int32_t* pred, int32_t* succ, ali_stream_t stream);
+int ali_ct_pp_update(const float* gx, int32_t gx_stride, float* v, float* y, const float* x0, float background,
+                     int32_t* it, int32_t* rnd, int32_t K, double lr, double beta, double clip, int32_t B, int64_t N,
+                     float* l1, float* l2, float* dist, float* gnorm, ali_stream_t stream);
 
 /* torch.optim.Adam step (mnist.py:176-179,230,236,241), no amsgrad / decay.
  * One launch over a flat parameter segment.  The 1-based step count is `step`, or *dev_step when
