@@ -25,6 +25,7 @@ from morphomnist import morpho as stmt
 from . import ops
 
 COLUMNS = ("thickness", "intensity", "slant", "area", "length", "slant_hires")
+BOUND_COLUMNS = ("width", "height", "slant_measure")             # with MorphoMeasure(bound_frac=...)
 WORKSPACE_BUDGET = 384 << 20     # bytes of scratch, distance maps and bitmaps one chunk may hold
 
 
@@ -44,15 +45,17 @@ def unpack_bits(words, Wh):
     return np.unpackbits(w, axis=2, bitorder="little")[:, :, :Wh].astype(bool)
 
 
-def scratch_bytes(H, W, scale):
-    """the largest scratch per image of the three kernels that use one (binarise, edt, thin)"""
-    return max(4 * H * W * scale if scale > 1 else 0, 2 * H * W * scale * scale)
+def scratch_bytes(H, W, scale, bounds=False):
+    """the largest scratch per image of the three kernels that use one (binarise, edt, thin), and of bounds when it
+    runs"""
+    need = max(4 * H * W * scale if scale > 1 else 0, 2 * H * W * scale * scale)
+    return max(need, ops.morpho_bounds_scratch_bytes(H, W, scale)) if bounds else need
 
 
-def per_image_bytes(H, W, scale):
+def per_image_bytes(H, W, scale, bounds=False):
     """what one image of a chunk holds on the device: scratch, the distance map and the two bitmaps"""
     Hh, Wh = H * scale, W * scale
-    return scratch_bytes(H, W, scale) + 4 * Hh * Wh + 2 * 4 * Hh * ((Wh + 31) // 32)
+    return scratch_bytes(H, W, scale, bounds) + 4 * Hh * Wh + 2 * 4 * Hh * ((Wh + 31) // 32)
 
 
 def as_images(images):
@@ -98,12 +101,22 @@ class MorphoMeasure:
 
     CUDA tensors: four launches per chunk of ``chunk`` images, no host read; the default chunk is what fits
     ``WORKSPACE_BUDGET`` (306 images of 28 x 28 at scale 16, 1.25 MB each), so memory is bounded whatever B is.
-    ``table()`` returns every row measured so far as numpy columns with one host read; ``reset()`` forgets them."""
+    ``table()`` returns every row measured so far as numpy columns with one host read; ``reset()`` forgets them.
 
-    def __init__(self, scale=16, threshold=.5, seed=0, chunk=None):
+    ``bound_frac`` (0 < bound_frac < 1, or None): the bounding parallelogram of ``morphomnist.measure.measure_image``
+    too, on hires = expand(image - image.min()) -- one more launch per chunk (csrc/morpho.hip: bounds), still no host
+    read.  It adds "width", "height" ((right - left) / scale, (bottom - top) / scale) and "slant_measure" (atan(-u11 /
+    u02) of hires): float32 [B]; "bounds": float64 [B, 6] = left, right, top, bottom, shear, middle in up-sampled pixels;
+    "corners": float64 [B, 4, 2], (x, y) clockwise from the top left; NaN without mass or with a shear that is not
+    finite.  None: every output, the chunk and the launches are those above."""
+
+    def __init__(self, scale=16, threshold=.5, seed=0, chunk=None, bound_frac=None):
         self.scale, self.threshold, self.seed = int(scale), float(threshold), int(seed)
         if self.scale < 1:
             raise ValueError("MorphoMeasure: scale >= 1")
+        if bound_frac is not None and not 0.0 < float(bound_frac) < 1.0:
+            raise ValueError(f"MorphoMeasure: 0 < bound_frac < 1, or None; got {bound_frac}")
+        self.bound_frac = None if bound_frac is None else float(bound_frac)
         self.chunk = chunk
         self._ops, self._ws, self._blocks = {}, {}, []
         self._keep = stmt.keep_bits()
@@ -111,7 +124,7 @@ class MorphoMeasure:
     def chunk_for(self, H, W):
         if self.chunk is not None:
             return max(int(self.chunk), 1)
-        return max(WORKSPACE_BUDGET // per_image_bytes(H, W, self.scale), 1)
+        return max(WORKSPACE_BUDGET // per_image_bytes(H, W, self.scale, self.bound_frac is not None), 1)
 
     def operators(self, H, W, device):
         """(AH, AW): the expand operators as fp32 device tensors, built once per size in fp64 on the host"""
@@ -122,11 +135,24 @@ class MorphoMeasure:
         return self._ops[key]
 
     def _workspace(self, n, H, W, device):
-        need = ops.WS_RESERVED + n * scratch_bytes(H, W, self.scale)
+        need = ops.WS_RESERVED + n * scratch_bytes(H, W, self.scale, self.bound_frac is not None)
         ws = self._ws.get(str(device))
         if ws is None or ws.numel() < need:
             ws = self._ws[str(device)] = torch.zeros(need, dtype=torch.uint8, device=device)
         return ws
+
+    def _bounds_columns(self, bounds, dtype):
+        """width, height, slant_measure in ``dtype`` and the corners [B, 4, 2] from bounds [B, 6] (float64, any
+        device), each operation on its own as the statement takes them"""
+        left, right, top, bottom, shear, middle = bounds.unbind(1)
+        s = float(self.scale)
+        width, height = ((right - left) / s).to(dtype), ((bottom - top) / s).to(dtype)
+        slant = torch.atan(-shear).to(dtype)
+        at_top, at_bottom = shear * (top - middle), shear * (bottom - middle)
+        corners = torch.stack([torch.stack([left + at_top, top], 1), torch.stack([right + at_top, top], 1),
+                               torch.stack([right + at_bottom, bottom], 1), torch.stack([left + at_bottom, bottom], 1)],
+                              1)
+        return width, height, slant, corners
 
     @torch.no_grad()
     def measure(self, images):
@@ -149,6 +175,7 @@ class MorphoMeasure:
         AH, AW = self.operators(H, W, dev)
         n = min(self.chunk_for(H, W), B)
         ws = self._workspace(n, H, W, dev)
+        bounds = None if self.bound_frac is None else torch.empty(B, 6, dtype=torch.float64, device=dev)
         for lo in range(0, B, n):
             hi = min(lo + n, B)
             bits, fg, hstats = ops.morpho_binarise(x[lo:hi], self.scale, AH, AW, self.threshold, ws=ws)
@@ -157,35 +184,53 @@ class MorphoMeasure:
             ops.morpho_measure(x[lo:hi], self.scale, skel, d2, fg, hstats, st,
                                out=(counts[lo:hi], values[lo:hi], slant[lo:hi]))
             status[lo:hi] = st
-        return self._remember(counts, values, slant, status)
+            if bounds is not None:
+                ops.morpho_bounds(x[lo:hi], self.scale, AH, AW, self.bound_frac, ws=ws, out=bounds[lo:hi])
+        extra = None if bounds is None else (*self._bounds_columns(bounds, torch.float32), bounds)
+        return self._remember(counts, values, slant, status, extra)
 
     def _measure_cpu(self, x):
         dtype = np.float64 if x.dtype == torch.float64 else np.float32
         rows = [statement_row(img.numpy(), self.scale, self.threshold, self.seed, dtype) for img in x]
+        extra = None
+        if self.bound_frac is not None:
+            got = [stmt.measure_bounds(img.numpy(), self.scale, self.bound_frac, dtype) for img in x]
+            col = lambda k: torch.from_numpy(np.array([g[k] for g in got], dtype=dtype))
+            extra = (col("width"), col("height"), col("slant"), torch.from_numpy(np.stack([g["corners"] for g in got])),
+                     torch.from_numpy(np.stack([g["bounds"] for g in got])))
         return (torch.from_numpy(np.stack([r[0] for r in rows]).astype(np.int32)),
                 torch.from_numpy(np.stack([r[1] for r in rows])),
                 torch.from_numpy(np.array([r[2] for r in rows], dtype=dtype)),
-                torch.tensor([r[3] for r in rows], dtype=torch.int32))
+                torch.tensor([r[3] for r in rows], dtype=torch.int32), extra)
 
-    def _remember(self, counts, values, slant, status):
+    def _remember(self, counts, values, slant, status, extra=None):
         out = {"area": values[:, 0], "length": values[:, 1], "thickness": values[:, 2], "intensity": values[:, 3],
                "slant": values[:, 4], "slant_hires": slant, "counts": counts, "status": status}
         # one block of float64 per call: the integers are exact in it, and ``table`` reads every block at once
-        self._blocks.append(torch.cat([values.double(), slant.double().reshape(-1, 1), counts.double(),
-                                       status.double().reshape(-1, 1)], dim=1))
+        block = [values.double(), slant.double().reshape(-1, 1), counts.double(), status.double().reshape(-1, 1)]
+        if extra is not None:
+            width, height, slant_measure, corners, bounds = extra
+            out.update(width=width, height=height, slant_measure=slant_measure, bounds=bounds, corners=corners)
+            block += [torch.stack([width, height, slant_measure], 1).double(), bounds, corners.reshape(-1, 8)]
+        self._blocks.append(torch.cat(block, dim=1))
         return out
 
     def table(self):
         """{column: numpy array} of every row measured so far, in order (one host read): the float columns of
-        ``COLUMNS``, ``counts`` int64 [N, 4] and ``status`` int64 [N]"""
+        ``COLUMNS``, ``counts`` int64 [N, 4] and ``status`` int64 [N]; with ``bound_frac`` also those of
+        ``BOUND_COLUMNS``, ``bounds`` [N, 6] and ``corners`` [N, 4, 2]"""
+        wide = self.bound_frac is not None
         if not self._blocks:
-            host = np.zeros((0, 11))
+            host = np.zeros((0, 28 if wide else 11))
         else:
             host = torch.cat(self._blocks).cpu().numpy()
         out = {"area": host[:, 0], "length": host[:, 1], "thickness": host[:, 2], "intensity": host[:, 3],
                "slant": host[:, 4], "slant_hires": host[:, 5]}
         out["counts"] = host[:, 6:10].astype(np.int64)
         out["status"] = host[:, 10].astype(np.int64)
+        if wide:
+            out.update(width=host[:, 11], height=host[:, 12], slant_measure=host[:, 13], bounds=host[:, 14:20],
+                       corners=host[:, 20:28].reshape(-1, 4, 2))
         return out
 
     def reset(self):

@@ -2134,6 +2134,41 @@ def morpho_measure(x, scale, skel, d2, fg, hstats, status, out=None):
     return counts, values, slant
 
 
+MORPHO_BOUNDS_LDS_T = 28 * 448   # floats of ali_morpho_bounds' T kept in LDS; a larger T goes to the workspace
+
+
+def morpho_bounds_scratch_bytes(H, W, scale):
+    """the workspace ali_morpho_bounds needs per image behind the reserved head: T when it does not fit in LDS"""
+    return 4 * H * W * scale if scale > 1 and H * W * scale > MORPHO_BOUNDS_LDS_T else 0
+
+
+def morpho_bounds(x, scale, AH=None, AW=None, bound_frac=0.02, ws=None, debug=False, out=None):
+    """The bounding parallelogram of x [B, H, W] (include/ali_hip.h: ali_morpho_bounds) on hires = expand(x - min x);
+    AH, AW as ``morpho_binarise`` takes them.  Returns bounds float64 [B, 6] = left, right, top, bottom, shear, middle in
+    up-sampled pixels, and with ``debug`` also (hcdf float64 [B, W * scale], vcdf float64 [B, H * scale]); ``out``: the
+    bounds tensor to write into."""
+    lib = _lib.load()
+    ptr, ld, B, H, W, Hh, Wh = _morpho_images(x, scale)
+    if scale > 1:
+        for a, n in ((AH, H), (AW, W)):
+            if a is None or tuple(a.shape) != (n * scale, n):
+                raise ValueError(f"morpho_bounds: need an expand operator of shape {(n * scale, n)}")
+    bound_frac = float(bound_frac)
+    if not 0.0 < bound_frac < 1.0:
+        raise ValueError(f"morpho_bounds: 0 < bound_frac < 1, got {bound_frac}")
+    dev = x.device
+    bounds = torch.empty(B, 6, dtype=torch.float64, device=dev) if out is None else out
+    hcdf = torch.empty(B, Wh, dtype=torch.float64, device=dev) if debug else None
+    vcdf = torch.empty(B, Hh, dtype=torch.float64, device=dev) if debug else None
+    wp, wn = _morpho_ws(ws, dev)
+    _lib.check(lib.ali_morpho_bounds(ptr, ld, B, H, W, int(scale), None if scale == 1 else _chk(AH, "AH"),
+                                     None if scale == 1 else _chk(AW, "AW"), bound_frac,
+                                     _f64(bounds, (B, 6), "bounds"), None if hcdf is None else _f64(hcdf, (B, Wh), "hcdf"),
+                                     None if vcdf is None else _f64(vcdf, (B, Hh), "vcdf"), wp, wn, _stream()),
+               "ali_morpho_bounds")
+    return (bounds, hcdf, vcdf) if debug else bounds
+
+
 MORPHO_MAX_RADIUS = 64           # the largest radius of ali_morpho_reshape's half-width table
 
 

@@ -1080,6 +1080,209 @@ morpho_local_kernel(const uint32_t* __restrict__ bin, const int* __restrict__ d2
   }
 }
 
+// --------------------------------------------------------------------------------------------------------- bounds
+// The bounding parallelogram of morphomnist/morpho.py (bounds_of) on hires = expand(X - min X), formed as
+// morpho_binarise_kernel forms it and never stored.  Pass 1 reduces the fp64 moments behind the shear u11 / u02 and the
+// centroid row; pass 2 forms every row again (the same instructions: the same bits), takes its fp64 prefix P_y in LDS,
+// and the thread that owns bin t adds P_y[k(y, t)] in ascending y, k(y, t) = #{x : x + .5 < t + shear (y - middle)}
+// counted with the statement's own comparison.  The vertical cdf is the running sum of the rows' totals.  Then the
+// four crossings of quantile_loc.  T = (X - min) AWt stays in LDS up to kBdLdsT floats (28 x 448: 50 KB), else in the
+// workspace.
+constexpr int kBdLdsT = 28 * 448;
+
+// rows i0 .. i0 + kMoRows - 1 of column j of hires.  MODE 0: scale 1 (hires = X - min); 1, 2: 255 * AH T with explicit
+// fmaf in ascending r, as morpho_binarise_kernel's tile
+template <int MODE>
+__device__ __forceinline__ void bounds_tile(const float* X, float xmn, int H, int W, int Hh, int Wh, const float* T,
+                                            const float* __restrict__ AH, int i0, int j, float (&v)[kMoRows]) {
+  if (MODE == 0) {
+#pragma unroll
+    for (int k = 0; k < kMoRows; ++k) v[k] = i0 + k < Hh ? X[(i0 + k) * W + j] - xmn : 0.f;
+    return;
+  }
+  float acc[kMoRows];
+#pragma unroll
+  for (int k = 0; k < kMoRows; ++k) acc[k] = 0.f;
+  for (int r = 0; r < H; ++r) {
+    const float t = T[r * Wh + j];
+#pragma unroll
+    for (int k = 0; k < kMoRows; ++k) {
+      const int i = i0 + k < Hh ? i0 + k : Hh - 1;                   // (uniform in the block)
+      acc[k] = fmaf(AH[i * H + r], t, acc[k]);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < kMoRows; ++k) v[k] = 255.f * acc[k];
+}
+
+// shear = u11 / u02 and middle = m01 from the sums q = (m00, x, y, xy, yy), each operation rounded on its own as
+// ImageMoments forms them
+__device__ void bounds_moments(const double* q, double* shear, double* middle) {
+#pragma clang fp contract(off)
+  const double m00 = q[0];
+  const double m10 = q[1] / m00, m01 = q[2] / m00;
+  const double u11 = q[3] / m00 - m10 * m01;
+  const double u02 = q[4] / m00 - m01 * m01;
+  *shear = u11 / u02;
+  *middle = m01;
+}
+
+// #{x in 0 .. Wh - 1 : x + .5 < t + shear * (y - middle)}, the comparison evaluated as the statement writes it
+__device__ int bounds_count(int t, int y, double shear, double middle, int Wh) {
+#pragma clang fp contract(off)
+  const double dy = (double)y - middle;
+  const double sd = shear * dy;
+  const double c = (double)t + sd;
+  if (!(0.5 < c)) return 0;                                          // (NaN: no x)
+  int k = (int)fmin(fmax(ceil(c - 0.5), 0.0), (double)Wh);          // an estimate, then the comparison itself decides
+  while (k > 0 && !((double)(k - 1) + 0.5 < c)) --k;
+  while (k < Wh && (double)k + 0.5 < c) ++k;
+  return k;
+}
+
+// np.interp's interpolation on interval j of the cdf c
+__device__ double bounds_interp(const double* c, int j, double f) {
+#pragma clang fp contract(off)
+  if (f == c[j]) return (double)j;
+  const double slope = ((double)(j + 1) - (double)j) / (c[j + 1] - c[j]);
+  const double d = f - c[j];
+  const double p = slope * d;
+  return p + (double)j;
+}
+
+__device__ __forceinline__ int block_imax(int v, int* s) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v = max(v, __shfl_xor(v, m, 64));
+  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
+  __syncthreads();
+  int t = s[0];
+#pragma unroll
+  for (int w = 1; w < kMoWaves; ++w) t = max(t, s[w]);
+  __syncthreads();
+  return t;
+}
+
+// quantile_loc(c[0 .. n - 1], f, left / right) by the whole block
+__device__ double bounds_locate(const double* c, int n, double f, bool right, int* s_i) {
+  constexpr int kNone = -(1 << 30);
+  int best = kNone;                                                  // right: the last j; left: -(the first j)
+  for (int j = threadIdx.x; j + 1 < n; j += kMoBlock)
+    if (c[j] <= f && f < c[j + 1]) best = max(best, right ? j : -j);
+  best = block_imax(best, s_i);
+  if (!(f >= c[0])) return 0.0;
+  if (f >= c[n - 1]) return (double)(n - 1);
+  if (best == kNone) return __longlong_as_double(0x7ff8000000000000LL);   // (a finite cdf always crosses here)
+  return bounds_interp(c, right ? best : -best, f);
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(kMoBlock)
+morpho_bounds_kernel(const float* __restrict__ x, long long ld, int H, int W, int s, const float* __restrict__ AH,
+                     const float* __restrict__ AW, double frac, float* __restrict__ Tws, double* __restrict__ bounds,
+                     double* __restrict__ hcdf, double* __restrict__ vcdf) {
+  __shared__ double s_big[kBdLdsT / 2];                              // T (MODE 1); after pass 2: hcdf
+  __shared__ double s_P[kMoMaxSide + 1];                             // the prefix of the current row
+  __shared__ double s_seg[2 * kMoWaves];                             // its 64-column segment totals
+  __shared__ double s_vc[kMoMaxSide];                                // the mass above each row, then vcdf
+  __shared__ float s_f[kMoWaves];
+  __shared__ double s_d[kMoWaves];
+  __shared__ int s_i[kMoWaves];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int Hh = H * s, Wh = W * s;
+  const float* X = x + (long long)b * ld;
+  float* T = MODE == 0 ? nullptr : MODE == 1 ? reinterpret_cast<float*>(s_big) : Tws + (long long)b * H * Wh;
+  float xmn = INFINITY;
+  for (int e = tid; e < H * W; e += kMoBlock) xmn = fminf(xmn, X[e]);
+  xmn = -block_max<kMoWaves>(-xmn, s_f);
+  if (MODE != 0) {
+    for (int e = tid; e < H * Wh; e += kMoBlock) {
+      const int r = e / Wh, j = e % Wh;
+      float acc = 0.f;
+      for (int c = 0; c < W; ++c) acc = fmaf(X[r * W + c] - xmn, AW[j * W + c], acc);
+      T[e] = acc;
+    }
+    __syncthreads();                                                 // (the block reads what the block wrote)
+  }
+  // pass 1: m00, sum x h, sum y h, sum x y h, sum y^2 h
+  double m[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int i0 = 0; i0 < Hh; i0 += kMoRows)
+    for (int j = tid; j < Wh; j += kMoBlock) {
+      float v[kMoRows];
+      bounds_tile<MODE>(X, xmn, H, W, Hh, Wh, T, AH, i0, j, v);
+#pragma unroll
+      for (int k = 0; k < kMoRows; ++k) {
+        if (i0 + k >= Hh) break;
+        const double d = (double)v[k], xx = (double)j, yy = (double)(i0 + k);
+        m[0] += d; m[1] += xx * d; m[2] += yy * d; m[3] += xx * yy * d; m[4] += yy * yy * d;
+      }
+    }
+#pragma unroll
+  for (int q = 0; q < 5; ++q) m[q] = block_sum<kMoWaves>(m[q], s_d);
+  double shear, middle;
+  bounds_moments(m, &shear, &middle);
+  // pass 2: the rows again, their prefixes, the bins
+  const int j0 = tid, j1 = tid + kMoBlock;
+  double hacc[2] = {0.0, 0.0}, above = 0.0;                          // (above: thread 0's running row total)
+  if (tid == 0) s_P[0] = 0.0;
+  for (int i0 = 0; i0 < Hh; i0 += kMoRows) {
+    float v0[kMoRows], v1[kMoRows];
+    if (j0 < Wh) bounds_tile<MODE>(X, xmn, H, W, Hh, Wh, T, AH, i0, j0, v0);
+    if (j1 < Wh) bounds_tile<MODE>(X, xmn, H, W, Hh, Wh, T, AH, i0, j1, v1);
+#pragma unroll
+    for (int k = 0; k < kMoRows; ++k) {
+      const int y = i0 + k;
+      if (y >= Hh) break;                                            // (uniform)
+      double a = j0 < Wh ? (double)v0[k] : 0.0, c = j1 < Wh ? (double)v1[k] : 0.0;
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) {                             // inclusive scans along the wave, in a fixed order
+        const double pa = __shfl_up(a, d, 64), pc = __shfl_up(c, d, 64);
+        if (lane >= d) { a = pa + a; c = pc + c; }
+      }
+      if (lane == 63) { s_seg[wave] = a; s_seg[kMoWaves + wave] = c; }
+      __syncthreads();
+      double run = 0.0, off0 = 0.0, off1 = 0.0;                      // the segments in column order
+#pragma unroll
+      for (int q = 0; q < 2 * kMoWaves; ++q) {
+        if (q == wave) off0 = run;
+        if (q == kMoWaves + wave) off1 = run;
+        run = run + s_seg[q];
+      }
+      if (j0 < Wh) s_P[j0 + 1] = off0 + a;
+      if (j1 < Wh) s_P[j1 + 1] = off1 + c;
+      if (tid == 0) {
+        s_vc[y] = above;
+        above = above + run;
+      }
+      __syncthreads();
+      if (j0 < Wh) hacc[0] += s_P[bounds_count(j0, y, shear, middle, Wh)];
+      if (j1 < Wh) hacc[1] += s_P[bounds_count(j1, y, shear, middle, Wh)];
+    }
+  }
+  // (every read of T and s_P lies before the last barrier above)
+  double* s_hc = s_big;
+  if (j0 < Wh) s_hc[j0] = hacc[0] / m[0];
+  if (j1 < Wh) s_hc[j1] = hacc[1] / m[0];
+  __syncthreads();                                                   // (s_vc is thread 0's until here)
+  for (int t = tid; t < Hh; t += kMoBlock) s_vc[t] = s_vc[t] / m[0];
+  __syncthreads();
+  if (hcdf)
+    for (int t = tid; t < Wh; t += kMoBlock) hcdf[(long long)b * Wh + t] = s_hc[t];
+  if (vcdf)
+    for (int t = tid; t < Hh; t += kMoBlock) vcdf[(long long)b * Hh + t] = s_vc[t];
+  const double half = frac / 2.0, upper = 1.0 - half;
+  const double left = bounds_locate(s_hc, Wh, half, false, s_i);
+  const double right = bounds_locate(s_hc, Wh, upper, true, s_i);
+  const double top = bounds_locate(s_vc, Hh, half, false, s_i);
+  const double bottom = bounds_locate(s_vc, Hh, upper, true, s_i);
+  if (tid == 0) {
+    const bool ok = m[0] > 0.0 && isfinite(shear);
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    double* o = bounds + (long long)b * 6;
+    o[0] = ok ? left : nan; o[1] = ok ? right : nan; o[2] = ok ? top : nan; o[3] = ok ? bottom : nan;
+    o[4] = shear; o[5] = middle;
+  }
+}
+
 // the side limits every entry point shares
 static int morpho_check_dims(const char* who, int32_t B, int32_t Hh, int32_t Wh) {
   if (B < 1 || Hh < 1 || Wh < 1 || Hh > kMoMaxSide || Wh > kMoMaxSide) {
@@ -1350,4 +1553,35 @@ extern "C" int ali_morpho_local(const uint32_t* bin, const int32_t* d2, const in
                      (Wh + 31) / 32, (int)scale, out, reinterpret_cast<int*>(radius), reinterpret_cast<long long*>(sums),
                      reinterpret_cast<int*>(status_out));
   return check_launch("morpho_local_kernel");
+}
+
+extern "C" int ali_morpho_bounds(const float* x, int64_t ld, int32_t B, int32_t H, int32_t W, int32_t scale,
+                                 const float* AH, const float* AW, double bound_frac, double* bounds, double* hcdf,
+                                 double* vcdf, void* ws, size_t ws_bytes, ali_stream_t stream) {
+  if (!x || !bounds || (scale > 1 && (!AH || !AW))) {
+    set_error("ali_morpho_bounds: NULL argument");
+    return ALI_ERR_BAD_ARG;
+  }
+  if (H < 1 || W < 1 || scale < 1 || ld < (int64_t)H * W || !(bound_frac > 0.0 && bound_frac < 1.0)) {
+    set_error("ali_morpho_bounds: H = %d, W = %d or scale = %d < 1, ld = %lld < H * W, or bound_frac = %g outside "
+              "(0, 1)", (int)H, (int)W, (int)scale, (long long)ld, bound_frac);
+    return ALI_ERR_BAD_ARG;
+  }
+  int rc = morpho_check_dims("ali_morpho_bounds", B, hires_side(H, scale), hires_side(W, scale));
+  if (rc != ALI_OK) return rc;
+  const int Wh = W * scale;
+  const int mode = scale == 1 ? 0 : (H * Wh <= kBdLdsT ? 1 : 2);
+  void* T = nullptr;
+  rc = morpho_scratch("ali_morpho_bounds", ws, ws_bytes, mode == 2 ? sizeof(float) * (size_t)B * H * Wh : 0, &T);
+  if (rc != ALI_OK) return rc;
+  if (mode == 0)
+    hipLaunchKernelGGL(morpho_bounds_kernel<0>, dim3((unsigned)B), dim3(kMoBlock), 0, ST(stream), x, (long long)ld,
+                       (int)H, (int)W, 1, AH, AW, bound_frac, static_cast<float*>(T), bounds, hcdf, vcdf);
+  else if (mode == 1)
+    hipLaunchKernelGGL(morpho_bounds_kernel<1>, dim3((unsigned)B), dim3(kMoBlock), 0, ST(stream), x, (long long)ld,
+                       (int)H, (int)W, (int)scale, AH, AW, bound_frac, static_cast<float*>(T), bounds, hcdf, vcdf);
+  else
+    hipLaunchKernelGGL(morpho_bounds_kernel<2>, dim3((unsigned)B), dim3(kMoBlock), 0, ST(stream), x, (long long)ld,
+                       (int)H, (int)W, (int)scale, AH, AW, bound_frac, static_cast<float*>(T), bounds, hcdf, vcdf);
+  return check_launch("morpho_bounds_kernel");
 }

@@ -296,6 +296,103 @@ class ImageMoments:
             return self.u11 / self.u20
 
 
+def quantile_loc(c, f, side):
+    """Where the cdf ``c`` [n] crosses the level ``f``, interpolated as ``np.interp(f, c, arange(n))`` interpolates.
+    ``c`` need not be monotone (the up-sampled image rings below zero), so the crossing is a definition:
+    0 if f < c[0]; n - 1 if f >= c[-1]; otherwise the first j with c[j] <= f < c[j + 1] for ``side`` "left" (left, top)
+    or the last such j for "right" (right, bottom), and np.interp's own formula on it -- the same bits as np.interp
+    wherever the crossing is unique."""
+    c = np.asarray(c, dtype=np.float64)
+    n = len(c)
+    f = np.float64(f)
+    if not f >= c[0]:
+        return np.float64(0)
+    if f >= c[-1]:
+        return np.float64(n - 1)
+    hits = np.nonzero((c[:-1] <= f) & (f < c[1:]))[0]
+    j = int(hits[0] if side == "left" else hits[-1])
+    if f == c[j]:
+        return np.float64(j)
+    slope = (np.float64(j + 1) - np.float64(j)) / (c[j + 1] - c[j])
+    return slope * (f - c[j]) + np.float64(j)
+
+
+def horizontal_cdf(img, shear, middle):
+    """hcdf [W]: the mass left of each sheared line t, sum((x + .5 < t + shear * (y - middle)) * img) / img.sum(), as
+    the reference's ``_horz_cdf`` writes it"""
+    img = np.asarray(img, dtype=float)
+    height, width = img.shape
+    x = np.arange(width)[None, :]
+    y = np.arange(height)[:, None]
+    counts = np.zeros(width)
+    for t in range(width):
+        counts[t] = ((x + .5 < t + shear * (y - middle)) * img).sum()
+    return counts / img.sum()
+
+
+def vertical_cdf(img):
+    """vcdf [H]: the mass above each row t, sum((y < t) * img) / img.sum(), as the reference's ``_vert_cdf``"""
+    img = np.asarray(img, dtype=float)
+    y = np.arange(img.shape[0])[:, None]
+    counts = np.zeros(img.shape[0])
+    for t in range(img.shape[0]):
+        counts[t] = ((y < t) * img).sum()
+    return counts / img.sum()
+
+
+def bounds_of(img, frac, moments=None):
+    """(left, right, top, bottom, shear, middle, hcdf, vcdf) of ``bounding_parallelogram`` (float64; the four locations
+    NaN when the mass is not positive or the shear not finite)"""
+    img = np.asarray(img, dtype=float)
+    if moments is None:
+        moments = ImageMoments(img)
+    middle = np.float64(moments.centroid[1])
+    shear = np.float64(moments.horizontal_shear)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        hcdf = horizontal_cdf(img, shear, middle)
+        vcdf = vertical_cdf(img)
+    if not (img.sum() > 0 and np.isfinite(shear)):
+        nan = np.float64(np.nan)
+        return nan, nan, nan, nan, shear, middle, hcdf, vcdf
+    half = frac / 2                                                  # two-sided
+    left, right = quantile_loc(hcdf, half, "left"), quantile_loc(hcdf, 1. - half, "right")
+    top, bottom = quantile_loc(vcdf, half, "left"), quantile_loc(vcdf, 1. - half, "right")
+    return left, right, top, bottom, shear, middle, hcdf, vcdf
+
+
+def corners_of(left, right, top, bottom, shear, middle):
+    """the parallelogram's corners as (x, y) arrays, clockwise from the top left (the reference's)"""
+    top_left = np.array([left + shear * (top - middle), top])
+    top_right = np.array([right + shear * (top - middle), top])
+    bottom_left = np.array([left + shear * (bottom - middle), bottom])
+    bottom_right = np.array([right + shear * (bottom - middle), bottom])
+    return top_left, top_right, bottom_right, bottom_left
+
+
+def bounding_parallelogram(img, frac, moments=None):
+    """The corners (top left, top right, bottom right, bottom left; (x, y) arrays) of the parallelogram that leaves
+    ``frac`` / 2 of the mass of ``img`` outside each side, its slanted sides along the image's horizontal shear through
+    the centroid row.  ``moments``: any object with ``centroid`` and ``horizontal_shear``.  The crossings follow
+    ``quantile_loc``; the corners are NaN when the mass is not positive or the shear not finite."""
+    return corners_of(*bounds_of(img, frac, moments)[:6])
+
+
+def measure_bounds(image, scale, bound_frac, dtype=np.float64):
+    """The bounding-parallelogram half of ``measure_image``: hires = expand(image - image.min(), scale)
+    with the product in ``dtype`` (float64: the statement; float32: the yardstick of the device), then the reference's
+    fp64 moments and ``bounding_parallelogram``.  Returns {"bounds": float64 [6] = left, right, top, bottom, shear,
+    middle; "corners": float64 [4, 2]; "width", "height": (right - left) / scale, (bottom - top) / scale; "slant":
+    arctan(-shear); "hires"}."""
+    image = np.asarray(image, dtype=dtype)
+    hires = expand(image - image.min(), scale, dtype)
+    moments = ImageMoments(hires)
+    b = bounds_of(hires, bound_frac, moments)[:6]
+    with np.errstate(invalid="ignore"):
+        return {"bounds": np.array(b, dtype=np.float64), "corners": np.stack(corners_of(*b)),
+                "width": (b[1] - b[0]) / scale, "height": (b[3] - b[2]) / scale, "slant": np.arctan(-b[4]),
+                "hires": hires}
+
+
 def intensity(image):
     """the median of the pixels in the upper half of the image's range (np.median: the mean of the two middle values
     for an even count), in the image's units"""

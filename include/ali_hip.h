@@ -938,6 +938,20 @@ int ali_morpho_local(const uint32_t* bin, const int32_t* d2, const int32_t* d2c,
                      int32_t Hh, int32_t Wh, int32_t scale, uint32_t* out, int32_t* radius, int64_t* sums,
                      int32_t* status_out, ali_stream_t stream);
 
+/* The bounding parallelogram of Morpho-MNIST's measure_image (morphomnist/morpho.py: bounds_of, quantile_loc): x, ld, B,
+ * H, W, scale, AH, AW as ali_morpho_binarise takes them; hires = expand(x - min x), formed as ali_morpho_binarise forms it
+ * (fp32 fmaf, never stored).  bounds [B][6] fp64 = left, right, top, bottom, shear, middle in up-sampled pixels: shear =
+ * u11 / u02 and middle = m01 of hires in fp64 (every operation rounded on its own); hcdf[t] = sum over rows y of the fp64
+ * prefix of row y up to #{x : x + .5 < t + shear * (y - middle)}, over m00; vcdf[t] = the rows above t over m00; left /
+ * top = the first crossing of bound_frac / 2, right / bottom = the last crossing of 1 - bound_frac / 2, interpolated with
+ * np.interp's formula (0 below the first entry, n - 1 at or above the last).  The four locations are NaN when m00 <= 0
+ * or the shear is not finite.  hcdf [B][W * scale] and vcdf [B][H * scale] fp64 are written when non-NULL.  0 <
+ * bound_frac < 1.  ws >= ALI_WS_RESERVED + 4 * B * H * W * scale bytes when scale > 1 and H * W * scale > 28 * 448 (T
+ * is kept in LDS up to that size), else none.  LDS: 58.5 KB.  One workgroup per image, no atomics, fixed-order sums. */
+int ali_morpho_bounds(const float* x, int64_t ld, int32_t B, int32_t H, int32_t W, int32_t scale, const float* AH,
+                      const float* AW, double bound_frac, double* bounds, double* hcdf, double* vcdf, void* ws,
+                      size_t ws_bytes, ali_stream_t stream);
+
 /* Attribute plumbing of one batch (mnist.py:47-55, audio_mnist.py:203-210, whalecalls.py:455): idx[b*n_cat + j] =
  * argmax of categorical attribute j (one-hot rows of n_classes[j] floats, or int32 when cat_is_int[j]; first maximum
  * like torch.argmax); cont[b*n_cont + j] = cont_in[j][b]. */
