@@ -72,6 +72,21 @@ def as_images(images):
                      f"{tuple(images.shape)}")
 
 
+def checked_images(images, who, scale):
+    """``as_images`` of float images within the up-sampling limit -> (x [B, H, W], B, H, W); on a GPU x is fp32 with
+    contiguous images, what the launches take"""
+    x = as_images(images)
+    if not x.is_floating_point():
+        raise ValueError(f"{who}: float images only")
+    B, H, W = x.shape
+    if H * scale > ops.MORPHO_MAX_SIDE or W * scale > ops.MORPHO_MAX_SIDE:
+        raise ValueError(f"{who}: {H} x {W} images at scale {scale} exceed the limit of "
+                         f"{ops.MORPHO_MAX_SIDE} x {ops.MORPHO_MAX_SIDE} up-sampled pixels")
+    if x.is_cuda and (x.dtype != torch.float32 or not x[0].is_contiguous()):
+        x = x.float().contiguous()
+    return x, B, H, W
+
+
 def statement_row(image, scale=16, threshold=.5, seed=0, dtype=np.float64, binary=None):
     """One image through the statement: (counts [4] int64, values [5], slant_hires, status), the floats in ``dtype``.
     ``binary``: continue from this binary image instead of the statement's own."""
@@ -156,17 +171,9 @@ class MorphoMeasure:
 
     @torch.no_grad()
     def measure(self, images):
-        x = as_images(images)
-        if not x.is_floating_point():
-            raise ValueError("MorphoMeasure: float images only")
-        B, H, W = x.shape
-        if H * self.scale > ops.MORPHO_MAX_SIDE or W * self.scale > ops.MORPHO_MAX_SIDE:
-            raise ValueError(f"MorphoMeasure: {H} x {W} images at scale {self.scale} exceed the limit of "
-                             f"{ops.MORPHO_MAX_SIDE} x {ops.MORPHO_MAX_SIDE} up-sampled pixels")
+        x, B, H, W = checked_images(images, "MorphoMeasure", self.scale)
         if not x.is_cuda:
             return self._remember(*self._measure_cpu(x))
-        if x.dtype != torch.float32 or not x[0].is_contiguous():
-            x = x.float().contiguous()
         dev = x.device
         counts = torch.empty(B, 4, dtype=torch.int32, device=dev)
         values = torch.empty(B, 5, dtype=torch.float32, device=dev)
@@ -314,18 +321,10 @@ class MorphoPerturb:
 
     @torch.no_grad()
     def apply(self, images, thickness=None, slant=None, intensity=None):
-        x = as_images(images)
-        if not x.is_floating_point():
-            raise ValueError("MorphoPerturb: float images only")
-        B, H, W = x.shape
         s = self.scale
-        if H * s > ops.MORPHO_MAX_SIDE or W * s > ops.MORPHO_MAX_SIDE:
-            raise ValueError(f"MorphoPerturb: {H} x {W} images at scale {s} exceed the limit of "
-                             f"{ops.MORPHO_MAX_SIDE} x {ops.MORPHO_MAX_SIDE} up-sampled pixels")
+        x, B, H, W = checked_images(images, "MorphoPerturb", s)
         if not x.is_cuda:
             return self._apply_cpu(x, thickness, slant, intensity)
-        if x.dtype != torch.float32 or not x[0].is_contiguous():
-            x = x.float().contiguous()
         dev = x.device
         t_t = self._target(thickness, B, dev, torch.float32, "thickness")
         t_i = self._target(intensity, B, dev, torch.float32, "intensity")
@@ -447,14 +446,8 @@ class MorphoLocal:
 
     @torch.no_grad()
     def apply(self, images, kind):
-        x = as_images(images)
-        if not x.is_floating_point():
-            raise ValueError("MorphoLocal: float images only")
-        B, H, W = x.shape
         s = self.scale
-        if H * s > ops.MORPHO_MAX_SIDE or W * s > ops.MORPHO_MAX_SIDE:
-            raise ValueError(f"MorphoLocal: {H} x {W} images at scale {s} exceed the limit of "
-                             f"{ops.MORPHO_MAX_SIDE} x {ops.MORPHO_MAX_SIDE} up-sampled pixels")
+        x, B, H, W = checked_images(images, "MorphoLocal", s)
         if isinstance(kind, str):
             if kind not in KINDS:
                 raise ValueError(f"MorphoLocal: kind is one of {KINDS} or an int32 [B] tensor, got {kind!r}")
@@ -466,8 +459,6 @@ class MorphoLocal:
             kinds = kind.contiguous()
         if not x.is_cuda:
             return self._apply_cpu(x, kinds)
-        if x.dtype != torch.float32 or not x[0].is_contiguous():
-            x = x.float().contiguous()
         dev = x.device
         Hh, Wh = H * s, W * s
         i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
