@@ -199,6 +199,12 @@ SIGNATURES = {
                                    c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ali_morpho_bounds": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_double,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "ali_morpho_width": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_size_t, c_void_p]),
+    "ali_morpho_affine_reduce": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_size_t, c_void_p]),
     "ali_attr_pack": (c_int32, [POINTER(c_void_p), POINTER(c_int32), POINTER(c_int32), c_int32, POINTER(c_void_p), c_int32,
                                 c_int32, c_void_p, c_void_p, c_void_p]),
     "ali_g_input": (c_int32, [c_void_p, c_int32, POINTER(c_void_p), POINTER(c_int32), POINTER(c_int32), POINTER(c_void_p),

@@ -8,14 +8,16 @@
   MorphoPerturb   ``apply(images, thickness, slant, intensity)`` returns the ground-truth counterfactual images of
                   ``mnist_vae_measured_cf.py`` and the data-set builders -- ``SetThickness``, ``SetSlant``, ``downscale``,
                   the intensity rescale -- as device tensors with no host read: the four launches above and three more
-                  per chunk (reshape, shear_reduce, set_intensity).
+                  per chunk (reshape, shear_reduce, set_intensity).  ``set_width(images, width, intensity)`` is
+                  ``SetWidth`` and ``downscale``: binarise, width, affine_reduce per chunk, and the reference's
+                  validation as one re-application selected per row on the device.
   MorphoLocal     ``apply(images, kind)`` returns the images of the five Morpho-MNIST data sets -- plain, ``Thinning``,
                   ``Thickening``, ``Swelling``, ``Fracture`` and ``downscale`` -- as device tensors with no host read: the four
                   launches above, then locate, local and shear_reduce (and one more distance map for "thick").
 
 CPU tensors run the statement ``morphomnist.morpho`` row by row in the dtype of the tensor (float64: the tests'
 reference; float32: their yardstick), and ``morphomnist.perturb`` likewise.  What is measured and perturbed is that
-statement, not scikit-image's pipeline (DESIGN 3.16, 3.17, 3.20).
+statement, not scikit-image's pipeline (DESIGN 3.16, 3.17, 3.20, 3.22).
 """
 import numpy as np
 import torch
@@ -259,6 +261,19 @@ def perturb_image_bytes(H, W, scale):
             + 2 * 4 * H * W + 6 * 8)
 
 
+def width_scratch_bytes(H, W, scale):
+    """the largest scratch per image of the ``set_width`` chain: binarise's T (fp32 [H, W * scale]), width's T when it
+    does not fit in LDS, affine_reduce's T (float64 [H * scale, W]), and bounds' for ``validate``"""
+    return max(4 * H * W * scale, 8 * H * W * scale, ops.morpho_bounds_scratch_bytes(H, W, scale)) if scale > 1 else 0
+
+
+def width_image_bytes(H, W, scale):
+    """what one image of a ``MorphoPerturb.set_width`` chunk holds on the device: the scratch, the bitmap, two rounds
+    of the quantised image with the selected and the rescaled one, and the sums, values and statuses"""
+    Hh, Wh = H * scale, W * scale
+    return width_scratch_bytes(H, W, scale) + 2 * 4 * Hh * ((Wh + 31) // 32) + 4 * 4 * H * W + 4 * (6 * 8 + 6 * 8 + 16)
+
+
 class MorphoPerturb:
     """The ground-truth counterfactual image of ``mnist_vae_measured_cf.py`` / ``mnist_vae_counterfactuals.py`` and the
     data-set builders for a batch: ``SetThickness``, ``SetSlant``, ``downscale`` and the intensity rescale of
@@ -274,7 +289,10 @@ class MorphoPerturb:
     CUDA tensors: per chunk the four launches of ``MorphoMeasure`` and three more (csrc/morpho.hip: reshape,
     shear_reduce, set_intensity) on the current stream, no host read; the chunk is what fits ``WORKSPACE_BUDGET`` by
     ``perturb_image_bytes``.  The footprints up to ``max_radius`` are built on the host once (seconds at 64).  CPU
-    tensors run the statement row by row in the tensor's dtype."""
+    tensors run the statement row by row in the tensor's dtype.
+
+    ``set_width(images, width, intensity=None, bound_frac=.02, validate=False)`` is ``SetWidth`` with ``downscale``, a
+    chain of its own (binarise, width, affine_reduce): see its docstring."""
 
     def __init__(self, scale=16, threshold=.5, seed=0, chunk=None, max_radius=64):
         self.measure = MorphoMeasure(scale, threshold, seed, chunk)
@@ -371,6 +389,113 @@ class MorphoPerturb:
                 "status": col("status", np.int32), "radius": col("radius", np.int32),
                 "thickness_before": col("thickness", dtype), "shear_before": col("shear", np.float64),
                 "intensity_before": col("median", dtype)}
+
+    # ------------------------------------------------------------------------------------------------- SetWidth
+    def width_chunk_for(self, H, W):
+        if self.chunk is not None:
+            return max(int(self.chunk), 1)
+        return max(WORKSPACE_BUDGET // width_image_bytes(H, W, self.scale), 1)
+
+    def _width_workspace(self, n, H, W, device):
+        need = ops.WS_RESERVED + n * width_scratch_bytes(H, W, self.scale)
+        ws = self._ws.get(str(device))
+        if ws is None or ws.numel() < need:
+            ws = self._ws[str(device)] = torch.zeros(need, dtype=torch.uint8, device=device)
+        return ws
+
+    def _width_round(self, x, H, W, target, frac, operators, ws):
+        """binarise, width, affine_reduce of one chunk: (q, status, wb)"""
+        AH, AW, RH, RW = operators
+        s = self.scale
+        bits, fg, _ = ops.morpho_binarise(x, s, AH, AW, self.threshold, ws=ws)
+        sums, wb, st = ops.morpho_width(x, s, bits, fg, target, AH, AW, frac, ws=ws)
+        q, st = ops.morpho_affine_reduce(bits, H, W, s, sums, wb, st, RH, RW, ws=ws)
+        return q, st, wb
+
+    @torch.no_grad()
+    def set_width(self, images, width, intensity=None, bound_frac=.02, validate=False):
+        """``SetWidth(width)`` and ``downscale`` of ``morphomnist.perturb.width_image`` for a batch, then the scripts'
+        intensity rescale when ``intensity`` is given.  ``images`` as ``apply`` takes them; ``width``, ``intensity``: [B]
+        tensors on the images' device (``intensity`` may be None), the target width in pixels of the image (the
+        ``width`` column ``MorphoMeasure(bound_frac=...)`` measures).
+
+        Returns {"images": float [B, H, W] in 0 .. 255, "status": int32 [B] (0; 1: no background; 4: nothing left to
+        work with -- an empty bitmap, every pixel in one row, no grey mass, a width that is not finite or <= 0, or a
+        result that is 0 everywhere; 5: the target is NaN, infinite or <= 0 -- the image is 0 then), "width_before":
+        float32 [B], the measured width (right - left) / scale, "factor": float64 [B] = width_before / width,
+        "bounds_before": float64 [B, 2] = left, right in up-sampled pixels, "shear_before": float64 [B], u11 / u02 of
+        the bitmap, "intensity_before": the median of the quantised result (NaN when ``intensity`` is None on a GPU:
+        the launch that selects it runs only with a target)}; NaN where the status is not 0.
+
+        ``validate``: the reference's check, once: "width_after" (float32 [B], the width of the first round's result,
+        before any intensity rescale, under its own grey moments -- one ``morpho_bounds`` launch) and "off_target" (bool
+        [B], |width_after - width| > 1, compared in fp64) are added,
+        a second round is computed from the result for the whole chunk and taken, row by row, where the first is off
+        target.  Exactly one re-application is made (the reference's ``SetWidth`` recurses until the width fits); the
+        outputs named "..._before" stay those of the first round.
+
+        CUDA tensors: per chunk binarise, width, affine_reduce (csrc/morpho.hip) and, only with ``intensity``,
+        set_intensity, on the current stream, no host read (``validate``: bounds and the three again); the chunk is
+        what fits ``WORKSPACE_BUDGET`` by ``width_image_bytes``.  CPU tensors run the statement row by row in the
+        tensor's dtype."""
+        s = self.scale
+        x, B, H, W = checked_images(images, "MorphoPerturb", s)
+        frac = float(bound_frac)
+        if not 0.0 < frac < 1.0:
+            raise ValueError(f"MorphoPerturb: 0 < bound_frac < 1, got {bound_frac}")
+        if width is None:
+            raise ValueError(f"MorphoPerturb: width is a [{B}] tensor on {x.device}")
+        t_w = self._target(width, B, x.device, torch.float64, "width")
+        t_i = self._target(intensity, B, x.device, torch.float32, "intensity")
+        if not x.is_cuda:
+            return self._set_width_cpu(x, t_w, t_i, frac, validate)
+        dev = x.device
+        f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        f64 = lambda *shape: torch.empty(*shape, dtype=torch.float64, device=dev)
+        out = {"images": f32(B, H, W), "status": torch.empty(B, dtype=torch.int32, device=dev), "width_before": f32(B),
+               "factor": f64(B), "bounds_before": f64(B, 2), "shear_before": f64(B),
+               "intensity_before": torch.full((B,), float("nan"), dtype=torch.float32, device=dev)}
+        if validate:
+            out["width_after"], out["off_target"] = f32(B), torch.empty(B, dtype=torch.bool, device=dev)
+        operators = (*self.measure.operators(H, W, dev), *self.reduce_operators(H, W, dev))
+        n = min(self.width_chunk_for(H, W), B)
+        ws = self._width_workspace(n, H, W, dev)
+        for lo in range(0, B, n):
+            hi = min(lo + n, B)
+            q, st, wb = self._width_round(x[lo:hi], H, W, t_w[lo:hi], frac, operators, ws)
+            if validate:
+                bounds = ops.morpho_bounds(q, s, operators[0], operators[1], frac, ws=ws)
+                after = (bounds[:, 1] - bounds[:, 0]) / float(s)
+                off = (after - t_w[lo:hi]).abs() > 1.0                # (fp64; a NaN width: not off target)
+                q2, st2, _ = self._width_round(q, H, W, t_w[lo:hi], frac, operators, ws)
+                q, st = torch.where(off[:, None, None], q2, q), torch.where(off, st2, st)
+                out["width_after"][lo:hi], out["off_target"][lo:hi] = after, off
+            if t_i is not None:
+                _, median, st = ops.morpho_set_intensity(q, t_i[lo:hi], st, out=out["images"][lo:hi])
+                out["intensity_before"][lo:hi] = median
+            else:
+                out["images"][lo:hi] = q
+            out["status"][lo:hi] = st
+            out["width_before"][lo:hi] = ((wb[:, 1] - wb[:, 0]) / float(s)).float()
+            out["factor"][lo:hi], out["bounds_before"][lo:hi], out["shear_before"][lo:hi] = wb[:, 5], wb[:, :2], wb[:, 2]
+        return out
+
+    def _set_width_cpu(self, x, width, intensity, frac, validate):
+        from morphomnist import perturb
+        dtype = np.float64 if x.dtype == torch.float64 else np.float32
+        pick = lambda t, b: None if t is None else t[b].item()
+        rows = [perturb.width_image(x[b].numpy(), pick(width, b), pick(intensity, b), self.scale, self.threshold, dtype,
+                                    frac, validate) for b in range(x.shape[0])]
+        first = [r.get("first", r) for r in rows]
+        col = lambda rs, k, dt: torch.from_numpy(np.array([r[k] for r in rs], dtype=dt))
+        out = {"images": torch.from_numpy(np.stack([r["image"] for r in rows]).astype(dtype)),
+               "status": col(rows, "status", np.int32), "width_before": col(first, "source_width", dtype),
+               "factor": col(first, "factor", np.float64),
+               "bounds_before": torch.stack([col(first, "left", np.float64), col(first, "right", np.float64)], 1),
+               "shear_before": col(first, "shear", np.float64), "intensity_before": col(rows, "median", dtype)}
+        if validate:
+            out["width_after"], out["off_target"] = col(rows, "width_after", dtype), col(rows, "off_target", bool)
+        return out
 
 
 KINDS = ops.MORPHO_KINDS

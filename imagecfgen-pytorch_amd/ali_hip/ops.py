@@ -2169,6 +2169,73 @@ def morpho_bounds(x, scale, AH=None, AW=None, bound_frac=0.02, ws=None, debug=Fa
     return (bounds, hcdf, vcdf) if debug else bounds
 
 
+def morpho_width(x, scale, bits, fg, target, AH=None, AW=None, bound_frac=0.02, ws=None, debug=False):
+    """The measuring half of ``SetWidth`` (include/ali_hip.h: ali_morpho_width): x, AH, AW as ``morpho_binarise`` takes
+    them, bits and fg what it returned for x; target: float64 [B], the target widths.  Returns (sums int64 [B, 6] of the
+    bitmaps, wb float64 [B, 6] = left, right, shear, cx, cy, factor, status int32 [B]), and with ``debug`` also hcdf
+    float64 [B, W * scale].  The scratch is ``morpho_bounds_scratch_bytes``."""
+    lib = _lib.load()
+    ptr, ld, B, H, W, Hh, Wh = _morpho_images(x, scale)
+    if scale > 1:
+        for a, n in ((AH, H), (AW, W)):
+            if a is None or tuple(a.shape) != (n * scale, n):
+                raise ValueError(f"morpho_width: need an expand operator of shape {(n * scale, n)}")
+    bound_frac = float(bound_frac)
+    if not 0.0 < bound_frac < 1.0:
+        raise ValueError(f"morpho_width: 0 < bound_frac < 1, got {bound_frac}")
+    dev = x.device
+    sums = torch.empty(B, 6, dtype=torch.int64, device=dev)
+    wb = torch.empty(B, 6, dtype=torch.float64, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    hcdf = torch.empty(B, Wh, dtype=torch.float64, device=dev) if debug else None
+    wp, wn = _morpho_ws(ws, dev)
+    _lib.check(lib.ali_morpho_width(ptr, ld, B, H, W, int(scale), None if scale == 1 else _chk(AH, "AH"),
+                                    None if scale == 1 else _chk(AW, "AW"),
+                                    _i32s(bits, (B, Hh, (Wh + 31) // 32), "bin"), _i32(fg, "fg", B), bound_frac,
+                                    _f64(target, (B,), "target"), c_void_p(sums.data_ptr()), c_void_p(wb.data_ptr()),
+                                    _i32(status, "status"), None if hcdf is None else _f64(hcdf, (B, Wh), "hcdf"), wp, wn,
+                                    _stream()), "ali_morpho_width")
+    return (sums, wb, status, hcdf) if debug else (sums, wb, status)
+
+
+def morpho_affine_reduce(bits, H, W, scale, sums, wb, status, RH=None, RW=None, ws=None, debug=False, out=None):
+    """The warp of ``SetWidth`` and ``downscale`` (include/ali_hip.h: ali_morpho_affine_reduce) of the bitmaps bits [B, H
+    * scale, ceil(W * scale / 32)] with sums, wb and status as ``morpho_width`` returned them; RH, RW as
+    ``morpho_shear_reduce`` takes them.  Returns (q fp32 [B, H, W] grey levels, status int32 [B]: 4 where q is 0
+    everywhere), and with ``debug`` also (raw fp32 [B, H, W], the warped bitmaps' words like bits); ``out``: the tensor q
+    is written into."""
+    lib = _lib.load()
+    scale = int(scale)
+    Hh, Wh = H * scale, W * scale
+    if H < 1 or W < 1 or scale < 1 or Hh > MORPHO_MAX_SIDE or Wh > MORPHO_MAX_SIDE:
+        raise ValueError(f"morpho: {H} x {W} images at scale {scale} exceed the limit of {MORPHO_MAX_SIDE} x "
+                         f"{MORPHO_MAX_SIDE} up-sampled pixels")
+    if not (bits.is_cuda and bits.dim() == 3 and tuple(bits.shape[1:]) == (Hh, (Wh + 31) // 32)):
+        raise ValueError(f"morpho_affine_reduce: bits is [B, {Hh}, {(Wh + 31) // 32}]")
+    B = bits.shape[0]
+    if scale > 1:
+        for a, n in ((RH, H), (RW, W)):
+            if a is None or tuple(a.shape) != (n, n * scale):
+                raise ValueError(f"morpho_affine_reduce: need a reduce operator of shape {(n, n * scale)}")
+    dev = bits.device
+    q = torch.empty(B, H, W, dtype=torch.float32, device=dev) if out is None else out
+    if tuple(q.shape) != (B, H, W):
+        raise ValueError(f"morpho_affine_reduce: out is [{B}, {H}, {W}]")
+    status_out = torch.empty(B, dtype=torch.int32, device=dev)
+    raw = torch.empty(B, H, W, dtype=torch.float32, device=dev) if debug else None
+    warped = torch.empty_like(bits) if debug else None
+    wp, wn = _morpho_ws(ws, dev)
+    _lib.check(lib.ali_morpho_affine_reduce(_i32s(bits, (B, Hh, (Wh + 31) // 32), "bin"),
+                                            _typed(sums, torch.int64, (B, 6), "sums"), _f64(wb, (B, 6), "wb"),
+                                            _i32(status, "status", B), B, H, W, scale,
+                                            None if scale == 1 else _f64(RH, (H, Hh), "RH"),
+                                            None if scale == 1 else _f64(RW, (W, Wh), "RW"), _chk(q, "q"), _opt(raw, "raw"),
+                                            None if warped is None else _i32(warped, "warped"),
+                                            _i32(status_out, "status_out"), wp, wn, _stream()),
+               "ali_morpho_affine_reduce")
+    return (q, status_out, raw, warped) if debug else (q, status_out)
+
+
 MORPHO_MAX_RADIUS = 64           # the largest radius of ali_morpho_reshape's half-width table
 
 

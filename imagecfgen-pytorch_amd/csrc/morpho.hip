@@ -37,7 +37,8 @@
 //             once, quantised with a guard of 1/128 grey level.
 //   set_intensity  the median of the bright pixels by `measure`'s selection, q * (target / median) clipped to 0 .. 255.
 // The local perturbations (ali_morpho_locate, ali_morpho_local; the statement is morphomnist/skeleton.py and the second
-// half of morphomnist/perturb.py) are described in front of their kernels below.
+// half of morphomnist/perturb.py) are described in front of their kernels below, as are the bounding parallelogram
+// (ali_morpho_bounds) and SetWidth (ali_morpho_width, ali_morpho_affine_reduce).
 // Every sum runs in a fixed order (ali_reduce.h): the same inputs give the same bits on every run.
 #include "ali_reduce.h"
 
@@ -602,6 +603,50 @@ __device__ int row_shift(double delta, double cy, int y, int Wh) {
   return (int)fmin(fmax(f, -(double)Wh), (double)Wh);
 }
 
+// downscale of the warped bitmap s_w (LDS, pad bits 0) of one image by the whole block: T = warped RWt into Tb (a sum
+// over the set pixels of a row, ascending), raw = 255 * RH T rounded to fp32 once, Q = floor(clip(raw, 0, 255) + 2^-7).
+// Shared by ali_morpho_shear_reduce and ali_morpho_affine_reduce.  Returns whether this thread wrote a Q above 0.
+__device__ __forceinline__ bool reduce_warped(const uint32_t* s_w, int H, int W, int s, int wpr,
+                                              const double* __restrict__ RH, const double* __restrict__ RW,
+                                              double* __restrict__ Tb, float* __restrict__ Q, float* __restrict__ raw) {
+  const int tid = threadIdx.x, Hh = H * s, Wh = W * s, N = H * W;
+  bool any = false;
+  if (s > 1) {
+    for (int e = tid; e < Hh * W; e += kMoBlock) {
+      const int y = e / W, c = e % W;
+      const double* rw = RW + (long long)c * Wh;
+      double acc = 0.0;
+      for (int w = 0; w < wpr; ++w) {
+        uint32_t u = s_w[y * wpr + w];
+        while (u) {
+          const int bit = __ffs(u) - 1;
+          u &= u - 1;
+          acc += rw[32 * w + bit];
+        }
+      }
+      Tb[e] = acc;
+    }
+    __syncthreads();                                                 // (the block reads what the block wrote)
+  }
+  for (int e = tid; e < N; e += kMoBlock) {
+    const int i = e / W, c = e % W;
+    double acc;
+    if (s > 1) {
+      acc = 0.0;
+      const double* rh = RH + (long long)i * Hh;
+      for (int y = 0; y < Hh; ++y) acc = fma(rh[y], Tb[y * W + c], acc);
+    } else {
+      acc = (double)((s_w[i * wpr + (c >> 5)] >> (c & 31)) & 1u);
+    }
+    const float v = (float)(255.0 * acc);
+    if (raw) raw[e] = v;
+    const float q = floorf(fminf(fmaxf(v, 0.f), 255.f) + 0.0078125f);
+    Q[e] = q;
+    any = any || q > 0.f;
+  }
+  return any;
+}
+
 // SetSlant and downscale: the bitmap sheared row by row (nearest neighbour, 0 outside) into LDS, T = warped RWt into
 // the workspace (a sum over the set pixels of a row, ascending), raw = 255 * RH T rounded to fp32 once, q =
 // floor(clip(raw, 0, 255) + 2^-7) in fp32.  Operators, T and both sums are fp64: the rows of the reduce operator have
@@ -649,38 +694,7 @@ morpho_shear_reduce_kernel(const uint32_t* __restrict__ bin, const long long* __
     s_w[e] = (uint32_t)(((hi << 32) | lo) >> off) & tail_mask(w, wpr, Wh);
   }
   __syncthreads();
-  double* Tb = T + (long long)b * Hh * W;
-  if (s > 1) {
-    for (int e = tid; e < Hh * W; e += kMoBlock) {
-      const int y = e / W, c = e % W;
-      const double* rw = RW + (long long)c * Wh;
-      double acc = 0.0;
-      for (int w = 0; w < wpr; ++w) {
-        uint32_t u = s_w[y * wpr + w];
-        while (u) {
-          const int bit = __ffs(u) - 1;
-          u &= u - 1;
-          acc += rw[32 * w + bit];
-        }
-      }
-      Tb[e] = acc;
-    }
-    __syncthreads();                                                 // (the block reads what the block wrote)
-  }
-  for (int e = tid; e < N; e += kMoBlock) {
-    const int i = e / W, c = e % W;
-    double acc;
-    if (s > 1) {
-      acc = 0.0;
-      const double* rh = RH + (long long)i * Hh;
-      for (int y = 0; y < Hh; ++y) acc = fma(rh[y], Tb[y * W + c], acc);
-    } else {
-      acc = (double)((s_w[i * wpr + (c >> 5)] >> (c & 31)) & 1u);
-    }
-    const float v = (float)(255.0 * acc);
-    if (raw) raw[(long long)b * N + e] = v;
-    Q[e] = floorf(fminf(fmaxf(v, 0.f), 255.f) + 0.0078125f);
-  }
+  reduce_warped(s_w, H, W, s, wpr, RH, RW, T + (long long)b * Hh * W, Q, raw ? raw + (long long)b * N : nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------------ intensity
@@ -1283,6 +1297,223 @@ morpho_bounds_kernel(const float* __restrict__ x, long long ld, int H, int W, in
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------- width
+// SetWidth (morphomnist/perturb.py: width_stage, width_columns, affine_stage).  morpho_width_kernel measures: the
+// bitmap's integer moment sums, shear / cx / cy from them as shear_of_sums forms them, then pass 2 of
+// morpho_bounds_kernel under THESE moments -- the rows of hires by bounds_tile, their fp64 prefixes in LDS, the bins by
+// bounds_count -- with the grey mass m00 taken as the running total of the rows (every thread adds the same segment
+// totals in the same order: the same bits in every thread), the horizontal cdf alone and its two crossings.  T lives
+// where morpho_bounds_kernel keeps it (LDS up to kBdLdsT floats).  morpho_affine_reduce_kernel warps: a thread per
+// output pixel forms the source column in fp64 in the statement's order, reads that bit of the row and the wave packs
+// 64 of them by ballot into LDS; then reduce_warped.
+constexpr int kMoBadTarget = 5;                                      // status: the target width is NaN, infinite or <= 0
+
+// k = shear * (1 - factor): the off-diagonal entry of SetWidth's matrix
+__device__ double width_offdiag(double shear, double factor) {
+#pragma clang fp contract(off)
+  const double g = 1.0 - factor;
+  return shear * g;
+}
+// u(x) = cx + a * (x - cx) and v(y) = k * (y - cy): the two halves of a source column
+__device__ double width_along(double a, double cx, int x) {
+#pragma clang fp contract(off)
+  const double dx = (double)x - cx;
+  const double p = a * dx;
+  return cx + p;
+}
+__device__ double width_across(double k, double cy, int y) {
+#pragma clang fp contract(off)
+  const double dy = (double)y - cy;
+  return k * dy;
+}
+// floor((u + v) + 0.5) held to -1 .. Wh (a NaN: -1)
+__device__ int width_column(double u, double v, int Wh) {
+#pragma clang fp contract(off)
+  const double w = u + v;
+  const double z = w + 0.5;
+  const double f = floor(z);
+  if (!(f == f)) return -1;
+  return (int)fmin(fmax(f, -1.0), (double)Wh);
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(kMoBlock)
+morpho_width_kernel(const float* __restrict__ x, long long ld, int H, int W, int s, const float* __restrict__ AH,
+                    const float* __restrict__ AW, const uint32_t* __restrict__ bin, int wpr, const int* __restrict__ fg,
+                    double frac, const double* __restrict__ target, float* __restrict__ Tws,
+                    long long* __restrict__ sums, double* __restrict__ wb, int* __restrict__ status,
+                    double* __restrict__ hcdf) {
+  __shared__ double s_big[kBdLdsT / 2];                              // T (MODE 1); after pass 2: hcdf
+  __shared__ double s_P[kMoMaxSide + 1];                             // the prefix of the current row
+  __shared__ double s_seg[2 * kMoWaves];                             // its 64-column segment totals
+  __shared__ float s_f[kMoWaves];
+  __shared__ long long s_l[kMoWaves];
+  __shared__ int s_i[kMoWaves];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int Hh = H * s, Wh = W * s, nw = Hh * wpr;
+  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+  // leave with a status: sums 0, wb NaN, hcdf 0 (st is uniform in the block wherever this is called)
+  auto leave = [&](int st) {
+    if (hcdf)
+      for (int t = tid; t < Wh; t += kMoBlock) hcdf[(long long)b * Wh + t] = 0.0;
+    if (tid < 6) {
+      sums[(long long)b * 6 + tid] = 0;
+      wb[(long long)b * 6 + tid] = nan;
+    }
+    if (tid == 0) status[b] = st;
+  };
+  const double tgt = target[b];
+  if (fg[b] == Hh * Wh) return leave(1);
+  if (!(tgt > 0.0) || isinf(tgt)) return leave(kMoBadTarget);
+  // the bitmap's six sums
+  const uint32_t* bm = bin + (long long)b * nw;
+  long long m[6] = {0, 0, 0, 0, 0, 0};
+  for (int e = tid; e < nw; e += kMoBlock) {
+    const long long yy = e / wpr;
+    const int x0 = 32 * (e % wpr);
+    uint32_t u = bm[e] & tail_mask(e, wpr, Wh);
+    while (u) {
+      const long long xx = x0 + __ffs(u) - 1;
+      u &= u - 1;
+      m[0] += 1; m[1] += xx; m[2] += yy; m[3] += xx * xx; m[4] += xx * yy; m[5] += yy * yy;
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 6; ++q) m[q] = waves_sum<kMoWaves>(wave_lsum(m[q]), s_l);
+  if (m[0] == 0 || m[0] * m[5] == m[2] * m[2]) return leave(kMoStuck);   // empty, or one row (u02 == 0)
+  double shear, middle;
+  shear_of_sums(m, &shear, &middle);
+  const double cx = __ddiv_rn((double)m[1], (double)m[0]);
+  // T = (X - min) AWt
+  const float* X = x + (long long)b * ld;
+  float* T = MODE == 0 ? nullptr : MODE == 1 ? reinterpret_cast<float*>(s_big) : Tws + (long long)b * H * Wh;
+  float xmn = INFINITY;
+  for (int e = tid; e < H * W; e += kMoBlock) xmn = fminf(xmn, X[e]);
+  xmn = -block_max<kMoWaves>(-xmn, s_f);
+  if (MODE != 0) {
+    for (int e = tid; e < H * Wh; e += kMoBlock) {
+      const int r = e / Wh, j = e % Wh;
+      float acc = 0.f;
+      for (int c = 0; c < W; ++c) acc = fmaf(X[r * W + c] - xmn, AW[j * W + c], acc);
+      T[e] = acc;
+    }
+    __syncthreads();                                                 // (the block reads what the block wrote)
+  }
+  // the rows, their prefixes, the bins (morpho_bounds_kernel's pass 2)
+  const int j0 = tid, j1 = tid + kMoBlock;
+  double hacc[2] = {0.0, 0.0}, m00 = 0.0;
+  if (tid == 0) s_P[0] = 0.0;
+  for (int i0 = 0; i0 < Hh; i0 += kMoRows) {
+    float v0[kMoRows], v1[kMoRows];
+    if (j0 < Wh) bounds_tile<MODE>(X, xmn, H, W, Hh, Wh, T, AH, i0, j0, v0);
+    if (j1 < Wh) bounds_tile<MODE>(X, xmn, H, W, Hh, Wh, T, AH, i0, j1, v1);
+#pragma unroll
+    for (int k = 0; k < kMoRows; ++k) {
+      const int y = i0 + k;
+      if (y >= Hh) break;                                            // (uniform)
+      double a = j0 < Wh ? (double)v0[k] : 0.0, c = j1 < Wh ? (double)v1[k] : 0.0;
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) {                             // inclusive scans along the wave, in a fixed order
+        const double pa = __shfl_up(a, d, 64), pc = __shfl_up(c, d, 64);
+        if (lane >= d) { a = pa + a; c = pc + c; }
+      }
+      if (lane == 63) { s_seg[wave] = a; s_seg[kMoWaves + wave] = c; }
+      __syncthreads();
+      double run = 0.0, off0 = 0.0, off1 = 0.0;                      // the segments in column order
+#pragma unroll
+      for (int q = 0; q < 2 * kMoWaves; ++q) {
+        if (q == wave) off0 = run;
+        if (q == kMoWaves + wave) off1 = run;
+        run = run + s_seg[q];
+      }
+      if (j0 < Wh) s_P[j0 + 1] = off0 + a;
+      if (j1 < Wh) s_P[j1 + 1] = off1 + c;
+      m00 = m00 + run;
+      __syncthreads();
+      if (j0 < Wh) hacc[0] += s_P[bounds_count(j0, y, shear, middle, Wh)];
+      if (j1 < Wh) hacc[1] += s_P[bounds_count(j1, y, shear, middle, Wh)];
+    }
+  }
+  __syncthreads();                                                   // (the last reads of T and s_P lie before here)
+  double* s_hc = s_big;
+  if (j0 < Wh) s_hc[j0] = hacc[0] / m00;
+  if (j1 < Wh) s_hc[j1] = hacc[1] / m00;
+  __syncthreads();
+  const double half = frac / 2.0, upper = 1.0 - half;
+  const double left = bounds_locate(s_hc, Wh, half, false, s_i);
+  const double right = bounds_locate(s_hc, Wh, upper, true, s_i);
+  const bool ok = m00 > 0.0 && isfinite(shear);
+  const double width = ok ? __ddiv_rn(__dsub_rn(right, left), (double)s) : nan;
+  if (!(isfinite(width) && width > 0.0)) return leave(kMoStuck);      // (uniform: every thread holds the same values)
+  if (hcdf)
+    for (int t = tid; t < Wh; t += kMoBlock) hcdf[(long long)b * Wh + t] = s_hc[t];
+  if (tid == 0) {
+    double* o = wb + (long long)b * 6;
+    o[0] = left; o[1] = right; o[2] = shear; o[3] = cx; o[4] = middle; o[5] = __ddiv_rn(width, tgt);
+    for (int q = 0; q < 6; ++q) sums[(long long)b * 6 + q] = m[q];
+    status[b] = 0;
+  }
+}
+
+__global__ void __launch_bounds__(kMoBlock)
+morpho_affine_reduce_kernel(const uint32_t* __restrict__ bin, const long long* __restrict__ sums,
+                            const double* __restrict__ wb, const int* __restrict__ status, int H, int W, int s, int wpr,
+                            const double* __restrict__ RH, const double* __restrict__ RW, double* __restrict__ T,
+                            float* __restrict__ qout, float* __restrict__ raw, uint32_t* __restrict__ warped,
+                            int* __restrict__ status_out) {
+  __shared__ uint32_t s_w[kMoMaxSide * (kMoMaxSide / 32)];
+  __shared__ int s_i[kMoWaves];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int Hh = H * s, Wh = W * s, nw = Hh * wpr, N = H * W;
+  float* Q = qout + (long long)b * N;
+  const int st = status[b];
+  if (st != 0) {                                                     // (uniform)
+    for (int e = tid; e < N; e += kMoBlock) {
+      Q[e] = 0.f;
+      if (raw) raw[(long long)b * N + e] = 0.f;
+    }
+    if (warped)
+      for (int e = tid; e < nw; e += kMoBlock) warped[(long long)b * nw + e] = 0u;
+    if (tid == 0) status_out[b] = st;
+    return;
+  }
+  double shear, cy;
+  shear_of_sums(sums + (long long)b * 6, &shear, &cy);
+  const double cx = __ddiv_rn((double)sums[(long long)b * 6 + 1], (double)sums[(long long)b * 6]);
+  const double factor = wb[(long long)b * 6 + 5];
+  const double k = width_offdiag(shear, factor);
+  const uint32_t* bm = bin + (long long)b * nw;
+  // a thread owns columns tid and tid + kMoBlock (Wh <= 2 * kMoBlock); 64 pixels of a row make two words by ballot
+  double u[2];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) u[h] = width_along(factor, cx, tid + h * kMoBlock);
+  for (int y = 0; y < Hh; ++y) {
+    const double v = width_across(k, cy, y);
+    const uint32_t* row = bm + y * wpr;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int j = tid + h * kMoBlock;
+      if (h * kMoBlock >= Wh) break;                                 // (uniform: every lane reaches the ballot)
+      bool set = false;
+      if (j < Wh) {
+        const int c = width_column(u[h], v, Wh);
+        if (c >= 0 && c < Wh) set = (row[c >> 5] >> (c & 31)) & 1u;
+      }
+      const unsigned long long bits = __ballot(set);
+      const int w0 = (h * kMoBlock + (tid & ~63)) >> 5;
+      if ((tid & 63) == 0 && w0 < wpr) s_w[y * wpr + w0] = (uint32_t)bits;
+      if ((tid & 63) == 32 && w0 + 1 < wpr) s_w[y * wpr + w0 + 1] = (uint32_t)(bits >> 32);
+    }
+  }
+  __syncthreads();
+  if (warped)
+    for (int e = tid; e < nw; e += kMoBlock) warped[(long long)b * nw + e] = s_w[e];
+  const bool any = reduce_warped(s_w, H, W, s, wpr, RH, RW, T + (long long)b * Hh * W, Q,
+                                 raw ? raw + (long long)b * N : nullptr);
+  const int lit = block_imax(any ? 1 : 0, s_i);
+  if (tid == 0) status_out[b] = lit ? 0 : kMoStuck;                  // (Q is 0 everywhere already)
+}
+
 // the side limits every entry point shares
 static int morpho_check_dims(const char* who, int32_t B, int32_t Hh, int32_t Wh) {
   if (B < 1 || Hh < 1 || Wh < 1 || Hh > kMoMaxSide || Wh > kMoMaxSide) {
@@ -1584,4 +1815,63 @@ extern "C" int ali_morpho_bounds(const float* x, int64_t ld, int32_t B, int32_t 
     hipLaunchKernelGGL(morpho_bounds_kernel<2>, dim3((unsigned)B), dim3(kMoBlock), 0, ST(stream), x, (long long)ld,
                        (int)H, (int)W, (int)scale, AH, AW, bound_frac, static_cast<float*>(T), bounds, hcdf, vcdf);
   return check_launch("morpho_bounds_kernel");
+}
+
+extern "C" int ali_morpho_width(const float* x, int64_t ld, int32_t B, int32_t H, int32_t W, int32_t scale,
+                                const float* AH, const float* AW, const uint32_t* bin, const int32_t* fg,
+                                double bound_frac, const double* target, int64_t* sums, double* wb, int32_t* status,
+                                double* hcdf, void* ws, size_t ws_bytes, ali_stream_t stream) {
+  if (!x || !bin || !fg || !target || !sums || !wb || !status || (scale > 1 && (!AH || !AW))) {
+    set_error("ali_morpho_width: NULL argument");
+    return ALI_ERR_BAD_ARG;
+  }
+  if (H < 1 || W < 1 || scale < 1 || ld < (int64_t)H * W || !(bound_frac > 0.0 && bound_frac < 1.0)) {
+    set_error("ali_morpho_width: H = %d, W = %d or scale = %d < 1, ld = %lld < H * W, or bound_frac = %g outside (0, 1)",
+              (int)H, (int)W, (int)scale, (long long)ld, bound_frac);
+    return ALI_ERR_BAD_ARG;
+  }
+  int rc = morpho_check_dims("ali_morpho_width", B, hires_side(H, scale), hires_side(W, scale));
+  if (rc != ALI_OK) return rc;
+  const int Wh = W * scale, wpr = (Wh + 31) / 32;
+  const int mode = scale == 1 ? 0 : (H * Wh <= kBdLdsT ? 1 : 2);
+  void* T = nullptr;
+  rc = morpho_scratch("ali_morpho_width", ws, ws_bytes, mode == 2 ? sizeof(float) * (size_t)B * H * Wh : 0, &T);
+  if (rc != ALI_OK) return rc;
+  auto launch = [&](auto kernel, int s) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(kMoBlock), 0, ST(stream), x, (long long)ld, (int)H, (int)W, s, AH,
+                       AW, bin, wpr, reinterpret_cast<const int*>(fg), bound_frac, target, static_cast<float*>(T),
+                       reinterpret_cast<long long*>(sums), wb, reinterpret_cast<int*>(status), hcdf);
+  };
+  if (mode == 0)
+    launch(morpho_width_kernel<0>, 1);
+  else if (mode == 1)
+    launch(morpho_width_kernel<1>, (int)scale);
+  else
+    launch(morpho_width_kernel<2>, (int)scale);
+  return check_launch("morpho_width_kernel");
+}
+
+extern "C" int ali_morpho_affine_reduce(const uint32_t* bin, const int64_t* sums, const double* wb,
+                                        const int32_t* status, int32_t B, int32_t H, int32_t W, int32_t scale,
+                                        const double* RH, const double* RW, float* q, float* raw, uint32_t* warped,
+                                        int32_t* status_out, void* ws, size_t ws_bytes, ali_stream_t stream) {
+  if (!bin || !sums || !wb || !status || !q || !status_out || (scale > 1 && (!RH || !RW))) {
+    set_error("ali_morpho_affine_reduce: NULL argument");
+    return ALI_ERR_BAD_ARG;
+  }
+  if (H < 1 || W < 1 || scale < 1) {
+    set_error("ali_morpho_affine_reduce: H = %d, W = %d or scale = %d < 1", (int)H, (int)W, (int)scale);
+    return ALI_ERR_BAD_ARG;
+  }
+  int rc = morpho_check_dims("ali_morpho_affine_reduce", B, hires_side(H, scale), hires_side(W, scale));
+  if (rc != ALI_OK) return rc;
+  void* T = nullptr;
+  rc = morpho_scratch("ali_morpho_affine_reduce", ws, ws_bytes,
+                      scale > 1 ? sizeof(double) * (size_t)B * H * scale * W : 0, &T);
+  if (rc != ALI_OK) return rc;
+  hipLaunchKernelGGL(morpho_affine_reduce_kernel, dim3((unsigned)B), dim3(kMoBlock), 0, ST(stream), bin,
+                     reinterpret_cast<const long long*>(sums), wb, reinterpret_cast<const int*>(status), (int)H, (int)W,
+                     (int)scale, (W * scale + 31) / 32, RH, RW, static_cast<double*>(T), q, raw, warped,
+                     reinterpret_cast<int*>(status_out));
+  return check_launch("morpho_affine_reduce_kernel");
 }

@@ -1,11 +1,11 @@
 """The perturbations the measured-counterfactual scripts and the data-set builders use -- ``SetThickness``, ``SetSlant``,
-``SetIntensity`` -- and the four of the published Morpho-MNIST data sets -- ``Thinning``, ``Thickening``, ``Swelling``,
-``Fracture`` -- written on numpy and scipy alone, with the scripts' five-line chain for one image,
-``counterfactual_image``, and the data sets' chain, ``local_image``.  This module is the *statement* the kernels
-``ali_morpho_reshape``, ``ali_morpho_shear_reduce``, ``ali_morpho_set_intensity``, ``ali_morpho_locate`` and
-``ali_morpho_local`` (csrc/morpho.hip) are tested against; agreement with scikit-image's ``dilation`` / ``pyramid_reduce`` /
-``warp`` / ``draw.line`` has not been checked (DESIGN 3.17 and 3.20 say why, and list the deviations).  ``SetWidth`` is
-not built.
+``SetIntensity``, ``SetWidth`` -- and the four of the published Morpho-MNIST data sets -- ``Thinning``, ``Thickening``,
+``Swelling``, ``Fracture`` -- written on numpy and scipy alone, with the scripts' five-line chain for one image,
+``counterfactual_image``, the data sets' chain, ``local_image``, and the width chain, ``width_image``.  This module is
+the *statement* the kernels ``ali_morpho_reshape``, ``ali_morpho_shear_reduce``, ``ali_morpho_set_intensity``,
+``ali_morpho_locate``, ``ali_morpho_local``, ``ali_morpho_width`` and ``ali_morpho_affine_reduce`` (csrc/morpho.hip) are
+tested against; agreement with scikit-image's ``dilation`` / ``pyramid_reduce`` / ``warp`` / ``draw.line`` has not been
+checked (DESIGN 3.17, 3.20 and 3.22 say why, and list the deviations).
 
   footprint  ``SetThickness`` dilates / erodes by a disk of 16 r made small again: the support of zoom(gaussian(disk(16 r),
              16 / 3), (2 r + 1) / (32 r + 1), order 1).  The 16 is the reference's constant in ``_get_disk``, not the
@@ -19,19 +19,24 @@ not built.
   swell      ``Swelling``: the radial power warp around a location drawn on the skeleton, nearest neighbour, 0 outside.
   fracture   ``Fracture``: cuts of a disk brush along digital lines across the stroke, at locations drawn on the skeleton
              away from its tips and forks (``morphomnist.skeleton``), perpendicular to its local direction.
+  width      ``SetWidth``: row y of the bitmap read at the column ``width_columns`` gives -- the horizontal scaling by
+             factor = measured width / target about the bitmap's centroid that keeps its shear -- nearest neighbour,
+             constant 0.  The width is the bounding parallelogram's, measured on the grey up-sampled image under the
+             bitmap's shear and centroid row (``measure_width``).
 """
 import functools
 
 import numpy as np
 from scipy import ndimage
 
-from .morpho import ImageMoments, ImageMorphology, intensity, quantise_levels, reduce, squared_distance
+from .morpho import (ImageMoments, ImageMorphology, binarise, bounds_of, expand, intensity, measure_bounds,
+                     quantise_levels, reduce, squared_distance)
 
 DISK_SCALE = 16                  # the reference's ``_get_disk(radius, scale=16)``
 MAX_RADIUS = 64                  # the largest radius the kernels take (a 2049 x 2049 disk on the host, once)
 RADIUS_CAP = 2.0 ** 30           # a radius is reported up to here (status 3 long before)
 
-OK, NO_BACKGROUND, THIN_STUCK, RADIUS_TOO_LARGE, NOTHING_LEFT = 0, 1, 2, 3, 4
+OK, NO_BACKGROUND, THIN_STUCK, RADIUS_TOO_LARGE, NOTHING_LEFT, BAD_TARGET = 0, 1, 2, 3, 4, 5
 
 
 def disk(k):
@@ -529,3 +534,207 @@ def local_image(image, kind, scale=16, threshold=.5, seed=0, dtype=np.float64, c
     morph = ImageMorphology(image, threshold, scale, seed, dtype)
     return local_continue_from(morph.binary_image, morph.squared_distance, morph.skeleton, morph.mean_thickness, kind, H,
                                W, scale, morph.status, dtype, seed, counter, row, **params)
+
+
+# --------------------------------------------------------------------------------------------------- SetWidth
+WIDTH_TOLERANCE = 1.             # the reference's ``SetWidth._tolerance``, in pixels of the low-resolution image
+WIDTH_MAX_DEPTH = 4              # re-applications ``SetWidth(validate=True)`` makes at most (the reference: unbounded)
+
+
+class SumMoments:
+    """what ``bounding_parallelogram`` reads of an ``ImageMoments``, formed from a bitmap's six integer sums as
+    ``horizontal_shear`` forms them: ``centroid`` = (sx / n, sy / n), ``horizontal_shear`` = u11 / u02 -- the bits of
+    ``ImageMoments(bitmap)``"""
+
+    def __init__(self, sums):
+        with np.errstate(invalid="ignore", divide="ignore"):
+            self.horizontal_shear, cy = horizontal_shear(sums)
+            self.centroid = (np.float64(sums[1]) / np.float64(sums[0]), cy)
+
+
+def measure_width(morph, frac=.02, moments=None):
+    """The reference's ``_measure_width``: (right - left) / morph.scale of the bounding parallelogram of the grey
+    up-sampled image, ``moments`` (any object with ``centroid`` and ``horizontal_shear``; None: the image's own)
+    giving the shear and the middle row of the horizontal cdf.  The up-sampled image is expand(image - image.min(),
+    scale), DESIGN 3.21's rule: for an image whose minimum is 0 it is the reference's ``morph.hires_image`` (the same
+    deviation, for the same reason: an image in -1 .. 1 and the same image in 0 .. 255 measure alike).  The reference
+    subtracts the two top corners' x, which carry the same offset shear * (top - middle); the difference is taken of
+    left and right themselves here."""
+    image = np.asarray(morph.image, dtype=morph.dtype)
+    hires = expand(image - image.min(), morph.scale, morph.dtype)
+    left, right = bounds_of(hires, frac, moments)[:2]
+    return (right - left) / morph.scale
+
+
+def affine_columns(a, k, cx, cy, Hh, Wh):
+    """int64 [Hh, Wh]: floor(((cx + a * (x - cx)) + k * (y - cy)) + 0.5) held to -1 .. Wh, in fp64 with every operation
+    rounded on its own and in this order:
+
+        dx = x - cx;  p = a * dx;  u = cx + p;          (by column)
+        dy = y - cy;  v = k * dy;                       (by row)
+        w = u + v;  z = w + 0.5;  f = floor(z);  column = min(max(f, -1), Wh)     (a NaN: -1)
+
+    -1 and Wh both lie outside the image.  The row read is y itself."""
+    a, k, cx, cy = (np.float64(v) for v in (a, k, cx, cy))
+    with np.errstate(invalid="ignore", over="ignore"):
+        u = cx + a * (np.arange(Wh, dtype=np.float64) - cx)
+        v = k * (np.arange(Hh, dtype=np.float64) - cy)
+        f = np.floor((u[None, :] + v[:, None]) + np.float64(0.5))
+        f = np.where(f == f, np.minimum(np.maximum(f, -1.0), np.float64(Wh)), -1.0)
+    return f.astype(np.int64)
+
+
+def width_columns(factor, shear, cx, cy, Hh, Wh):
+    """int64 [Hh, Wh]: the source column of output pixel (y, x) under ``SetWidth``'s matrix [[factor, shear * (1 -
+    factor)], [0, 1]] about the centroid (cx, cy) -- ``LinearDeformation.warp`` followed by the rounding of a nearest
+    neighbour warp: floor(((cx + factor * (x - cx)) + (shear * (1 - factor)) * (y - cy)) + 0.5), held to -1 .. Wh
+    before the conversion.  Order of operations, each rounded to fp64 on its own, none fused:
+
+        g = 1 - factor;  k = shear * g;  then ``affine_columns(factor, k, cx, cy, Hh, Wh)``.
+
+    factor = source width / target width: a factor above 1 reads farther from the centroid, so the digit narrows."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        k = np.float64(shear) * (np.float64(1) - np.float64(factor))
+    return affine_columns(factor, k, cx, cy, Hh, Wh)
+
+
+def read_columns(bitmap, columns):
+    """out(y, x) = bitmap(y, columns[y, x]), 0 where the column lies outside the image"""
+    bitmap = np.asarray(bitmap, dtype=bool)
+    H, W = bitmap.shape
+    inside = (columns >= 0) & (columns < W)
+    return inside & bitmap[np.arange(H)[:, None], np.clip(columns, 0, W - 1)]
+
+
+class SetWidth(Perturbation):
+    """``transform.warp`` of the boolean image under the horizontal scaling about its centroid that brings its
+    measured width to the target and keeps its shear: nearest neighbour, constant 0 (``width_columns``).
+    ``validate``: the reference's check -- the result is brought down, its width measured under its own grey moments,
+    and when that is more than ``WIDTH_TOLERANCE`` from the target the reference's message is printed and the
+    perturbation applied once more to the morphology of the downscaled result.  The reference recurses without a
+    bound; here at most ``WIDTH_MAX_DEPTH`` re-applications are made (``depth`` counts them)."""
+
+    _tolerance = WIDTH_TOLERANCE
+
+    def __init__(self, target_width, validate=False):
+        self.target_width = target_width
+        self._validate = validate
+
+    def __call__(self, morph, depth=0):
+        binary = np.asarray(morph.binary_image, dtype=bool)
+        sums = moment_sums(binary)
+        moments = SumMoments(sums)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            factor = measure_width(morph, moments=moments) / np.float64(self.target_width)
+        warped = read_columns(binary, width_columns(factor, moments.horizontal_shear, *moments.centroid, *binary.shape))
+        if self._validate and depth < WIDTH_MAX_DEPTH:
+            pert_morph = ImageMorphology(morph.downscale(warped), morph.threshold, morph.scale, morph.seed, morph.dtype)
+            width = measure_width(pert_morph)
+            if abs(width - self.target_width) > self._tolerance:
+                print(f"!!! Incorrect width after transformation: {width:.1f}, expected {self.target_width:.1f}.")
+                warped = self(pert_morph, depth + 1)
+        return warped
+
+
+WIDTH_VALUES = ("left", "right", "shear", "cx", "cy", "factor")      # the six fp64 values ``ali_morpho_width`` leaves
+
+
+def width_stage(binary, hires, target_width, scale, frac=.02, status=OK):
+    """The measuring half of ``SetWidth`` with its corners, as ``ali_morpho_width`` has it.  ``binary``: the bitmap [H s,
+    W s]; ``hires``: expand(image - image.min(), scale); ``status``: 0, or 1 for a bitmap without background.  Returns a
+    dict: ``sums`` (the bitmap's six integer moment sums), ``shear``, ``cx``, ``cy`` (of the sums, as
+    ``horizontal_shear`` forms them), ``left``, ``right`` (``bounds_of`` under that shear and cy), ``source_width`` =
+    (right - left) / scale, ``factor`` = source_width / target_width, ``hcdf`` and ``status``, decided in this order: the
+    status given; 5 for a target that is NaN, infinite or <= 0; 4 for an empty bitmap or one with every set pixel in one
+    row; 4 for a grey mass <= 0 or a width that is not finite or <= 0.  With a status the sums are 0 and the floats
+    NaN."""
+    nan = np.float64("nan")
+    out = dict(sums=np.zeros(6, dtype=np.int64), shear=nan, cx=nan, cy=nan, left=nan, right=nan, source_width=nan,
+               factor=nan, hcdf=None, status=int(status))
+    if status:
+        return out
+    target = np.float64(target_width)
+    if not (target > 0 and np.isfinite(target)):
+        out["status"] = BAD_TARGET
+        return out
+    sums = moment_sums(binary)
+    if sums[0] == 0 or one_row(sums):
+        out["status"] = NOTHING_LEFT
+        return out
+    moments = SumMoments(sums)
+    left, right, _, _, shear, cy, hcdf, _ = bounds_of(hires, frac, moments)
+    out["hcdf"] = hcdf
+    with np.errstate(invalid="ignore"):
+        width = (right - left) / np.float64(scale)
+    if not (np.isfinite(width) and width > 0):                      # (a mass <= 0 makes left and right NaN)
+        out["status"] = NOTHING_LEFT
+        return out
+    with np.errstate(over="ignore"):                                 # (a denormal target: the factor is infinite)
+        factor = width / target
+    out.update(sums=sums, shear=shear, cx=moments.centroid[0], cy=cy, left=left, right=right, source_width=width,
+               factor=factor)
+    return out
+
+
+def affine_stage(binary, factor, shear, cx, cy, scale, dtype=np.float64):
+    """The warp of ``SetWidth`` and the reduce of a bitmap with status 0, as ``ali_morpho_affine_reduce`` has them:
+    (warped bitmap, raw = 255 * reduce in ``dtype``, quantised)"""
+    warped = read_columns(binary, width_columns(factor, shear, cx, cy, *np.shape(binary)))
+    raw = dtype(255) * reduce(warped, scale, dtype)
+    return warped, raw, quantise_levels(raw)
+
+
+def width_continue_from(binary, hires, H, W, target_width, target_intensity=None, scale=16, status=OK,
+                        dtype=np.float64, frac=.02):
+    """The chain of ``width_image`` from a binary image [H s, W s] and the grey up-sampled image on (the tests hand it
+    the device's own bitmap): the dict of ``width_image``."""
+    Hh, Wh = H * scale, W * scale
+    out = width_stage(binary, hires, target_width, scale, frac, status)
+    out.update(warped=np.zeros((Hh, Wh), dtype=bool), raw=np.zeros((H, W), dtype=dtype),
+               quantised=np.zeros((H, W), dtype=dtype), median=dtype("nan"), image=np.zeros((H, W), dtype=dtype))
+    if out["status"]:
+        return out
+    out["warped"], out["raw"], q = affine_stage(binary, out["factor"], out["shear"], out["cx"], out["cy"], scale, dtype)
+    if q.max() == 0:
+        out["status"] = NOTHING_LEFT
+        return out
+    out["quantised"] = q
+    out["image"], out["median"] = set_intensity(q, target_intensity, dtype)
+    return out
+
+
+def width_image(image, width, intensity=None, scale=16, threshold=.5, dtype=np.float64, frac=.02, validate=False):
+    """``SetWidth(width)`` and ``morph.downscale`` for one image [H, W], then the scripts' intensity rescale when
+    ``intensity`` is given:
+
+        bitmap, sums -> shear, cx, cy -> left, right -> source_width, factor -> warped -> raw = 255 * reduce ->
+        quantised -> image
+
+    Returns a dict with all of these (``width_stage``'s keys, ``binary``, ``warped``, ``raw``, ``quantised``, ``median``,
+    ``image`` [H, W] in 0 .. 255) and ``status``: 0; 1: the bitmap has no background; 4 (NOTHING_LEFT): the bitmap is
+    empty, every set pixel lies in one row, the grey mass is <= 0, the measured width is not finite or <= 0, or the
+    quantised image is 0 everywhere; 5 (BAD_TARGET): the target is NaN, infinite or <= 0.  A non-zero status: ``image``
+    is 0.  ``validate``: ``width_after`` (the width of ``quantised`` under its own grey moments, ``measure_bounds``)
+    and ``off_target`` (|width_after - width| > WIDTH_TOLERANCE) are added, and an image that is off target is put
+    through the chain once more, from ``quantised``, exactly once (what ``MorphoPerturb.set_width`` does; the class
+    ``SetWidth`` recurses as the reference does); ``first`` then holds the first round's dict."""
+    image = np.asarray(image, dtype=dtype)
+    H, W = image.shape
+    hires = expand(image, scale, dtype)
+    binary = np.ones(hires.shape, dtype=bool) if image.max() == image.min() else binarise(hires, threshold)
+    grey = expand(image - image.min(), scale, dtype)
+    out = width_continue_from(binary, grey, H, W, width, None if validate else intensity, scale, int(binary.all()),
+                              dtype, frac)
+    out["binary"] = binary
+    if not validate:
+        return out
+    with np.errstate(invalid="ignore", divide="ignore"):
+        after = measure_bounds(out["quantised"], scale, frac, dtype)["width"]
+        off = bool(abs(after - np.float64(width)) > WIDTH_TOLERANCE)
+    if off:
+        first, out = out, width_image(out["quantised"], width, None, scale, threshold, dtype, frac)
+        out["first"] = first
+    out["width_after"], out["off_target"] = after, off
+    if not out["status"]:
+        out["image"], out["median"] = set_intensity(out["quantised"], intensity, dtype)
+    return out

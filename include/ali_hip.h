@@ -952,6 +952,41 @@ int ali_morpho_bounds(const float* x, int64_t ld, int32_t B, int32_t H, int32_t 
                       const float* AW, double bound_frac, double* bounds, double* hcdf, double* vcdf, void* ws,
                       size_t ws_bytes, ali_stream_t stream);
 
+/* SetWidth of Morpho-MNIST (morphomnist/perturb.py: width_stage, width_columns, affine_stage): the width of the bounding
+ * parallelogram measured on the grey up-sampled image under the BITMAP's shear and centroid row, then the horizontal
+ * scaling about the bitmap's centroid that brings that width to the target and keeps the shear, then downscale.  One
+ * workgroup per image, no atomics, integers and fixed-order fp64 sums, every fp64 operation of the statement rounded on
+ * its own: the same inputs give the same bits on every run.  Status values: 0; 1: the bitmap has no background (fg[b] ==
+ * Hh * Wh); 5: target[b] is NaN, infinite or <= 0; 4: the bitmap is empty or every set pixel lies in one row, the grey
+ * mass is <= 0, the width is not finite or <= 0, or the quantised image is 0 everywhere -- decided in this order.  An
+ * image with a status != 0 passes through as zeros.
+ *
+ * ali_morpho_width: x, ld, B, H, W, scale, AH, AW as ali_morpho_binarise takes them; bin, fg: what it wrote for the same
+ *   x.  sums [B][6] int64 = { count, sum x, sum y, sum x^2, sum x y, sum y^2 } of bin.  wb [B][6] fp64 = left, right,
+ *   shear, cx, cy, factor: shear = u11 / u02, cx = sum x / count, cy = sum y / count of the sums, as
+ *   ali_morpho_shear_reduce forms them; left, right = the first crossing of bound_frac / 2 and the last crossing of 1 -
+ *   bound_frac / 2 of hcdf[t] = sum over rows y of the fp64 prefix of row y of hires up to #{x : x + .5 < t + shear * (y -
+ *   cy)}, over m00 -- pass 2 of ali_morpho_bounds (the same fp32 fmaf chains for hires = expand(x - min x), the same
+ *   prefixes, comparison and interpolation) under the bitmap's moments; m00 = the rows' totals added in ascending y;
+ *   factor = ((right - left) / scale) / target[b].  target [B] fp64.  With a status sums are 0 and wb NaN.  hcdf [B][W *
+ *   scale] fp64 is written when non-NULL (0 with a status).  0 < bound_frac < 1.  ws as ali_morpho_bounds: >=
+ *   ALI_WS_RESERVED + 4 * B * H * W * scale bytes when scale > 1 and H * W * scale > 28 * 448, else none.  LDS: 54.4 KB.
+ * ali_morpho_affine_reduce: bin, sums, wb, status as ali_morpho_width left them: shear, cx and cy are formed from sums
+ *   again (the same bits as wb's), factor is wb[b][5].  Output pixel (y, x) of the warped bitmap reads bit c of row y of bin, c =
+ *   floor(((cx + factor * (x - cx)) + (shear * (1 - factor)) * (y - cy)) + 0.5) held to -1 .. Wh in fp64 (a NaN: -1),
+ *   each operation rounded on its own in the order morphomnist/perturb.py: width_columns fixes; 0 outside the image: the
+ *   columns equal numpy's bit for bit.  Then T, raw and q exactly as ali_morpho_shear_reduce forms them (RH, RW, ws and
+ *   the scale == 1 short cut as there).  q [B][H][W]; raw [B][H][W] and warped [B][H * scale][ceil(W * scale / 32)] (pad
+ *   bits 0) are written when non-NULL.  status_out [B] = status, or 4 when q is 0 everywhere.  LDS: 4 * 512 * 16 bytes. */
+int ali_morpho_width(const float* x, int64_t ld, int32_t B, int32_t H, int32_t W, int32_t scale, const float* AH,
+                     const float* AW, const uint32_t* bin, const int32_t* fg, double bound_frac, const double* target,
+                     int64_t* sums, double* wb, int32_t* status, double* hcdf, void* ws, size_t ws_bytes,
+                     ali_stream_t stream);
+int ali_morpho_affine_reduce(const uint32_t* bin, const int64_t* sums, const double* wb, const int32_t* status, int32_t B,
+                             int32_t H, int32_t W, int32_t scale, const double* RH, const double* RW, float* q,
+                             float* raw, uint32_t* warped, int32_t* status_out, void* ws, size_t ws_bytes,
+                             ali_stream_t stream);
+
 /* Attribute plumbing of one batch (mnist.py:47-55, audio_mnist.py:203-210, whalecalls.py:455): idx[b*n_cat + j] =
  * argmax of categorical attribute j (one-hot rows of n_classes[j] floats, or int32 when cat_is_int[j]; first maximum
  * like torch.argmax); cont[b*n_cont + j] = cont_in[j][b]. */
