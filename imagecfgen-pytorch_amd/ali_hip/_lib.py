@@ -225,6 +225,7 @@ SIGNATURES = {
     "ali_tconv_scatter_wgrad": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int64] + [c_int32] * 10
                                 + [c_void_p, c_size_t, c_void_p]),
     "ali_tconv_scatter": (c_int32, [c_void_p] * 4 + [c_int32] * 13 + [c_float, c_void_p]),
+    "ali_tconv_scatter_plan": (c_int32, [c_int32] * 13 + [POINTER(c_int64)]),
     "ali_tconv1_fwd": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int32] * 9 + [c_float, c_void_p, c_int32,
                                                                                             c_void_p]),
     "ali_tconv1_dgrad": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_float, c_void_p] + [c_int32] * 7

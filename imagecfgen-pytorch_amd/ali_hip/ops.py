@@ -1074,6 +1074,26 @@ def tconv_scatter_wgrad(big, small, sstride, dw, s_k, s_tap, B, P, Q, K, H, W, R
     return dw
 
 
+ScatterPlan = collections.namedtuple("ScatterPlan", "name lds blocks nt obh obw rb bands ws")
+
+
+def tconv_scatter_plan(op, B, H, W, C, Hout, Wout, R, S, stride, pad, NC=1, ostride=None):
+    """The launch plan of ``tconv_scatter`` (``op`` "fwd") / ``tconv_scatter_wgrad`` ("wgrad") for a shape, or None
+    where the launch refuses it (include/ali_hip.h: ali_tconv_scatter_plan; ``_lib.load().ali_last_error()`` says why).
+    B, H, W, C: the 64-channel map (the weight gradient's B, P, Q, K); Hout x Wout: the 1-2 channel map; ``ostride``: its
+    element stride (default NC).  ``name`` is "scatter<NT;OBHxOBW>" -- tconv_scatter_kernel<NT> on OBH x OBW output tiles
+    -- or "scatter_wgrad<NT;rbRB>" -- tconvs_wgrad_mfma_kernel<NT,4> on bands of RB rows; ``lds`` the dynamic LDS bytes,
+    ``blocks`` the grid, ``ws`` the weight gradient's workspace bytes.  Host arithmetic of the library: needs no GPU."""
+    out = (ctypes.c_int64 * 6)()
+    rc = _lib.load().ali_tconv_scatter_plan({"fwd": 0, "wgrad": 1}[op], B, H, W, C, Hout, Wout, NC,
+                                            NC if ostride is None else ostride, R, S, stride, pad, out)
+    if rc != 0:
+        return None
+    if op == "fwd":
+        return ScatterPlan(f"scatter<{out[0]};{out[1]}x{out[2]}>", out[3], out[4], out[0], out[1], out[2], 0, 0, 0)
+    return ScatterPlan(f"scatter_wgrad<{out[0]};rb{out[1]}>", out[3], out[4], out[0], 0, 0, out[1], out[2], out[5])
+
+
 def spect_post(y, B, T, F, out, mean=None, std=None, clip_k=3.0):
     lib = _lib.load()
     _lib.check(lib.ali_spect_post(_chk(y, "y"), B, T, F, _opt(mean, "mean"), _opt(std, "std"), float(clip_k),

@@ -956,40 +956,120 @@ extern "C" int32_t ali_tconv_scatter_ok(int32_t C, int32_t NC, int32_t R, int32_
           stride <= 4 && tuning().no_t1_mfma == 0) ? 1 : 0;      // (ALI_NO_T1_MFMA=1: the two-launch form, A/B)
 }
 
-extern "C" int ali_tconv_scatter(const float* x, const float* w_nc, const float* bias, float* out, int32_t B, int32_t H,
-                                 int32_t W, int32_t C, int32_t Hout, int32_t Wout, int32_t NC, int32_t ostride, int32_t R,
-                                 int32_t S, int32_t stride, int32_t pad, int32_t act, float slope, ali_stream_t stream) {
-  if (!x || !w_nc || !out || B <= 0 || B > 65535 || H <= 0 || W <= 0 || Hout <= 0 || Wout <= 0 || ostride < NC || pad < 0 ||
+// ---------------------------------------------------------------- launch plans of the scatter form
+// As the T1Plan functions above: the launch parameters of ali_tconv_scatter / ali_tconv_scatter_wgrad are decided ONCE
+// each, read by the launch, by ali_tconv_scatter_wgrad_ws and by the host query ali_tconv_scatter_plan.  No HIP call.
+struct TSPlan {
+  int NT;                   // tap tiles of 16 columns: the instantiation tconv_scatter_kernel<NT>
+  int OBH, OBW;             // output tile of a block
+  int N, LDC, ntx;          // tap columns, pitch of the contribution rows, tiles per output row
+  size_t lds;
+  long long nblk;           // tiles per image (grid.x; grid.y = B)
+};
+
+static int ts_plan_fwd(int B, int H, int W, int C, int Hout, int Wout, int NC, int ostride, int R, int S, int stride,
+                       int pad, TSPlan& pl) {
+  if (B <= 0 || B > 65535 || H <= 0 || W <= 0 || Hout <= 0 || Wout <= 0 || ostride < NC || pad < 0 ||
       !ali_tconv_scatter_ok(C, NC, R, S, stride)) {
     set_error("ali_tconv_scatter: bad argument (needs 64 input channels, 1-2 output channels, <= 64 tap columns)");
     return ALI_ERR_BAD_ARG;
   }
-  TSDesc d = {};
-  d.x = x; d.w = w_nc; d.bias = bias; d.out = out;
-  d.B = B; d.H = H; d.W = W; d.Hout = Hout; d.Wout = Wout; d.NC = NC; d.ostride = ostride; d.R = R; d.S = S;
-  d.stride = stride; d.pad = pad; d.act = act; d.slope = slope;
-  d.N = NC * R * S;
-  d.LDC = d.N | 1;
+  pl.N = NC * R * S;
+  pl.LDC = pl.N | 1;
   // output tile: as large as 64 KB of contributions allow (two blocks per CU), at most 32 x 64
   int obh = 32, obw = 64;
   auto npx = [&](int bh, int bw) {
     return (long long)((bh - 1 + R - 1) / stride + 1) * ((bw - 1 + S - 1) / stride + 1);
   };
-  while (npx(obh, obw) * d.LDC * 4 > 64 * 1024 && (obh > 4 || obw > 8)) {
+  while (npx(obh, obw) * pl.LDC * 4 > 64 * 1024 && (obh > 4 || obw > 8)) {
     if (obw > 2 * obh && obw > 8) obw >>= 1; else if (obh > 4) obh >>= 1; else obw >>= 1;
   }
-  if (npx(obh, obw) * d.LDC * 4 > 64 * 1024 || npx(obh, obw) >= 65536) { set_error("ali_tconv_scatter: filter too large"); return ALI_ERR_BAD_ARG; }
-  d.OBH = obh; d.OBW = obw;
-  d.ntx = (Wout + obw - 1) / obw;
-  const long long nblk = (long long)d.ntx * ((Hout + obh - 1) / obh);
-  if (nblk >= (1LL << 31)) { set_error("ali_tconv_scatter: output too large"); return ALI_ERR_BAD_ARG; }
-  const size_t lds = (size_t)npx(obh, obw) * d.LDC * sizeof(float);
-  dim3 grid((unsigned)nblk, B);
-#define TSC(NT_) hipLaunchKernelGGL((tconv_scatter_kernel<NT_>), grid, dim3(256), lds, (hipStream_t)stream, d)
-  if (d.N <= 16) TSC(1);
-  else if (d.N <= 32) TSC(2);
-  else if (d.N <= 48) TSC(3);
-  else TSC(4);
+  if (npx(obh, obw) * pl.LDC * 4 > 64 * 1024 || npx(obh, obw) >= 65536) { set_error("ali_tconv_scatter: filter too large"); return ALI_ERR_BAD_ARG; }
+  pl.OBH = obh; pl.OBW = obw;
+  pl.ntx = (Wout + obw - 1) / obw;
+  pl.nblk = (long long)pl.ntx * ((Hout + obh - 1) / obh);
+  if (pl.nblk >= (1LL << 31)) { set_error("ali_tconv_scatter: output too large"); return ALI_ERR_BAD_ARG; }
+  pl.lds = (size_t)npx(obh, obw) * pl.LDC * sizeof(float);
+  pl.NT = pl.N <= 16 ? 1 : pl.N <= 32 ? 2 : pl.N <= 48 ? 3 : 4;
+  return ALI_OK;
+}
+
+struct TSWPlan {
+  int mnt;                  // tap tiles of 16: the instantiation tconvs_wgrad_mfma_kernel<mnt, 4>
+  int rb, bands;            // big rows per band (block), bands per image
+  size_t lds;
+  long long nblk;           // blocks = partial slabs
+  int64_t ws;               // workspace payload bytes (without the reserved head)
+};
+
+static int ts_plan_wgrad(int B, int P, int Q, int K, int R, int S, int stride, TSWPlan& pl) {
+  if (K != 64 || R < 1 || S < 1 || R * S > 32 || stride < 1 || stride > 4 || B <= 0 || P <= 0 || Q <= 0 ||
+      tuning().no_t1_mfma != 0) {
+    set_error("ali_tconv_scatter_wgrad: bad argument / unsupported shape (ali_tconv_scatter_wgrad_ws)");
+    return ALI_ERR_BAD_ARG;
+  }
+  pl.mnt = (R * S + 15) / 16;
+  // the band image ((rb - 1) * stride + R) x ((Q - 1) * stride + S), or the fold scratch where that is larger, in 64 KB
+  auto lds = [&](int r) {
+    const long long img = (((long long)((r - 1) * stride + R) * ((Q - 1) * stride + S)) + 3) & ~3LL;
+    return (size_t)std::max(img, 4LL * 4 * pl.mnt * 64 * 4) * sizeof(float);
+  };
+  int rb = 8;
+  while (rb > 1 && lds(rb) > 64 * 1024) rb >>= 1;
+  if (lds(rb) > 64 * 1024) { set_error("ali_tconv_scatter_wgrad: one band row of the map exceeds 64 KB of LDS"); return ALI_ERR_BAD_ARG; }
+  pl.rb = rb; pl.bands = (P + rb - 1) / rb; pl.lds = lds(rb);
+  pl.nblk = (long long)B * pl.bands;
+  if (pl.nblk > (1 << 20)) { set_error("ali_tconv_scatter_wgrad: more than 2^20 bands"); return ALI_ERR_BAD_ARG; }
+  pl.ws = (int64_t)pl.nblk * K * R * S * (int64_t)sizeof(float);
+  return ALI_OK;
+}
+
+extern "C" int32_t ali_tconv_scatter_plan(int32_t op, int32_t B, int32_t H, int32_t W, int32_t C, int32_t Hout,
+                                          int32_t Wout, int32_t NC, int32_t ostride, int32_t R, int32_t S,
+                                          int32_t stride, int32_t pad, int64_t* plan) {
+  if (!plan) { set_error("ali_tconv_scatter_plan: bad argument"); return ALI_ERR_BAD_ARG; }
+  for (int i = 0; i < 6; ++i) plan[i] = 0;
+  if (op == ALI_TS_OP_FWD) {
+    TSPlan pl = {};
+    const int rc = ts_plan_fwd(B, H, W, C, Hout, Wout, NC, ostride, R, S, stride, pad, pl);
+    if (rc) return rc;
+    plan[0] = pl.NT; plan[1] = pl.OBH; plan[2] = pl.OBW; plan[3] = (int64_t)pl.lds; plan[4] = pl.nblk * B;
+    return ALI_OK;
+  }
+  if (op == ALI_TS_OP_WGRAD) {
+    if (NC != 1 || ostride < 1 || Hout <= 0 || Wout <= 0 || pad < 0) {
+      set_error("ali_tconv_scatter_wgrad: bad argument / unsupported shape (ali_tconv_scatter_wgrad_ws)");
+      return ALI_ERR_BAD_ARG;
+    }
+    TSWPlan pl = {};
+    const int rc = ts_plan_wgrad(B, H, W, C, R, S, stride, pl);
+    if (rc) return rc;
+    plan[0] = pl.mnt; plan[1] = pl.rb; plan[2] = pl.bands; plan[3] = (int64_t)pl.lds; plan[4] = pl.nblk;
+    plan[5] = pl.ws + (int64_t)kWsReserved;
+    return ALI_OK;
+  }
+  set_error("ali_tconv_scatter_plan: bad op %d", op);
+  return ALI_ERR_BAD_ARG;
+}
+
+extern "C" int ali_tconv_scatter(const float* x, const float* w_nc, const float* bias, float* out, int32_t B, int32_t H,
+                                 int32_t W, int32_t C, int32_t Hout, int32_t Wout, int32_t NC, int32_t ostride, int32_t R,
+                                 int32_t S, int32_t stride, int32_t pad, int32_t act, float slope, ali_stream_t stream) {
+  if (!x || !w_nc || !out) {
+    set_error("ali_tconv_scatter: bad argument (needs 64 input channels, 1-2 output channels, <= 64 tap columns)");
+    return ALI_ERR_BAD_ARG;
+  }
+  TSPlan pl = {};
+  const int rc = ts_plan_fwd(B, H, W, C, Hout, Wout, NC, ostride, R, S, stride, pad, pl);
+  if (rc) return rc;
+  TSDesc d = {};
+  d.x = x; d.w = w_nc; d.bias = bias; d.out = out;
+  d.B = B; d.H = H; d.W = W; d.Hout = Hout; d.Wout = Wout; d.NC = NC; d.ostride = ostride; d.R = R; d.S = S;
+  d.stride = stride; d.pad = pad; d.act = act; d.slope = slope;
+  d.N = pl.N; d.LDC = pl.LDC; d.OBH = pl.OBH; d.OBW = pl.OBW; d.ntx = pl.ntx;
+  dim3 grid((unsigned)pl.nblk, B);
+#define TSC(NT_) case NT_: hipLaunchKernelGGL((tconv_scatter_kernel<NT_>), grid, dim3(256), pl.lds, (hipStream_t)stream, d); break
+  switch (pl.NT) { TSC(1); TSC(2); TSC(3); default: TSC(4); }
 #undef TSC
   return check_launch("tconv_scatter_kernel");
 }
@@ -997,49 +1077,34 @@ extern "C" int ali_tconv_scatter(const float* x, const float* w_nc, const float*
 // (see tconvs_wgrad_mfma_kernel) returns the workspace bytes the launch needs, 0 when the shape is not served
 extern "C" int64_t ali_tconv_scatter_wgrad_ws(int32_t B, int32_t P, int32_t Q, int32_t K, int32_t R, int32_t S,
                                               int32_t stride) {
-  if (K != 64 || R < 1 || S < 1 || R * S > 32 || stride < 1 || stride > 4 || B <= 0 || P <= 0 || Q <= 0 ||
-      tuning().no_t1_mfma != 0) return 0;
-  int rb = 8;
-  auto lds = [&](int r) {
-    const long long img = (((long long)((r - 1) * stride + R) * ((Q - 1) * stride + S)) + 3) & ~3LL;
-    return (size_t)std::max(img, 4LL * 4 * ((R * S + 15) / 16) * 64 * 4) * sizeof(float);
-  };
-  while (rb > 1 && lds(rb) > 64 * 1024) rb >>= 1;
-  if (lds(rb) > 64 * 1024) return 0;
-  const long long nblk = (long long)B * ((P + rb - 1) / rb);
-  if (nblk > (1 << 20)) return 0;
-  return (int64_t)nblk * K * R * S * (int64_t)sizeof(float) + (int64_t)kWsReserved;   // (incl. the reserved head)
+  TSWPlan pl = {};
+  if (ts_plan_wgrad(B, P, Q, K, R, S, stride, pl)) return 0;
+  return pl.ws + (int64_t)kWsReserved;       // (incl. the reserved head)
 }
 
 extern "C" int ali_tconv_scatter_wgrad(const float* big, const float* small, int32_t sstride, float* dw, int64_t s_k,
                                        int64_t s_tap, int32_t B, int32_t P, int32_t Q, int32_t K, int32_t H, int32_t W,
                                        int32_t R, int32_t S, int32_t stride, int32_t pad, void* ws, size_t ws_bytes,
                                        ali_stream_t stream) {
-  int64_t need = ali_tconv_scatter_wgrad_ws(B, P, Q, K, R, S, stride);
-  if (need > 0) need -= (int64_t)kWsReserved;
-  if (!big || !small || !dw || sstride < 1 || H <= 0 || W <= 0 || pad < 0 || need <= 0) {
+  if (!big || !small || !dw || sstride < 1 || H <= 0 || W <= 0 || pad < 0) {
     set_error("ali_tconv_scatter_wgrad: bad argument / unsupported shape (ali_tconv_scatter_wgrad_ws)");
     return ALI_ERR_BAD_ARG;
   }
+  TSWPlan pl = {};
+  const int rc = ts_plan_wgrad(B, P, Q, K, R, S, stride, pl);
+  if (rc) return rc;
   ws = ws_payload(ws);                       // (the head of every workspace holds the GEMM kernels' arrival counters)
   ws_bytes = ws_payload_bytes(ws_bytes);
-  if (!ws || ws_bytes < (size_t)need) { set_error("ali_tconv_scatter_wgrad: workspace too small"); return ALI_ERR_WORKSPACE; }
+  if (!ws || ws_bytes < (size_t)pl.ws) { set_error("ali_tconv_scatter_wgrad: workspace too small"); return ALI_ERR_WORKSPACE; }
   const int T = R * S;
-  int rb = 8;
-  const int mnt = (T + 15) / 16;
-  auto lds = [&](int r) {
-    const long long img = (((long long)((r - 1) * stride + R) * ((Q - 1) * stride + S)) + 3) & ~3LL;
-    return (size_t)std::max(img, 4LL * 4 * mnt * 64 * 4) * sizeof(float);
-  };
-  while (rb > 1 && lds(rb) > 64 * 1024) rb >>= 1;
   TSWDesc d = {};
   d.big = big; d.small = small; d.part = reinterpret_cast<float*>(ws);
   d.B = B; d.P = P; d.Q = Q; d.H = H; d.W = W; d.R = R; d.S = S; d.pad = pad; d.stride = stride; d.sstride = sstride;
-  d.RB = rb; d.bands = (P + rb - 1) / rb;
-  const int nblk = B * d.bands;
+  d.RB = pl.rb; d.bands = pl.bands;
+  const int nblk = (int)pl.nblk;
   hipStream_t st = (hipStream_t)stream;
-  if (mnt == 1) hipLaunchKernelGGL((tconvs_wgrad_mfma_kernel<1, 4>), dim3(nblk), dim3(256), lds(rb), st, d);
-  else hipLaunchKernelGGL((tconvs_wgrad_mfma_kernel<2, 4>), dim3(nblk), dim3(256), lds(rb), st, d);
+  if (pl.mnt == 1) hipLaunchKernelGGL((tconvs_wgrad_mfma_kernel<1, 4>), dim3(nblk), dim3(256), pl.lds, st, d);
+  else hipLaunchKernelGGL((tconvs_wgrad_mfma_kernel<2, 4>), dim3(nblk), dim3(256), pl.lds, st, d);
   hipLaunchKernelGGL(t1_reduce_kernel, dim3(K * T), dim3(64), 0, st, d.part, nblk, K, T, 1, dw, (long long)s_k,
                      (long long)s_tap, 0LL);
   return check_launch("tconvs_wgrad_mfma");

@@ -1075,6 +1075,22 @@ int64_t ali_tconv_scatter_wgrad_ws(int32_t B, int32_t P, int32_t Q, int32_t K, i
 int ali_tconv_scatter_wgrad(const float* big, const float* small, int32_t sstride, float* dw, int64_t s_k, int64_t s_tap,
                             int32_t B, int32_t P, int32_t Q, int32_t K, int32_t H, int32_t W, int32_t R, int32_t S,
                             int32_t stride, int32_t pad, void* ws, size_t ws_bytes, ali_stream_t stream);
+/* The launch plan of the two entry points above for a shape: the launch, ali_tconv_scatter_wgrad_ws and this query read
+ * one plan each.  `op` is an ALI_TS_OP_*; the arguments are those of ali_tconv_scatter -- for ALI_TS_OP_WGRAD: B, H, W, C
+ * = the 64-channel map (the launch's B, P, Q, K), Hout x Wout = the one-channel map, NC = 1, ostride = its sstride.
+ * Fills plan[0..5] and returns ALI_OK, or returns the error code with which the launch would refuse the shape
+ * (ali_last_error says why; a workspace that is too small is the launch's own refusal: compare plan[5]):
+ *   ALI_TS_OP_FWD   : NT (tconv_scatter_kernel<NT>), OBH, OBW (output tile of a block), LDS bytes, blocks, 0
+ *   ALI_TS_OP_WGRAD : NT (tconvs_wgrad_mfma_kernel<NT, 4>), RB (rows of a band), bands per image, LDS bytes, blocks,
+ *                     workspace bytes (= ali_tconv_scatter_wgrad_ws)
+ * Host arithmetic only: works without a GPU.  It reads ALI_NO_T1_MFMA like the launches do.  Every plan a shape can
+ * reach -- 19 forward, 8 weight-gradient -- and every template of ali_col2im is held to an fp64 reference by
+ * tests/test_gpu_scatter_routes.py. */
+#define ALI_TS_OP_FWD 0
+#define ALI_TS_OP_WGRAD 1
+int32_t ali_tconv_scatter_plan(int32_t op, int32_t B, int32_t H, int32_t W, int32_t C, int32_t Hout, int32_t Wout,
+                               int32_t NC, int32_t ostride, int32_t R, int32_t S, int32_t stride, int32_t pad,
+                               int64_t* plan);
 
 /* Tail of the spectrogram front-end (the step in front of the path): torchaudio.transforms.Spectrogram
  * (power 2) + (. + 1e-6).log() and, optionally, spect_to_img (audio_mnist.py:116,347-363 and copies).  `y` holds, per

@@ -1,8 +1,10 @@
 """The route of every parity case of the routed kernel families, held to a record: tests/golden/routes_recorded.json
-lists, for each case of tests/test_gpu_direct_routes.py (ali_tconv1_fwd / _dgrad / _wgrad) and of tests/bn_cases.py (the
+lists, for each case of tests/test_gpu_direct_routes.py (ali_tconv1_fwd / _dgrad / _wgrad), of
+tests/test_gpu_scatter_routes.py (ali_tconv_scatter / ali_tconv_scatter_wgrad) and of tests/bn_cases.py (the
 stand-alone BatchNorm passes, ali_colsum, ali_act_bwd; every row case with aligned and with misaligned operands), what
-the launches' own queries -- ``ops.tconv1_route`` and ``ops.ew_plan`` -- answered when it was written: the route and,
-for the element-wise family, the two block counts.  A change of the dispatch code that is meant to keep every route
+the launches' own queries -- ``ops.tconv1_route``, ``ops.tconv_scatter_plan`` and ``ops.ew_plan`` -- answered when it
+was written: the route and, for the element-wise family, the two block counts, for the scatter family the LDS bytes
+and the block count.  A change of the dispatch code that is meant to keep every route
 runs against it; no GPU is needed.  ``python tests/test_routes_recorded_cpu.py`` rewrites the record from the queries
 (after a deliberate change of a route, or with new cases)."""
 import contextlib
@@ -21,15 +23,20 @@ def _ops():
 
 def cases():
     """(case id, family, shape, env): family and shape as a family-agnostic query would take them -- tconv1_<op>: B, P, Q,
-    K, R, S, pad (wgrad: + nc, workspace bytes); the element-wise entries: rows per group, rows per image, C, ld, groups,
-    aligned"""
+    K, R, S, pad (wgrad: + nc, workspace bytes); tconv_scatter_<op>: the arguments of ``ops.tconv_scatter_plan`` after the
+    op; the element-wise entries: rows per group, rows per image, C, ld, groups, aligned"""
     import bn_cases as bc
     import test_gpu_direct_routes as dr
+    import test_gpu_scatter_routes as sr
     for c in dr.CASES:
         yield "direct:" + c.id, "tconv1_" + c.op, list(c.dims()) + ([c.nc, WS_BYTES] if c.op == "wgrad" else []), c.env
     for op, dims, nc in dr.REFUSED:
         yield (f"direct:refused-{op}-{'x'.join(map(str, dims))}", "tconv1_" + op,
                list(dims) + ([nc, WS_BYTES] if op == "wgrad" else []), {})
+    for c in sr.FWD + sr.WGRAD:
+        yield "scatter:" + c.id, "tconv_scatter_" + c.op, list(c.query()[1:]), {}
+    for what, q, _ in sr.REFUSED:
+        yield "scatter:refused-" + what, "tconv_scatter_" + q[0], list(q[1:]), {}
     for c in bc.ROW_CASES + bc.WIDE_CASES:
         for op in ("bn_stats", "bn_apply", "bn_bwd", "bn_bwd_from_partials"):
             g = c.groups if op in ("bn_stats", "bn_apply") else 1
@@ -48,6 +55,9 @@ def query(ops, family, shape, env):
         if family.startswith("tconv1_"):
             nc, ws = shape[7:] or (1, None)
             return ops.tconv1_route(family[7:], *shape[:7], nc=nc, ws_bytes=ws), [0, 0]
+        if family.startswith("tconv_scatter_"):
+            got = ops.tconv_scatter_plan(family[14:], *shape)
+            return (None, [0, 0]) if got is None else (got.name, [got.lds, got.blocks])
         rows, rpi, C, ld, groups, aligned = shape
         got = ops.ew_plan(family, rows, rpi, C, ld=ld, groups=groups, aligned=bool(aligned))
     return (None, [0, 0]) if got is None else (got[0], [got[1], got[2]])
@@ -75,13 +85,19 @@ def test_queries_answer_the_recorded_routes():
 
 
 def test_the_record_agrees_with_the_case_tables():
-    """the route a case table names for a case is the recorded one (the direct cases, the aligned row cases, colsum)"""
+    """the route a case table names for a case is the recorded one (the direct and the scatter cases, the aligned row
+    cases, colsum)"""
     import bn_cases as bc
     import test_gpu_direct_routes as dr
+    import test_gpu_scatter_routes as sr
     with open(RECORD) as f:
         recorded = {r["case"]: r for r in json.load(f)}
     for c in dr.CASES:
         assert recorded["direct:" + c.id]["route"] == c.route, c.id
+    for c in sr.FWD + sr.WGRAD:
+        assert recorded["scatter:" + c.id]["route"] == c.plan, c.id
+    for what, _, _ in sr.REFUSED:
+        assert recorded["scatter:refused-" + what]["route"] is None, what
     for c in bc.ROW_CASES + bc.WIDE_CASES:
         for op in ("bn_apply", "bn_bwd_from_partials"):
             assert recorded[f"bn:{c.id}:{op}:aligned"]["route"] == c.route, (c.id, op)
