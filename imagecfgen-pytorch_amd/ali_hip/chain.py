@@ -777,8 +777,19 @@ def wgrad_geoms(plan: ChainPlan, saved):
     return [sv.geom for sv in saved if sv.route.wgrad[0] != "tconv1"]
 
 
-def _param_grads(st: Stage, sv, g_pre, ld: int, grads, grad_dst, fold):
-    """Weight and bias gradient of the stage's module (nothing in the chain reads them: no yield) into ``grads``."""
+def _head_bwd_ok(st: Stage, sv, ld: int) -> bool:
+    """Does ``ops.head_bwd`` serve this stage's data gradient (and with it its parameter gradients)?  A GEMV head with
+    dense operands, every channel real and no BatchNorm in front, fp32 (the kernel reproduces the fp32 MFMA's bits, not
+    the fp16 one's) -- unless ALI_NO_HEAD_BWD=1 keeps it on the GEMM."""
+    return (sv.route.fwd == "head" and sv.route.wgrad[0] == "head" and sv.bn is None and ld == 0
+            and not ops._PRECISION["f16"]
+            and sv.c_log == sv.in_shape[3] and sv.t.is_contiguous() and sv.x_in.is_contiguous()
+            and (sv.mask is None or sv.mask.stride(1) == 1) and not ops.switched_off("ALI_NO_HEAD_BWD"))
+
+
+def _param_grads(st: Stage, sv, g_pre, ld: int, grads, grad_dst, fold, head_later: bool = False):
+    """Weight and bias gradient of the stage's module (nothing in the chain reads them: no yield) into ``grads``.
+    ``head_later``: a "head" stage's launch is left to ``_data_grad`` (one launch for both); returns its (dw, db)."""
     m, g = st.mod, sv.geom
     B, H, W, Cp = sv.in_shape
     _, P, Q, K = sv.out_shape
@@ -812,6 +823,8 @@ def _param_grads(st: Stage, sv, g_pre, ld: int, grads, grad_dst, fold):
         if ops.tconv_scatter_wgrad(sv.t, g_pre, 1, dw, dw.stride(0), dw.stride(3), B, H, W, Cp, P, Q, R, S, m.stride[0],
                                    m.padding[0]) is not None:
             return
+    if path == "head" and head_later:     # (the data gradient's launch writes them: _data_grad, head_bwd)
+        return dw.reshape(-1), fused_db
     if path == "head":                    # (a head never joins: ld == 0)
         ops.head_wgrad(sv.t.reshape(B, Cp)[:, :c_in], g_pre.reshape(B), dw.reshape(-1), db=fused_db)
     elif path == "first_direct":
@@ -869,15 +882,23 @@ def _plane_grads(plan: ChainPlan, st: Stage, sv, g_pre, gx_planes):
 
 
 def _data_grad(plan: ChainPlan, st: Stage, sv, g_pre, ld: int, pact, pslope, want: bool, need_params: bool, grads,
-               grad_dst):
+               grad_dst, head_pg=None):
     """Gradient of the pre-activation that produced the stage's input (activation ``pact``): the data-gradient GEMM
     folded with what sits between the two -- Dropout2d mask and act' in its epilogue, BatchNorm backward (whose
     parameter gradients go into ``grads``) fused with the LeakyReLU derivative.  Generator: yields after a GEMM
-    request.  ``want`` False: only the BatchNorm parameter gradients are needed (returns None)."""
+    request.  ``want`` False: only the BatchNorm parameter gradients are needed (returns None).
+    A GEMV head (``_head_bwd_ok``) is an outer product, not a GEMM: ``ops.head_bwd`` writes it, and with ``head_pg`` =
+    (dw, db) of ``_param_grads(head_later=True)`` the stage's parameter gradients in the same launch."""
     m, g, bn, rt = st.mod, sv.geom, sv.bn, sv.route
     B, H, W, Cp = sv.in_shape
     dact_y = sv.x_in if pact != ACT_NONE else None
     gt = torch.empty(sv.in_shape, dtype=torch.float32, device=g_pre.device)
+    if _head_bwd_ok(st, sv, ld):
+        dw, db = head_pg if head_pg is not None else (None, None)
+        ops.head_bwd(g_pre.reshape(B), plan.packed(st, "fwd", Cp).reshape(-1), dact_y, pact, pslope, sv.mask,
+                     gt.reshape(B, Cp), sv.t.reshape(B, Cp), dw, db)
+        yield                             # (where the GEMM's request was: the rounds of run_parallel stay as they are)
+        return gt
     bn_red = None
     if bn is None:
         ep = ops.epilogue(mask=sv.mask, dact_y=dact_y, dact=pact, dslope=pslope)
@@ -953,11 +974,13 @@ def chain_backward_gen(plan: ChainPlan, saved, gy: torch.Tensor, c_log_in: int, 
         st, sv = plan.stages[i], saved[i]
         assert not isinstance(sv.bn_stats, list), "grouped forward state: backpropagate slice_saved(saved, g, groups)"
         ld = gy_ld if i == n - 1 else 0          # pixel pitch of g_pre (0 = dense)
-        if need_params:
-            _param_grads(st, sv, g_pre, ld, grads, grad_dst, fold)
+        head_pg = None
+        if need_params:       # (a head's own gradients ride in its data-gradient launch when there is one)
+            head_pg = _param_grads(st, sv, g_pre, ld, grads, grad_dst, fold,
+                                   head_later=i > 0 and _head_bwd_ok(st, sv, ld))
         if i > 0:
             g_pre = yield from _data_grad(plan, st, sv, g_pre, ld, plan.stages[i - 1].act, plan.stages[i - 1].slope, True,
-                                          need_params, grads, grad_dst)
+                                          need_params, grads, grad_dst, head_pg)
     # ---- the first stage's data gradient: a few planes of it, none of it, or all of it
     gx = (yield from _plane_grads(plan, st, sv, g_pre, gx_planes)) if gx_planes is not None else None
     if gx is None and (need_gx or sv.bn is not None):

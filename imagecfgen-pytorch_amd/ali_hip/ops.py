@@ -823,6 +823,35 @@ def head_wgrad(x2d, g, dw, db=None):
     return dw
 
 
+def switched_off(name: str) -> bool:
+    """Is the A/B switch ``name`` (ALI_NO_HEAD_BWD, ALI_NO_GZ_CHAIN: routes chosen on the Python side)
+    set?  Read from the environment at every decision, so ``ops.tuning(ALI_NO_HEAD_BWD=1)`` holds for its block."""
+    import os
+    return os.environ.get(name, "0") not in ("", "0")
+
+
+def head_bwd(gl, w, y_prev, dact, dslope, mask, g, x2d=None, dw=None, db=None):
+    """The head's backward pass in one launch (include/ali_hip.h: ali_head_bwd): g[b, c] = gl[b] * w[c] * mask[b, c] *
+    act'(y_prev[b, c]) into the dense [B, C] ``g``; with ``dw`` also dw[c] = sum_b gl[b] * x2d[b, c] and db = sum_b gl[b].
+    ``mask`` ([B, C]) and ``x2d`` may be column ranges of wider buffers (any row stride); ``y_prev`` (dense [B, C];
+    needed when ``dact`` is an activation) and ``mask`` may be None."""
+    B, C = g.shape
+    if gl.numel() != B or w.numel() != C or (y_prev is not None and y_prev.numel() != B * C):
+        raise ValueError("head_bwd: operand shapes do not match g [B, C]")
+    if dw is not None and (x2d is None or tuple(x2d.shape) != (B, C) or x2d.stride(1) != 1 or dw.numel() != C):
+        raise ValueError("head_bwd: dw needs x2d [B, C] with unit column stride and C weights")
+    if mask is not None and (mask.shape[0] != B or mask.shape[1] < C or mask.stride(1) != 1):
+        raise ValueError("head_bwd: mask must be [B, >= C] with unit column stride")
+    ws = workspace(g.device)
+    _lib.check(_lib.load().ali_head_bwd(_chk(gl, "gl"), _chk(w, "w"), _opt(y_prev, "y_prev"), dact, dslope,
+                                        None if mask is None else _ptr(mask), 0 if mask is None else mask.stride(0),
+                                        _chk(g, "g"),
+                                        None if dw is None else _ptr(x2d), 0 if dw is None else x2d.stride(0),
+                                        _opt(dw, "dw"), _opt(db, "db"), B, C, c_void_p(ws.data_ptr()), ws.numel(),
+                                        _stream()), "ali_head_bwd")
+    return g
+
+
 def copy_multi(pairs):
     """[(dst, src), ...]: dst.copy_(src) for all pairs -- same-dtype contiguous CUDA pairs share one launch
     (include/ali_hip.h: ali_copy_multi), anything else falls back to Tensor.copy_."""

@@ -570,11 +570,20 @@ class AliStepper:
 
     def _d_real_all(self, cx):
         """The whole D-real phase on one GPU: nothing has to hide an all-reduce, so E'(x) and D.dx(x) -- independent
-        chains -- run side by side (chain.run_parallel) instead of one in front of the E+G optimiser step."""
+        chains -- run side by side (chain.run_parallel) instead of one in front of the E+G optimiser step.  G'(z) of
+        the D-fake phase depends on that optimiser step only, so it is the third chain of the same rounds: its GEMMs
+        ride in launches that exist anyway instead of paying for four of their own (ALI_NO_GZ_CHAIN=1: it stays in
+        ``_d_fake_pre``).  G and E have neither BatchNorm nor Dropout2d: no mask or statistic changes its turn."""
         x0d, n_log, masked = self._d_real_input(cx)
         x0e, _ = self._planes(cx["images"], cx["idx"], cx["cont"], self.family.e_tables)
-        cx["dx_pre"], (cx["ex_pre"], _) = run_parallel(self._dx_forward_gen(x0d, n_log, True, x_masked=masked),
-                                                       chain_forward_gen(self.pE, x0e, True, n_log, False))
+        gens = [self._dx_forward_gen(x0d, n_log, True, x_masked=masked), chain_forward_gen(self.pE, x0e, True, n_log, False)]
+        if not ops.switched_off("ALI_NO_GZ_CHAIN"):
+            gin, g_log = self._g_input(cx["zin"], cx["onehots"], cx["cont"])
+            gens.append(chain_forward_gen(self.pG, gin, True, g_log, False))
+        res = run_parallel(*gens)
+        cx["dx_pre"], cx["ex_pre"] = res[0], res[1][0]
+        if len(res) > 2:
+            cx["gz"] = res[2][0]
         self._d_real_rest(cx)
 
     def _d_real_rest(self, cx):
@@ -595,6 +604,8 @@ class AliStepper:
 
     def _d_fake_pre(self, cx):
         """G'(z): independent of the D update whose gradients may still be in the all-reduce."""
+        if "gz" in cx:                 # (one GPU: computed beside D.dx(x) and E'(x), _d_real_all)
+            return
         gin, g_log = self._g_input(cx["zin"], cx["onehots"], cx["cont"])
         cx["gz"], _ = chain_forward(self.pG, gin, True, g_log, False)
 

@@ -1047,6 +1047,112 @@ __global__ void __launch_bounds__(256) head_wgrad_kernel(const float* __restrict
   }
 }
 
+// The head's whole backward pass in one launch.  Data gradient towards the previous stage's pre-activation,
+//   g[b][c] = ((gl[b] * w[c] + 0) * mask[b][c]) * act'(y_prev[b][c]),
+// which is what the implicit GEMM with its one gathered channel leaves: the fp32 MFMA accumulator starts at +0 and takes
+// one product, the epilogue adds the absent bias (+0) and applies mask and act' in that order.
+__device__ __forceinline__ float head_bwd_value(float gv, float wv, bool has_mask, float mk, bool has_y, float yv, int dact,
+                                                float dslope) {
+  float v = gv * wv + 0.f;
+  if (has_mask) v *= mk;
+  if (has_y) v *= act_grad_from_output(yv, dact, dslope);
+  return v;
+}
+// data gradient only: 32 columns x 64 rows a block (8 row lanes x 8 rows in flight)
+__global__ void __launch_bounds__(256) head_bwd_kernel(const float* __restrict__ gl, const float* __restrict__ w,
+                                                       const float* __restrict__ yprev, int dact, float dslope,
+                                                       const float* __restrict__ mask, int mask_ld, float* __restrict__ g,
+                                                       int B, int C) {
+  const int cl = threadIdx.x & 31, rl = threadIdx.x >> 5;
+  const int c = blockIdx.x * 32 + cl;
+  if (c >= C) return;
+  const float wv = w[c];
+  const int b0 = (int)blockIdx.y * 64 + rl;
+  float gv[8], yv[8], mk[8];
+#pragma unroll
+  for (int u = 0; u < 8; ++u) {
+    const int b = b0 + 8 * u;
+    const bool ok = b < B;
+    gv[u] = ok ? gl[b] : 0.f;
+    yv[u] = (ok && yprev) ? yprev[(long long)b * C + c] : 0.f;
+    mk[u] = (ok && mask) ? mask[(long long)b * mask_ld + c] : 1.f;
+  }
+#pragma unroll
+  for (int u = 0; u < 8; ++u) {
+    const int b = b0 + 8 * u;
+    if (b < B) g[(long long)b * C + c] = head_bwd_value(gv[u], wv, mask != nullptr, mk[u], yprev != nullptr, yv[u], dact, dslope);
+  }
+}
+
+// ... and with dw / db.  head_wgrad_kernel keeps, per column, 8 row lanes x 8 accumulators: accumulator (rl, u) sums the
+// rows rl + 8u + 64k in ascending k, a lane's eight are combined as a tree, the lanes in order.  Those 64 accumulators
+// are independent, so here every one has a thread of its own and every row lane a block of its own (grid: column
+// blocks x 8): 8 x the blocks of head_wgrad_kernel and one pass over the rows for both gradients (32 blocks streaming
+// 512 rows each are latency bound).  A block leaves its lane's tree sums in the workspace; the block of a column block
+// that arrives last adds the 8 lanes in order (the hand-off of ali_reduce.h; no block waits).  Same sums, same order,
+// same bits.  db: one thread per row lane walks its rows in head_wgrad_kernel's order.  (Sums that start at +0 never
+// become -0, so the zero terms head_wgrad_kernel adds for rows past the end change nothing.)
+__global__ void __launch_bounds__(256) head_bwd_wg_kernel(const float* __restrict__ gl, const float* __restrict__ w,
+                                                          const float* __restrict__ yprev, int dact, float dslope,
+                                                          const float* __restrict__ mask, int mask_ld, float* __restrict__ g,
+                                                          const float* __restrict__ x, int ld, float* __restrict__ dw,
+                                                          float* __restrict__ db, int B, int C, float* part, int* ctr) {
+  __shared__ float red[8][33];
+  __shared__ int s_last;
+  const int cl = threadIdx.x & 31, u = threadIdx.x >> 5, rl = blockIdx.y;
+  const int c = blockIdx.x * 32 + cl;
+  const bool live = c < C;
+  const bool sum_g = blockIdx.x == 0 && threadIdx.x == 0 && db != nullptr;
+  const bool x_is_y = x == yprev && ld == C;
+  float acc = 0.f;
+  if (live) {
+    const float wv = w[c];
+#pragma unroll 8
+    for (int b = rl + 8 * u; b < B; b += 64) {
+      const float gv = gl[b], xv = x[(long long)b * ld + c];
+      const float yv = x_is_y ? xv : yprev ? yprev[(long long)b * C + c] : 0.f;
+      const float mk = mask ? mask[(long long)b * mask_ld + c] : 1.f;
+      g[(long long)b * C + c] = head_bwd_value(gv, wv, mask != nullptr, mk, yprev != nullptr, yv, dact, dslope);
+      acc += gv * xv;
+    }
+  }
+  red[u][cl] = acc;
+  float s0 = 0.f;
+  if (sum_g) {
+    for (int b0 = rl; b0 < B; b0 += 64)
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (b0 + 8 * k < B) s0 += gl[b0 + 8 * k];
+  }
+  __syncthreads();
+  if (u == 0) {
+    const float v = ((red[0][cl] + red[1][cl]) + (red[2][cl] + red[3][cl])) + ((red[4][cl] + red[5][cl]) + (red[6][cl] + red[7][cl]));
+    if (live) __hip_atomic_store(part + (long long)rl * C + c, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (sum_g) __hip_atomic_store(part + (long long)8 * C + rl, s0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // the partials are out before the block arrives
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int arrived = __hip_atomic_fetch_add(ctr + blockIdx.x, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    s_last = arrived == 7;
+    if (s_last) __hip_atomic_store(ctr + blockIdx.x, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // all 8 have arrived
+  }
+  __syncthreads();
+  if (!s_last || u != 0) return;
+  if (live) {
+    float v = __hip_atomic_load(part + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+    for (int r = 1; r < 8; ++r) v += __hip_atomic_load(part + (long long)r * C + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    dw[c] = v;
+  }
+  if (sum_g) {
+    float sg = __hip_atomic_load(part + (long long)8 * C, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+    for (int r = 1; r < 8; ++r) sg += __hip_atomic_load(part + (long long)8 * C + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    db[0] = sg;
+  }
+}
+
 // ---- several small device-to-device copies in one launch (the step's inputs into the captured graph's buffers) --------
 constexpr int kCopyJobs = 8;
 struct CopyJobs { int n; const unsigned* src[kCopyJobs]; unsigned* dst[kCopyJobs]; long long words[kCopyJobs]; int blk0[kCopyJobs + 1]; };
@@ -1246,6 +1352,32 @@ extern "C" int ali_head_wgrad(const float* x, int32_t ld, const float* g, float*
   if (!x || !g || !dw || B <= 0 || C <= 0 || ld < C) { set_error("ali_head_wgrad: bad argument"); return ALI_ERR_BAD_ARG; }
   hipLaunchKernelGGL(head_wgrad_kernel, dim3((C + 31) / 32), dim3(256), 0, ST(stream), x, ld, g, dw, db, B, C);
   return check_launch("head_wgrad_kernel");
+}
+
+extern "C" int ali_head_bwd(const float* gl, const float* w, const float* y_prev, int32_t dact, float dslope,
+                            const float* mask, int32_t mask_ld, float* g, const float* x, int32_t ld, float* dw, float* db,
+                            int32_t B, int32_t C, void* ws, size_t ws_bytes, ali_stream_t stream) {
+  if (!gl || !w || !g || B <= 0 || C <= 0 || (mask && mask_ld < C) || (dw && (!x || ld < C)) || (db && !dw) ||
+      (dact != ALI_ACT_NONE && !y_prev)) {
+    set_error("ali_head_bwd: bad argument");
+    return ALI_ERR_BAD_ARG;
+  }
+  if (dact == ALI_ACT_NONE) y_prev = nullptr;
+  const int cb = (C + 31) / 32;
+  if (!dw) {
+    hipLaunchKernelGGL(head_bwd_kernel, dim3(cb, (B + 63) / 64), dim3(256), 0, ST(stream), gl, w, y_prev, dact, dslope,
+                       mask, mask_ld, g, B, C);
+    return check_launch("head_bwd_kernel");
+  }
+  // the row lanes' partial sums [8][C] + [8] behind the reserved head, one arrival counter per column block in it
+  const size_t need = ((size_t)8 * C + 8) * sizeof(float);
+  if (!ws || ws_payload_bytes(ws_bytes) < need || cb > (int)(kWsReserved / sizeof(int))) {
+    set_error("ali_head_bwd: workspace too small (%zu bytes behind the reserved head needed)", need);
+    return ALI_ERR_WORKSPACE;
+  }
+  hipLaunchKernelGGL(head_bwd_wg_kernel, dim3(cb, 8), dim3(256), 0, ST(stream), gl, w, y_prev, dact, dslope, mask, mask_ld,
+                     g, x, ld, dw, db, B, C, reinterpret_cast<float*>(ws_payload(ws)), reinterpret_cast<int*>(ws));
+  return check_launch("head_bwd_wg_kernel");
 }
 
 extern "C" int ali_copy_multi(int32_t n, const void* const* src, void* const* dst, const int64_t* bytes, ali_stream_t stream) {

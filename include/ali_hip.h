@@ -1169,6 +1169,17 @@ int ali_head_fwd(const float* x, int32_t ld, const float* w, const float* bias, 
                  ali_stream_t stream);
 int ali_head_wgrad(const float* x, int32_t ld, const float* g, float* dw, float* db, int32_t B, int32_t C,
                    ali_stream_t stream);
+/* The head's backward pass in one launch, bit for bit what ali_conv_bwd_data (one gathered channel, mask and act'
+ * epilogue) followed by ali_head_wgrad leave:
+ *   g[b][c] = ((gl[b] * w[c]) * mask[b][c]) * act'(y_prev[b][c])      g, y_prev dense [B][C]; mask rows mask_ld apart
+ *   dw[c]   = sum_b gl[b] * x[b][c],  db[0] = sum_b gl[b]             x rows ld floats apart
+ * mask may be NULL; y_prev is read only when dact != ALI_ACT_NONE; dw == NULL: data gradient only (x, ld, db, ws unused).
+ * With dw the row lanes of ali_head_wgrad's sum run as blocks of their own and meet in ws (zero-filled once; 32 C + 32
+ * bytes behind the reserved head, whose first ceil(C / 32) counters the launch uses and leaves at 0): the block that
+ * arrives last adds them in ali_head_wgrad's order. */
+int ali_head_bwd(const float* gl, const float* w, const float* y_prev, int32_t dact, float dslope, const float* mask,
+                 int32_t mask_ld, float* g, const float* x, int32_t ld, float* dw, float* db, int32_t B, int32_t C,
+                 void* ws, size_t ws_bytes, ali_stream_t stream);
 /* n device-to-device copies (dst[i] <- src[i], bytes[i] each; pointers and sizes multiples of 4) in one launch per 8:
  * the per-step refresh of the input buffers a captured HIP graph reads. */
 int ali_copy_multi(int32_t n, const void* const* src, void* const* dst, const int64_t* bytes, ali_stream_t stream);
