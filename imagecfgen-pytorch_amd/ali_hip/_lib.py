@@ -58,6 +58,18 @@ class AliGemmJob(Structure):
     _fields_ = [("opaque", c_uint64 * 112)]
 
 
+class AliCatPlan(Structure):
+    _fields_ = [(n, c_int32) for n in ("grid", "threads", "tile_rows", "tiles", "tiles_per_block", "grid2", "threads2",
+                                       "lds_bytes")] + [("ws_bytes", c_uint64)]
+
+
+class AliCatMapArgs(Structure):
+    _fields_ = [("country", c_void_p), ("country_ld", c_int64), ("country_cf", c_void_p), ("country_cf_ld", c_int64),
+                ("native_rows", c_void_p), ("native_ld", c_int64), ("y", c_void_p * 2), ("v", c_void_p * 2),
+                ("node", c_int32), ("cf_mask", c_int32), ("out", c_void_p * 2), ("status", c_void_p),
+                ("logits_out", c_void_p), ("g_out", c_void_p), ("noise_out", c_void_p)]
+
+
 ACT_NONE, ACT_LEAKY, ACT_TANH = 0, 1, 2
 
 # name -> (restype, argtypes); every symbol include/ali_hip.h declares
@@ -165,6 +177,13 @@ SIGNATURES = {
                               c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ali_gumbel_posterior": (c_int32, [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_int32, c_int32,
                                       c_void_p, c_void_p, c_void_p]),
+    "ali_cat_plan": (c_int32, [c_int64, c_int32, c_int32, c_int32, c_int32, POINTER(AliCatPlan)]),
+    "ali_cat_theta_size": (c_int32, [c_int32, c_int32, c_int32, c_int32]),
+    "ali_cat_nll": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_int64,
+                              c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_float, c_void_p, c_void_p,
+                              c_void_p, c_void_p, c_size_t, c_void_p]),
+    "ali_cat_map": (c_int32, [c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int64, POINTER(AliCatMapArgs),
+                              c_uint64, c_void_p, c_uint64, c_void_p]),
     "ali_mse": (c_int32, [c_void_p, c_void_p, c_int64, c_float, c_int32, c_void_p, c_void_p, c_void_p, c_size_t,
                           c_void_p]),
     "ali_cf_recon": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_int32,

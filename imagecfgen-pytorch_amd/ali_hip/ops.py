@@ -1396,6 +1396,125 @@ def gumbel_posterior(logits, y, g=None, seed=0, dev_counter=None, offset=0, want
     return noise, g_out
 
 
+# ---- the AudioMNIST attribute SCM (csrc/cat.hip) ---------------------------------------------------------------------
+CAT_LOGITS, CAT_SAMPLE, CAT_DIFFER, CAT_ABDUCT, CAT_CF = range(5)
+CAT_ENTRY_NLL, CAT_ENTRY_GRAD, CAT_ENTRY_MAP = range(3)
+CAT_TRIES = 64
+CatPlan = collections.namedtuple("CatPlan", "grid threads tile_rows tiles tiles_per_block grid2 threads2 lds_bytes ws_bytes")
+
+
+def cat_plan(N, Cc, Cn, Ca, entry=CAT_ENTRY_GRAD) -> CatPlan:
+    """how ``entry`` runs N rows of an AudioMNIST graph with (Cc, Cn, Ca) classes: grid, row tile, workspace bytes
+    (include/ali_hip.h: ali_cat_plan).  A host query; the launches use the same function."""
+    pl = _lib.AliCatPlan()
+    _lib.check(_lib.load().ali_cat_plan(int(N), int(Cc), int(Cn), int(Ca), int(entry), byref(pl)), "ali_cat_plan")
+    return CatPlan(*(int(getattr(pl, f)) for f in CatPlan._fields))
+
+
+def cat_sizes(Cc, Cn, Ca):
+    """(floats of theta, floats of the tower buffer) in the layouts of include/ali_hip.h; raises outside [1, 64]"""
+    lib = _lib.load()
+    n = lib.ali_cat_theta_size(int(Cc), int(Cn), int(Ca), 0), lib.ali_cat_theta_size(int(Cc), int(Cn), int(Ca), 1)
+    if not n[0]:
+        raise ValueError(f"cat: class counts ({Cc}, {Cn}, {Ca}) outside [1, 64]")
+    return n
+
+
+def _cat_rows(t, name, N=None):
+    """(pointer, rows, classes, row stride) of fp32 CUDA rows [N, C]; a column range of a wider table passes"""
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[0] >= 1
+            and t.shape[1] >= 1 and (t.shape[1] == 1 or t.stride(1) == 1)):
+        raise ValueError(f"{name}: need non-empty fp32 CUDA rows [N, C] with unit column stride")
+    ld = t.stride(0) if t.shape[0] > 1 else t.shape[1]
+    if ld < t.shape[1] or (N is not None and t.shape[0] != N):
+        raise ValueError(f"{name}: {tuple(t.shape)} rows at stride {ld}" + ("" if N is None else f", {N} rows expected"))
+    return c_void_p(t.data_ptr()), t.shape[0], t.shape[1], ld
+
+
+def _cat_i64(t, N, name):
+    if t is None:
+        return None
+    if not (t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.numel() == N):
+        raise ValueError(f"{name}: need {N} contiguous int64 CUDA values")
+    return t.data_ptr()
+
+
+def cat_nll(theta, towers, country, native, accent, index=None, wgt=None, gscale=1.0, want_lp=True, want_out3=True,
+            want_grad=False, gtheta=None):
+    """The log-probabilities of native_speaker and accent given their parents (include/ali_hip.h: ali_cat_nll).
+    ``country`` / ``native`` / ``accent``: fp32 rows (see ``_cat_rows``) of one row count; ``index`` (int64 [N]): row n
+    reads source row index[n].  Returns (lp [N, 2] or None, out3 = [-mean(lp_n + lp_a), mean lp_n, mean lp_a] or None,
+    gtheta or None): gtheta = gscale * sum_n wgt[n] . d lp[n] / d theta, ``wgt`` [N, 2] or, None, 1 / N each."""
+    pc, R, Cc, sc = _cat_rows(country, "country")
+    pn, _, Cn, sn = _cat_rows(native, "native", R)
+    pa, _, Ca, sa = _cat_rows(accent, "accent", R)
+    nth, ntw = cat_sizes(Cc, Cn, Ca)
+    N = R if index is None else index.numel()
+    ix = _cat_i64(index, N, "index")
+    dev = country.device
+    lp = torch.empty(N, 2, dtype=torch.float32, device=dev) if want_lp else None
+    out3 = torch.empty(3, dtype=torch.float32, device=dev) if want_out3 else None
+    if gtheta is None and want_grad:
+        gtheta = torch.empty(nth, dtype=torch.float32, device=dev)
+    if wgt is not None and tuple(wgt.shape) != (N, 2):
+        raise ValueError(f"cat_nll: wgt must be [{N}, 2], got {tuple(wgt.shape)}")
+    ws = workspace(dev)
+    _lib.check(_lib.load().ali_cat_nll(_flow_vec(theta, nth, "theta"), _flow_vec(towers, ntw, "towers"), Cc, Cn, Ca,
+                                       pc, sc, pn, sn, pa, sa, ix, R, N, _opt(wgt, "wgt"), float(gscale), _opt(lp),
+                                       _opt(out3), None if gtheta is None else _flow_vec(gtheta, nth, "gtheta"),
+                                       c_void_p(ws.data_ptr()), ws.numel(), _stream()), "ali_cat_nll")
+    return lp, out3, gtheta
+
+
+def cat_map(mode, theta, towers, country, Cn, Ca, country_cf=None, native_rows=None, y=(None, None), v=(None, None),
+            node=0, cf_mask=0, seed=0, dev_counter=None, offset=0, want_logits=False, want_g=False, want_noise=False):
+    """The three mechanisms row-wise in one launch (include/ali_hip.h: ali_cat_map).  ``y`` / ``v``: pairs (native_speaker,
+    accent) of int64 [N] classes or None.  Returns a dict: "out" (pair of int64 [N], None where the mode writes none),
+    "status" (int32 [N], CAT_DIFFER), "logits" / "g" / "noise" (the stored intermediates, on request; "noise" always for
+    CAT_ABDUCT)."""
+    pc, N, Cc, sc = _cat_rows(country, "country")
+    nth, ntw = cat_sizes(Cc, Cn, Ca)
+    dev, Ct = country.device, Cn + Ca
+    a = _lib.AliCatMapArgs()
+    a.country, a.country_ld = pc, sc
+    if country_cf is not None:
+        a.country_cf, _, Ccf, a.country_cf_ld = _cat_rows(country_cf, "country_cf", N)
+        if Ccf != Cc:
+            raise ValueError("cat_map: country_cf must have country's width")
+    if native_rows is not None:
+        a.native_rows, _, Cnr, a.native_ld = _cat_rows(native_rows, "native_rows", N)
+        if Cnr != Cn:
+            raise ValueError(f"cat_map: native_rows must be [{N}, {Cn}]")
+    for j in range(2):
+        a.y[j] = _cat_i64(y[j], N, "y")
+        a.v[j] = _cat_i64(v[j], N, "v")
+    a.node, a.cf_mask = int(node), int(cf_mask)
+    res = {"out": [None, None], "status": None, "logits": None, "g": None, "noise": None}
+    if mode in (CAT_SAMPLE, CAT_DIFFER, CAT_CF):
+        for j in range(2):
+            if mode == CAT_CF or y[j] is None:
+                res["out"][j] = torch.empty(N, dtype=torch.int64, device=dev)
+                a.out[j] = res["out"][j].data_ptr()
+    if mode == CAT_DIFFER:
+        res["status"] = torch.empty(N, dtype=torch.int32, device=dev)
+        a.status = res["status"].data_ptr()
+    if want_logits or mode == CAT_LOGITS:
+        res["logits"] = torch.empty((2, N, Ct) if mode == CAT_CF else (N, Ct), dtype=torch.float32, device=dev)
+        a.logits_out = res["logits"].data_ptr()
+    if want_g and mode != CAT_LOGITS:
+        shape = (CAT_TRIES, N, Ca if node else Cn) if mode == CAT_DIFFER else (N, Ct)
+        res["g"] = torch.zeros(shape, dtype=torch.float32, device=dev)
+        a.g_out = res["g"].data_ptr()
+    if mode == CAT_ABDUCT or (want_noise and mode == CAT_CF):
+        res["noise"] = torch.empty(N, Ct, dtype=torch.float32, device=dev)
+        a.noise_out = res["noise"].data_ptr()
+    _lib.check(_lib.load().ali_cat_map(int(mode), _flow_vec(theta, nth, "theta"), _flow_vec(towers, ntw, "towers"), Cc,
+                                       Cn, Ca, N, byref(a), *_rng_args(seed, dev_counter)[:2],
+                                       int(offset) & (2 ** 64 - 1), _stream()), "ali_cat_map")
+    res["out"] = tuple(res["out"])
+    return res
+
+
 def softmax_xent(logit, target, gscale=1.0, want_grad=True, want_pred=False, hits_accum=None):
     """Cross-entropy of [B, C] logits against probability rows, gradient, arg-max and hit count in one launch
     (include/ali_hip.h: ali_softmax_xent).  Returns (out2 = [mean loss, hits] device tensor, glogit or None,

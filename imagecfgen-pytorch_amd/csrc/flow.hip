@@ -20,6 +20,7 @@
 // partials, so thread 0's drain before the arrival covers all of them.  The last block then applies the Jacobians of
 // cumsum, softmax, softplus and sigmoid once and writes gtheta.
 #include "ali_reduce.h"
+#include "ali_gumbel.h"
 
 #include <float.h>
 
@@ -477,13 +478,7 @@ flow_map_kernel(const float* in, const float* __restrict__ val, float* out, floa
 }
 
 // ---------------------------------------------------------------------------------------------- ali_gumbel_posterior
-constexpr int kGumbelWaves = 4;
-
-// Gumbel(0, 1) = -log(-log u), u = (k + 0.5) / 2^24 strictly inside (0, 1): the top 24 bits of the hash of element e
-__device__ __forceinline__ float gumbel_at(uint64_t key, uint64_t e) {
-  const double u = ((double)hi24(hash_at(key, e)) + 0.5) * (double)kInv24;
-  return (float)-log(-log(u));
-}
+constexpr int kGumbelWaves = 4;   // (the draw and the posterior's formula: ali_gumbel.h)
 
 __global__ void __launch_bounds__(kGumbelWaves * 64)
 gumbel_posterior_kernel(const float* __restrict__ logits, const long long* __restrict__ y, const float* __restrict__ g_in,
@@ -508,7 +503,7 @@ gumbel_posterior_kernel(const float* __restrict__ logits, const long long* __res
     for (int j = lane; j < C; j += 64) {
       const float gf = g_in ? g_in[n * C + j] : gumbel_at(key, offset + (uint64_t)(n * C + j));
       const double zj = (double)z[j];
-      double v = j == yc ? gy + lse - zy : -log(exp(-(double)gf - zj) + ey) - zj;
+      double v = gumbel_posterior_at(j == yc, (double)gf, zj, gy, zy, ey, lse);
       if (!ok) v = NAN;
       noise[n * C + j] = (float)v;
       if (g_out) g_out[n * C + j] = gf;

@@ -728,6 +728,84 @@ int ali_gumbel_posterior(const float* logits, const int64_t* y, const float* g, 
                          const int64_t* dev_counter, uint64_t offset, int32_t N, int32_t C, float* noise, float* g_out,
                          ali_stream_t stream);
 
+/* The AudioMNIST attribute SCM (attribute_scms/audio_mnist.py: the statement); csrc/cat.hip.
+ *   native_speaker  logits = W4 relu(W3 relu(W2 relu(W1 c + b1) + b2) + b3) + b4, c the country row, 128 wide
+ *   accent          logits = V2 relu(V1 [tower_c(c) | tower_n(n)] + c1) + c2, n the native_speaker row, each tower
+ *                   Linear(C, 64) ReLU Linear(64, 64) ReLU Linear(64, 64) ReLU Linear(64, 64), frozen
+ * Cc, Cn, Ca (classes of country_of_origin, native_speaker, accent) lie in [1, 64], N in [1, 2^24): anything else is
+ * ALI_ERR_BAD_ARG before any launch.  Weights are torch Linear's [out][in], row-major.
+ *   theta  (trained, ali_cat_theta_size(Cc, Cn, Ca, 0) floats):
+ *          W1[128][Cc] b1[128] W2[128][128] b2[128] W3[128][128] b3[128] W4[Cn][128] b4[Cn] | V1[64][128] c1[64]
+ *          V2[Ca][64] c2[Ca]
+ *   towers (frozen, ali_cat_theta_size(Cc, Cn, Ca, 1) floats): tower_c then tower_n, each
+ *          A1[64][C] a1[64] A2[64][64] a2[64] A3[64][64] a3[64] A4[64][64] a4[64]
+ * Context and target rows are fp32 rows at a row stride (in floats, >= the width, <= 2^16), read as dense rows.  The
+ * matrix products run on the fp64 MFMA (fp32 operands are exact in it, activations stay fp64 between layers) and every
+ * result is rounded to fp32 once.  Sums over rows have fixed orders, no float atomics: the same inputs give the same bits.
+ *
+ * ali_cat_plan (host only): how entry (AliCatEntry) runs N rows -- a grid of `grid` blocks of `threads` threads, block b
+ *   taking the row tiles t = b, b + grid, ... < tiles (at most tiles_per_block of them), tile t being rows
+ *   [t * tile_rows, min(N, (t + 1) * tile_rows)); grid2 x threads2: the weight-gradient launch of ALI_CAT_ENTRY_GRAD;
+ *   ws_bytes: the workspace the entry needs (0 for ali_cat_map).  The launches use the same function.
+ *
+ * ali_cat_nll: row n reads source row index[n] (int64, optional; src_rows = rows of the tables, ignored without index)
+ *   of country, native and accent; a row's class is the first maximum of its target row.  An index outside
+ *   [0, src_rows) is not checked (device data): such a row reads nothing, its lp is NaN.
+ *   lp [N][2] (optional) = log softmax(logits)[class] of native_speaker and accent, the log-softmax max-shifted in fp64;
+ *   out3 (optional) = {-mean(lp_n + lp_a), mean lp_n, mean lp_a};
+ *   gtheta (optional, theta's layout; the second launch) = gscale * sum_n (wgt[n][0] d lp_n + wgt[n][1] d lp_a) / d theta,
+ *   wgt [N][2] or, NULL, 1 / N each.  A ReLU passes the gradient where its pre-activation is > 0.  The towers get none.
+ *   The arrival counter (last int of the reserved head) is left at zero.
+ *
+ * ali_cat_map: one launch, row-wise, mode (AliCatMode) over AliCatMapArgs.  Every decision is the first maximum of the
+ *   fp64 sums of stored fp32 values: the logits rounded to fp32 (logits_out [N][Cn + Ca], native_speaker's columns
+ *   first; ALI_CAT_CF: [2][N][Cn + Ca], observed then counterfactual parents) plus the draws g (g_out) or the noise
+ *   (noise_out [N][Cn + Ca]).  Draws are ali_gumbel_posterior's: g = gumbel(element e) of the stream keyed by (seed,
+ *   *dev_counter); a call uses the elements from `offset` on as stated per mode.  Classes are int64; a class outside
+ *   its range is not checked (device data): as a parent it is a zero row, as an observation its noise is NaN.
+ *   ALI_CAT_LOGITS  logits_out for country and native_rows (dense, optional) or the one-hot of y[0]
+ *   ALI_CAT_SAMPLE  native_speaker then accent, each held (y[node] given) or drawn: out[node] = argmax(logits + g), g at
+ *                   e = offset + n (Cn + Ca) + col, col the node's column in logits_out; g_out [N][Cn + Ca]
+ *   ALI_CAT_DIFFER  like SAMPLE, but node `node` is drawn up to ALI_CAT_TRIES times, try t at e = offset + (t N + n) C +
+ *                   class (C the node's classes), keeping the first try whose class is not v[node][n]; status[n] = 1
+ *                   when none is (out holds the last try).  g_out [ALI_CAT_TRIES][N][C] (optional) makes it draw and
+ *                   store every try.  The other node's draws lie behind the tries: offset + ALI_CAT_TRIES N C + the
+ *                   SAMPLE element.
+ *   ALI_CAT_ABDUCT  noise_out = the Gumbel posterior (ali_gumbel_posterior's formulas on the fp32 logits) of the observed
+ *                   y[0] under country and of y[1] under (country, y[0]); g as in SAMPLE
+ *   ALI_CAT_CF      abduction as above, then native_speaker before accent under country_cf (NULL: country): a node in
+ *                   cf_mask (bit 0 native_speaker, bit 1 accent) takes v[node], another argmax(logits(counterfactual
+ *                   parents) + noise) -> out[node] */
+#define ALI_CAT_TRIES 64
+typedef enum { ALI_CAT_LOGITS = 0, ALI_CAT_SAMPLE = 1, ALI_CAT_DIFFER = 2, ALI_CAT_ABDUCT = 3, ALI_CAT_CF = 4 } AliCatMode;
+typedef enum { ALI_CAT_ENTRY_NLL = 0, ALI_CAT_ENTRY_GRAD = 1, ALI_CAT_ENTRY_MAP = 2 } AliCatEntry;
+typedef struct AliCatPlan {
+  int32_t grid, threads, tile_rows, tiles, tiles_per_block, grid2, threads2, lds_bytes;
+  uint64_t ws_bytes;
+} AliCatPlan;
+typedef struct AliCatMapArgs {
+  const float* country;     int64_t country_ld;
+  const float* country_cf;  int64_t country_cf_ld;
+  const float* native_rows; int64_t native_ld;
+  const int64_t* y[2];      /* classes of native_speaker, accent: held (SAMPLE, DIFFER; NULL = drawn) or observed */
+  const int64_t* v[2];      /* CF: the values of the nodes in cf_mask; DIFFER: v[node] = the forbidden classes */
+  int32_t node, cf_mask;
+  int64_t* out[2];
+  int32_t* status;
+  float* logits_out;
+  float* g_out;
+  float* noise_out;
+} AliCatMapArgs;
+int ali_cat_plan(int64_t N, int32_t Cc, int32_t Cn, int32_t Ca, int32_t entry, AliCatPlan* plan);
+int32_t ali_cat_theta_size(int32_t Cc, int32_t Cn, int32_t Ca, int32_t towers); /* 0: a class count out of range */
+int ali_cat_nll(const float* theta, const float* towers, int32_t Cc, int32_t Cn, int32_t Ca, const float* country,
+                int64_t sc, const float* native, int64_t sn, const float* accent, int64_t sa, const int64_t* index,
+                int64_t src_rows, int64_t N, const float* wgt, float gscale, float* lp, float* out3, float* gtheta,
+                void* ws, size_t ws_bytes, ali_stream_t stream);
+int ali_cat_map(int32_t mode, const float* theta, const float* towers, int32_t Cc, int32_t Cn, int32_t Ca, int64_t N,
+                const AliCatMapArgs* args, uint64_t seed, const int64_t* dev_counter, uint64_t offset,
+                ali_stream_t stream);
+
 /* The counterfactual metrics family (train_morphomnist_ae.py, morphomnist_cf_metrics.py, mnist_oracle_scores.py);
  * csrc/cfmetrics.hip.  fp32 in and out, fp64 sums in a fixed order, no float atomics: bit-identical from run to run.
  *
